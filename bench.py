@@ -6,7 +6,12 @@ frontend.input_size 80, residual_dropout 0.1, synthetic 80-d fbank x 1000 frames
 B = 32 utterances per GPU, 16-bit MFMA operands / fp32 accumulate.  One step = zero grads, forward, backward,
 ONE gradient all-reduce (N>1), clip + Adam + Noam update: nothing is skipped in the timed region.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+--dump-outputs DIR writes what the last of the K timed steps computed as DIR/<name>.npy (train: loss.npy, params.npy and
+grads.npy -- a fixed seeded sample of 2^20 of the updated parameters and of their gradients --, optimizer.npy; decode: hyps.npy,
+scores.npy).  The inputs and weights are seeded, so two builds run with the same flags compare output for output -- within a
+tolerance: two runs of one build already differ in the last bits (loss ~1e-6 relative, parameters ~2e-7).
 
 N > 1 without a torchrun environment re-launches itself as `python -m torch.distributed.run --nnodes=1
 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same flags>` (one rank per GPU over RCCL); under
@@ -74,7 +79,45 @@ def parse():
     ap.add_argument('--opt-in-graph', default='on', choices=['on', 'off'],
                     help='N = 1: capture the optimizer launches in the step graph too (on) or issue them eagerly behind the replay (off)')
     ap.add_argument('--cpu-threads', type=int, default=0, help='torch threads of the CPU baseline (0 = best of 16 / 32 / 64)')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, '
+                         'a fixed seeded sample of the parameter-sized outputs): two builds run with the same flags compare output for output')
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
+
+
+DUMP_SAMPLE = 1 << 20       # elements kept of each parameter-sized output (4 MB in float32; the AISHELL model has 36.5 M parameters)
+
+
+def dump_outputs(out_dir, arrays):
+    """write {name: float32 / float64 array} as out_dir/<name>.npy"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
+def train_step_outputs(run, loss):
+    """what a caller of the timed train step holds after it: the loss of the step, and the model's parameters (updated by the
+    step's optimizer) and their gradients as the step left them in .grad (loss-scaled in fp16 mode), in model.parameters() order --
+    the two parameter-sized outputs as the same fixed, seeded sample of DUMP_SAMPLE positions on every run"""
+    import numpy as np
+    params = run['dp'].params
+    with torch.no_grad():
+        flat_p = torch.cat([p.detach().reshape(-1) for p in params]).float()
+        flat_g = torch.cat([p.grad.detach().reshape(-1) for p in params]).float()
+    n = flat_p.numel()
+    if n > DUMP_SAMPLE:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))).to(flat_p.device)
+        flat_p, flat_g = flat_p[idx], flat_g[idx]
+    st = run['opt'].stats()
+    return {'loss': np.array([loss], dtype=np.float64),
+            'params': flat_p.cpu().numpy(), 'grads': flat_g.cpu().numpy(),
+            'optimizer': np.array([st[k] for k in ('step', 'lr', 'grad_sqnorm', 'loss_scale', 'skipped', 'faults')], dtype=np.float64)}
 
 
 def relaunch_under_torchrun(args):
@@ -293,10 +336,13 @@ def decode_task(args):
     spec = importlib.util.spec_from_file_location('decode_bench', os.path.join(ROOT, 'tools', 'decode_bench.py'))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    argv = ['--mode', args.mode, '--iters', str(max(1, min(args.steps, 5))), '--warmup', str(max(1, min(args.warmup, 2)))]
+    argv = ['--mode', args.mode, '--iters', str(args.steps), '--warmup', str(args.warmup)]
     if args.no_cpu_baseline:
         argv.append('--no-cpu-baseline')
-    mod.main(argv)
+    outputs = {} if args.dump_outputs else None
+    mod.main(argv, outputs=outputs)
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
 
 
 def main():
@@ -475,6 +521,8 @@ def main():
 
     # ---- untimed extras: where the step time goes (every rank: the collectives must match)
     final_loss, final_stats = float(loss_buf.item()), opt.stats()      # state at the end of the timed region
+    if args.dump_outputs and rank == 0:       # before the extras below run more steps on the same replica
+        dump_outputs(args.dump_outputs, train_step_outputs(run, final_loss))
     parts = {}
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
     windows = None

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/*.npz by running the REAL reference (/root/reference) on CPU.
+"""Generate tests/golden/* by running the REAL reference (/root/reference) on CPU.
 
 TEST INFRASTRUCTURE.  Run in the build container only (the GPU box has no /root/reference):
     python oracle/make_golden.py
@@ -441,6 +441,25 @@ def golden_variants(c1_batch=None):
                      store_full_grads=['encoder.blocks.0.feed_forward.w_1.weight', 'decoder.blocks.1.feed_forward.w_1.bias'])
 
 
+def golden_registry():
+    """tests/golden/registry_switch.json: what tests/test_registry_switch.py compares the drop-in classes with -- the signatures of
+    the reference classes a caller relies on, and the state_dict keys / shapes / tied keys of the reference models built from the
+    test's yaml dicts"""
+    import importlib
+    import json
+    from tests import test_registry_switch as T
+    sigs = {}
+    for modpath, cls, methods in T.PAIRS:
+        c = getattr(importlib.import_module(modpath), cls)
+        for m in methods:
+            sigs['%s.%s.%s' % (modpath, cls, m)] = T.signature_record(getattr(c, m))
+    sds = {name: T.state_dict_record(End2EndModel['speech2text'](make())) for name, make in T.CONFIGS.items()}
+    with open(os.path.join(OUT, 'registry_switch.json'), 'w') as f:
+        json.dump({'signatures': sigs, 'state_dicts': sds}, f, indent=1, sort_keys=True)
+        f.write('\n')
+    print('registry_switch.json', len(sigs), 'signatures', {k: len(v['shapes']) for k, v in sds.items()})
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
@@ -481,8 +500,11 @@ if __name__ == '__main__':
         golden_optimizer()
     elif len(sys.argv) > 1 and sys.argv[1] == 'rnnlm':
         golden_decode_rnnlm()
+    elif len(sys.argv) > 1 and sys.argv[1] == 'registry':
+        golden_registry()
     else:
         main()
         golden_tools()
         golden_data()
         golden_bucket()
+        golden_registry()

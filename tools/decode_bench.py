@@ -12,6 +12,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -43,7 +44,9 @@ def timed(fn, iters, warmup=1):
     return (time.perf_counter() - t0) / iters, out
 
 
-def main(argv=None, emit=True):
+def main(argv=None, emit=True, outputs=None):
+    """outputs: a dict that receives what the last timed call of the hipGraph loop returned -- 'hyps' [batch, nbest, max_len]
+    (token ids as float32, -1 past the end) and 'scores' [batch, nbest] (float64)"""
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=8)
     ap.add_argument('--frames', type=int, default=1000)
@@ -74,6 +77,14 @@ def main(argv=None, emit=True):
         hyps[tag] = [u[0] for u in h]
         res[tag] = {'s_per_batch': t, 'utt_per_s': args.batch / t,
                     'ms_per_step': (t - t_enc) * 1e3 / args.max_len}
+        if tag == 'cached_hipgraph' and outputs is not None:
+            unit2idx = {u: i for i, u in idx2unit.items()}
+            ids = np.full((len(h), max(len(u) for u in h), args.max_len), -1.0, dtype=np.float32)
+            for b, nb in enumerate(h):
+                for k, hyp in enumerate(nb):
+                    tok = [unit2idx[u] for u in hyp.split()]
+                    ids[b, k, :len(tok)] = tok
+            outputs.update(hyps=ids, scores=torch.as_tensor(s).double().cpu().numpy())
     same = sum(a == b for a, b in zip(hyps['reforward'], hyps['cached_hipgraph']))
     out = {'metric': 'decode utterances/sec (C5: beam %d + TransformerLM fusion, max_len %d, %d frames)'
                      % (args.beam, args.max_len, args.frames),
