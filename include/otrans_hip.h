@@ -43,32 +43,19 @@ extern "C" {
 int32_t otr_version(void);
 /* OTR_BF16 or OTR_F16: the 16-bit type this library was built for */
 int32_t otr_half_type(void);
-/* tuning hook for benchmarks: key 0 = force GEMM tile (0 auto / 64 / 128), key 1 = force split-K (0 auto),
- * key 2 = 1: generic (bounds-checked) loaders only, key 3 = 1: no persistent tile loop, key 4 = ablation bits of the split FFN
- * kernels (ffn3.hip: 1 no weight DMA, 2 no MFMA, 4 no tile stores, 8 no tile loads, 16 clock stamps into otr_debug_trace's buffer;
- * timing only), key 5 retired, key 6 = 0/1: 256-wide
- * weight-gradient launch off / on (-1: environment OTR_WGRAD256), key 7 = its workgroup count (0 = one per CU), key 8 = its ablation / cache
- * policy switches (wgrad256.h), key 9 = the shortest contraction it takes, key 10 = ablations of otr_conv2_dgrad (1 = no mask loads /
- * result stores, 2 = every operand load from one line: timing only, results are garbage), key 11 = bound of every in-kernel
- * turnstile / arrival spin (<= 0: the default 2^22; tests force a give-up with 1), key 12 = 1: the split FFN kernels exchange their
- * partial sums with write-through stores / memory-served loads only (the path a row block split across XCDs takes), key 13 = 1:
- * attention backward as two launches (dQ, then dK/dV) instead of one, key 15 = workgroup mapping of the split FFN kernels (1, the
- * default: an XCD owns one weight slice; 0: the four slices of a row block share an XCD), key 16 = workgroup mapping of the
- * attention launches (1, the default: the blocks of one (head, utterance) on one XCD; 0: the plain 3-D grid), key 17 = 1: conv1
- * forward on the VALU stencil for every shape (default: the fp32 matrix pipe for 64 channels and 16-bit activations), key 18 = 0:
- * the 768-column row-block projection on one workgroup per row block (default: two, 384 columns each), key 19 = 0: 4-wave workgroups
- * for the 256-column row-block kernels (default: 8 waves), key 20 = 0: 4-wave (64 queries / keys) workgroups for the attention launches
- * (default: 8 waves, 128 queries / keys, for aligned 16-bit operands with head dim 64), key 21 = 0: the streamed attention backward instead of
- * csrc/encattn.hip, key 22 = conv2 forward on the weight-stationary kernel (1) or the implicit GEMM (0), key 23 = utterances per workgroup of
- * the fused decoder launches (0 = the library's choice), key 24 / 25 = forms of the cached decode self-attention / the beam top-k (25 = 2: the
- * arg-max rounds), key 26 = 0: natural GEMM tile order, key 27 = 0: scalar loads of the relative-position score term, key 28 = resident
- * workgroups of the persistent 64 x 64-tile GEMM (1024; 512 = round 5), key 29 = 0: conv2's weight gradient of a 256-channel frontend on the
- * transposing GEMM instead of the gathered-row form of wgrad256.hip, key 30 = 0: no sliced parity-class input gradient for 256 output channels,
- * key 31 = 0: otr_conv2_dgrad_wide answers "not served", key 32 = ablation bits of csrc/conv2wide.hip (1 no MFMAs, 2 one fragment read per chunk,
- * 4 no weight DMA, 8 no row reloads), key 33 = csrc/encattn96.hip: bit 0 = it serves (0: the streamed dQ + dK/dV pair), bits 1-3 = its ablations
- * (2 no score-term loads, 4 no d bias stores, 8 no tiles), key 34 = 0: conv2 forward's implicit-im2col operand on the bounds-checked loader, key 37 = the narrowest x operand the 256-wide weight-gradient
- * launch takes (96; 128 = round 5).
- * Ablations are for timing only: results are garbage. */
+/* tuning hook for benchmarks and tests' reference paths: key 0 = force GEMM tile (0 auto / 64 / 128), key 1 = force split-K (0 auto),
+ * key 6 = 0/1: 256-wide weight-gradient launch off / on (-1: environment OTR_WGRAD256), key 7 = its workgroup count (0 = one per CU),
+ * key 11 = bound of every in-kernel turnstile / arrival spin (<= 0: the default 2^22; tests force a give-up with 1), key 12 = 1: the
+ * split FFN kernels exchange their partial sums with write-through stores / memory-served loads only (the path a row block split across
+ * XCDs takes), key 13 = 1: attention backward as two launches (dQ, then dK/dV) instead of one, key 15 = workgroup mapping of the split
+ * FFN kernels (1, the default: an XCD owns one weight slice; 0: the four slices of a row block share an XCD), key 16 = workgroup mapping
+ * of the attention launches (1, the default: the blocks of one (head, utterance) on one XCD; 0: the plain 3-D grid), key 21 = 0: the
+ * streamed attention backward instead of csrc/encattn.hip, key 22 = conv2 forward on the weight-stationary kernel (1) or the implicit
+ * GEMM (0), key 23 = utterances per workgroup of the fused decoder launches (0 = the library's choice), key 24 / 25 = forms of the cached
+ * decode self-attention / the beam top-k (25 = 2: the arg-max rounds), key 29 = 0: conv2's weight gradient of a 256-channel frontend on
+ * the transposing GEMM instead of the gathered-row form of wgrad256.hip, key 30 = 0: no sliced parity-class input gradient for 256
+ * output channels, key 31 = 0: otr_conv2_dgrad_wide answers "not served", key 33 = 0: the streamed dQ + dK/dV pair instead of
+ * csrc/encattn96.hip.  Any other key is refused (returns -1). */
 int32_t otr_debug_set(int32_t key, int32_t value);
 /* Register the caller-owned, zero-initialised DEVICE word that spin-bounded kernels (the turnstile of the 256-wide
  * weight-gradient launch; NULL = none) add 1 to whenever a wait gives up -- the results of such a launch may be wrong sums.

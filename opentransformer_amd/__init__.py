@@ -19,7 +19,7 @@ from .nn import (ConvFrontEnd, TransformerEncoder, TransformerEncoderLayer, Tran
 
 def _apply_switch_overrides():
     """The ONE environment hook of the Python side (r06: the 39 `OTR_*` reads scattered over ops / nn / recognize are module constants
-    now): OTR_SWITCHES="ops._FFN_SLAB=0,nn._LN2=0,recognize._DECODE_FORK=0" sets module-level switches for an A/B run
+    now): OTR_SWITCHES="ops._FFN_SLAB=0,nn._LN2=0,recognize._DECODE_PAIR=0" sets module-level switches for an A/B run
     (tools/gpu_ab.sh TAG OTR_SWITCHES ops._X=1 ops._X=0).  Values are integers; a switch that is a bool stays a bool.  An unknown
     name is an error: a typo must not silently measure the default twice.  The C side has the same single hook: OTR_DEBUG_SET."""
     import os

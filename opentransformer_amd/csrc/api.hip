@@ -38,30 +38,14 @@ void otr_zero_f32(float* p, int64_t n, hipStream_t s) {
 
 int g_otr_force_tile = 0;
 int g_otr_force_ksplit = 0;
-int g_otr_gemm_xcd_map = 1;        // gemm_kernel.h gemm_tile_of (otr_debug_set(26, 0) = natural tile order)
-int g_otr_bias_vec4 = 1;           // attention.hip: relative-position score bias as 16-byte loads where the rows allow (otr_debug_set(27, 0) = scalar)
-int g_otr_gemm_resident64 = 1024;   // gemm_kernel.h: resident workgroups of the persistent 64 x 64-tile GEMM (otr_debug_set(28, v); 512 = r05)
 int g_otr_conv2_wgrad256 = 1;       // conv2 weight gradient of a C1 % 256 == 0 frontend on wgrad256.hip's gather form (otr_debug_set(29, 0) = the transposing GEMM)
 int g_otr_attn_enc96 = 1;          // encattn96.hip: the Conformer's attention backward on the whole-utterance kernel (otr_debug_set(33, 0) = the streamed dQ / dK,dV pair)
-int g_otr_im2k_fast = 1;            // gemm_kernel.h TileLoader RAWK (otr_debug_set(34, 0) = the bounds-checked loader)
-int g_otr_force_generic = 0;
-int g_otr_no_persist = 0;
-int g_otr_ffn2_ablate = 0;   // tuning hook (otr_debug_set(4, v)): bit 0 = no weight DMA after the first chunk, bit 1 = no MFMA work
 int g_otr_wgrad256 = -1;     // 256x256-tile weight-gradient launch (wgrad256.hip): -1 = environment OTR_WGRAD256 (default on), 0 / 1 (otr_debug_set(6, v))
-int g_otr_wgrad256_ablate = 0;   // tuning hook (otr_debug_set(8, v)), see wgrad256.h
-int g_otr_wgrad256_min_k = 96;      // narrowest x operand the 256-wide launch takes (otr_debug_set(37, v); 128 = round 5: the relative-position attention's 504 x 96 products then stay on the 128-wide grouped kernel)
-int g_otr_wgrad256_min_rows = 256;   // shortest contraction the 256-wide launch takes (otr_debug_set(9, v))
-extern int g_otr_conv2_dgrad_ablate;   // conv.hip (otr_debug_set(10, v))
 extern int g_otr_conv2_dgrad_wide;     // conv.hip (otr_debug_set(30, v))
 extern int g_otr_conv2_wide;           // conv.hip (otr_debug_set(31, v))
-extern int g_otr_conv2wide_ablate;     // conv2wide.hip (otr_debug_set(32, v))
 int g_otr_wgrad256_grid = 0; // workgroups of that launch; 0 = one per CU (otr_debug_set(7, v))
 int g_otr_conv2_fwd_direct = 1;  // conv2 forward on the weight-stationary kernel where it serves (otr_debug_set(22, v))
 int g_otr_attn_enc = 1;          // encoder-shape attention backward with the whole (utterance, head) in LDS (otr_debug_set(21, v))
-int g_otr_rb_waves8 = 1;         // 256-column row-block kernels on 8-wave workgroups (otr_debug_set(19, v))
-int g_otr_rb_nsplit = 1;         // q|k|v row-block projection: 1 = two workgroups per row block, 384 columns each (otr_debug_set(18, v))
-int g_otr_conv1_stencil = 0;     // 1: conv1 forward on the VALU stencil instead of the fp32 matrix pipe (otr_debug_set(17, v))
-int g_otr_attn_waves8 = 1;       // merged attention backward on 8-wave workgroups (128 queries / keys each; otr_debug_set(20, v))
 int g_otr_attn_xmap = 1;         // attention launches: the blocks of one (head, utterance) on one XCD (otr_debug_set(16, v))
 int g_otr_attn_bwd_split = 0;    // attention backward as two launches (dQ, then dK/dV) instead of one (otr_debug_set(13, v))
 int g_otr_beam_reg = 1;          // beam_topk with the row in registers and wave-level arg-max rounds (beam.hip; otr_debug_set(25, v))
@@ -76,39 +60,22 @@ extern "C" int32_t otr_debug_trace(void* buf) { g_otr_trace = (unsigned long lon
 extern "C" int32_t otr_debug_set(int32_t key, int32_t value) {
   if (key == 0) g_otr_force_tile = value;
   else if (key == 1) g_otr_force_ksplit = value;
-  else if (key == 26) g_otr_gemm_xcd_map = value;
-  else if (key == 27) g_otr_bias_vec4 = value;
-  else if (key == 29) g_otr_conv2_wgrad256 = value;
-  else if (key == 30) g_otr_conv2_dgrad_wide = value;
-  else if (key == 31) g_otr_conv2_wide = value;
-  else if (key == 32) g_otr_conv2wide_ablate = value;
-  else if (key == 33) g_otr_attn_enc96 = value;
-  else if (key == 34) g_otr_im2k_fast = value;
-  else if (key == 37) g_otr_wgrad256_min_k = value > 0 ? value : 96;
-  else if (key == 28) g_otr_gemm_resident64 = value > 0 ? value : 512;
-  else if (key == 2) g_otr_force_generic = value;
-  else if (key == 3) g_otr_no_persist = value;
-  else if (key == 4) g_otr_ffn2_ablate = value;
-  else if (key == 5) { /* retired (8-wave form of the 32-row FFN kernel) */ }
   else if (key == 6) g_otr_wgrad256 = value;
   else if (key == 7) g_otr_wgrad256_grid = value;
-  else if (key == 8) g_otr_wgrad256_ablate = value;
-  else if (key == 9) g_otr_wgrad256_min_rows = value;
-  else if (key == 10) g_otr_conv2_dgrad_ablate = value;
   else if (key == 11) g_otr_spin_limit = value > 0 ? value : 1 << 22;
   else if (key == 12) g_otr_ffn_coh_only = value;
   else if (key == 13) g_otr_attn_bwd_split = value;
+  else if (key == 15) g_otr_ffn_map = value;
   else if (key == 16) g_otr_attn_xmap = value;
-  else if (key == 20) g_otr_attn_waves8 = value;
-  else if (key == 17) g_otr_conv1_stencil = value;
-  else if (key == 18) g_otr_rb_nsplit = value;
-  else if (key == 19) g_otr_rb_waves8 = value;
   else if (key == 21) g_otr_attn_enc = value;
   else if (key == 22) g_otr_conv2_fwd_direct = value;
-  else if (key == 15) g_otr_ffn_map = value;
   else if (key == 23) g_otr_dec_group = value;
   else if (key == 24) g_otr_decode_attn64 = value;
   else if (key == 25) g_otr_beam_reg = value;
+  else if (key == 29) g_otr_conv2_wgrad256 = value;
+  else if (key == 30) g_otr_conv2_dgrad_wide = value;
+  else if (key == 31) g_otr_conv2_wide = value;
+  else if (key == 33) g_otr_attn_enc96 = value;
   else { otr_set_error("debug_set: unknown key %d", key); return -1; }
   return 0;
 }
@@ -227,7 +194,7 @@ extern "C" int32_t otr_ffn_glu_fwd(const void* x, int64_t ldx, const void* w1, i
   const bool big = M >= 128 && F >= 128 && t128 >= 256 && g_otr_force_tile != 64;
   const int half = big ? 64 : 32;                          // value columns per tile
   const bool ok = kc_vec(x, ldx, OTR_H16) && kc_vec(w1, ldw, OTR_H16) && d_model % 8 == 0 && F % half == 0 &&
-                  (uintptr_t)h % 16 == 0 && (uintptr_t)u % 16 == 0 && g_otr_force_generic == 0;
+                  (uintptr_t)h % 16 == 0 && (uintptr_t)u % 16 == 0;
   if (!ok) return 1;
   GemmArgs a{};
   a.A = x; a.B = w1; a.C = h; a.bias = b1;
@@ -256,7 +223,7 @@ extern "C" int32_t otr_ffn_glu_bwd(const void* dy, int32_t dy_dtype, int64_t ldy
   *partial_rows = 0;
   if (M == 0) return 0;
   const bool ok = dy_dtype == OTR_H16 && kc_vec(dy, ldy, OTR_H16) && kc_vec(w2t, ldw, OTR_H16) && d_model % 8 == 0 &&
-                  F % 8 == 0 && (uintptr_t)h % 16 == 0 && (uintptr_t)dh % 16 == 0 && g_otr_force_generic == 0;
+                  F % 8 == 0 && (uintptr_t)h % 16 == 0 && (uintptr_t)dh % 16 == 0;
   const int64_t t128 = (int64_t)((M + 127) / 128) * ((F + 127) / 128);
   const bool big = M >= 128 && F >= 128 && t128 >= 256 && g_otr_force_tile != 64;   // few tiles: 64x64 fills the chip better
   const int rows = (M + (big ? 127 : 63)) / (big ? 128 : 64);
@@ -282,8 +249,8 @@ extern "C" int32_t otr_ffn_glu_bwd(const void* dy, int32_t dy_dtype, int64_t ldy
 // All weight gradients of a backward pass in (a few) grouped launches: dw_i[N,K] += dy_i[M,N]^T x_i[M,K].
 // the problems the 256-wide launch takes: long contraction, 16-bit operands in 16-byte aligned rows, a few tiles at least
 static bool wgrad256_ok(const otr_wgrad_item_t& it, int compute) {
-  return compute == OTR_H16 && it.dy && it.x && it.dw && it.dy_dtype == OTR_H16 && it.x_dtype == OTR_H16 && it.M >= g_otr_wgrad256_min_rows && it.N >= 128 &&
-         it.K >= g_otr_wgrad256_min_k && it.N % 8 == 0 && it.K % 8 == 0 && it.ldy >= it.N && it.ldx >= it.K && it.ldw >= it.K && it.ldy % 8 == 0 &&
+  return compute == OTR_H16 && it.dy && it.x && it.dw && it.dy_dtype == OTR_H16 && it.x_dtype == OTR_H16 && it.M >= 256 && it.N >= 128 &&
+         it.K >= 96 && it.N % 8 == 0 && it.K % 8 == 0 && it.ldy >= it.N && it.ldx >= it.K && it.ldw >= it.K && it.ldy % 8 == 0 &&
          it.ldx % 8 == 0 && it.ldw % 4 == 0 && (uintptr_t)it.dy % 16 == 0 && (uintptr_t)it.x % 16 == 0 && (uintptr_t)it.dw % 16 == 0 &&
          it.ldy < (1ll << 24) && it.ldx < (1ll << 24) && (int64_t)(it.N + 256) * it.ldw * 4 < (1ll << 31) &&
          (!it.dbias || (uintptr_t)it.dbias % 4 == 0);
@@ -336,7 +303,7 @@ extern "C" int32_t otr_linear_wgrad_grouped(const otr_wgrad_item_t* items, int32
         big.push_back(W256Item{it.dy, it.x, it.dw, it.dbias, it.M, it.N, it.K, it.ldy, it.ldx, it.ldw, it.overwrite != 0});
       }
       if (!workspace || wgrad256_workspace_bytes(big.data(), (int)big.size()) > workspace_bytes) break;   // the grouped kernel takes them
-      if (int32_t e = wgrad256_launch(big.data(), (int)big.size(), workspace, workspace_bytes, g_otr_wgrad256_grid, g_otr_wgrad256_ablate, s)) return e;
+      if (int32_t e = wgrad256_launch(big.data(), (int)big.size(), workspace, workspace_bytes, g_otr_wgrad256_grid, s)) return e;
       for (size_t c = c0; c < c1; ++c) taken[(size_t)idx[c]] = 1;
       c0 = c1;
     }

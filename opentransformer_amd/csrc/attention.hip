@@ -816,7 +816,6 @@ static int32_t fill_args(const otr_attn_desc_t* d, AttnArgs& a) {
   a.causal = d->causal; a.scale = d->scale;
   return 0;
 }
-extern int g_otr_attn_waves8;      // api.hip (otr_debug_set(20, v)): 8-wave workgroups (128 queries / keys) for 16-bit operands, head dim 64
 extern int g_otr_attn_xmap;        // api.hip (otr_debug_set(16, v)): XCD-aware workgroup mapping of the attention launches
 static dim3 attn_grid(AttnArgs& a, const otr_attn_desc_t* d, int nx) {
   a.xmap = g_otr_attn_xmap;
@@ -854,7 +853,7 @@ extern "C" int32_t otr_attention_fwd(const otr_attn_desc_t* d, const void* q, co
   a.q = q; a.k = k; a.v = v; a.out = o; a.lse = lse; a.key_mask = key_mask;
   a.vec = vec_ok(d, {q, k, v, o});
   hipStream_t s = (hipStream_t)stream;
-  if (g_otr_attn_waves8 && a.vec && d->dtype == OTR_H16 && d->dk == 64) {
+  if (a.vec && d->dtype == OTR_H16 && d->dk == 64) {   // 8-wave workgroups, 128 queries each
     hipLaunchKernelGGL((attn_fwd_kernel<bf16_t, 64, true, 8>), attn_grid(a, d, (d->Tq + 127) / 128), dim3(512), 0, s, a);
     return otr_check_launch("attention_fwd");
   }
@@ -863,13 +862,12 @@ extern "C" int32_t otr_attention_fwd(const otr_attn_desc_t* d, const void* q, co
   return otr_check_launch("attention_fwd");
 }
 
-extern int g_otr_bias_vec4;
 static void set_bias(AttnArgs& a, const float* bias, float* dbias, int64_t bs, int64_t hs, int64_t rs, int rel_shift) {
   a.bias = bias; a.dbias = dbias; a.bias_bs = bs; a.bias_hs = hs; a.bias_rs = rs; a.rel_shift = rel_shift;
   // 16-byte loads run up to key 64 ceil(Tk / 64) - 1 of every row: allowed when that stays inside what the strides say is there
   // (every row of a relative-position tensor has its 2T - 1 columns; the address is linear in h and i, so the corners decide)
   a.bias_vec4 = 0;
-  if (rel_shift && g_otr_bias_vec4 && bs >= 0 && hs >= 0 && rs >= 0) {
+  if (rel_shift && bs >= 0 && hs >= 0 && rs >= 0) {
     const int64_t T = a.Tq, k64 = ((int64_t)a.Tk + 63) / 64 * 64, H = a.H;
     int64_t extent = 0, reach = 0;
     for (int64_t h : {(int64_t)0, H - 1})
@@ -892,7 +890,7 @@ extern "C" int32_t otr_attention_bias_fwd(const otr_attn_desc_t* d, const void* 
   a.vec = vec_ok(d, {q, k, v, o});
   set_bias(a, bias, nullptr, bias_bs, bias_hs, bias_rs, rel_shift);
   hipStream_t s = (hipStream_t)stream;
-  if (g_otr_attn_waves8 && a.vec && d->dtype == OTR_H16 && d->dk == 64) {
+  if (a.vec && d->dtype == OTR_H16 && d->dk == 64) {   // 8-wave workgroups, 128 queries each
     hipLaunchKernelGGL((attn_fwd_kernel<bf16_t, 64, true, 8>), attn_grid(a, d, (d->Tq + 127) / 128), dim3(512), 0, s, a);
     return otr_check_launch("attention_bias_fwd");
   }
@@ -945,15 +943,13 @@ int32_t encattn_bwd_launch(const void* q, const void* k, const void* v, const vo
                            void* dq, void* dk, void* dv, int B, int H, int T, int64_t q_bs, int64_t q_ts, int64_t k_bs, int64_t k_ts, int64_t v_bs,
                            int64_t v_ts, int64_t o_bs, int64_t o_ts, float scale, hipStream_t stream);
 template <class CT, int DK> static void attn_bwd_merged_launch(const otr_attn_desc_t* d, AttnArgs& a, hipStream_t s) {
-  if constexpr (DK == 64 && sizeof(CT) == 2) {
-    if (g_otr_attn_waves8) {
-      const int nq8 = (d->Tq + 127) / 128, nk8 = (d->Tk + 127) / 128;
-      hipLaunchKernelGGL((attn_bwd_kernel<CT, DK, 8>), attn_grid(a, d, nq8 + nk8), dim3(512), 0, s, a, nq8);
-      return;
-    }
+  if constexpr (DK == 64 && sizeof(CT) == 2) {   // 8-wave workgroups, 128 queries / keys each
+    const int nq8 = (d->Tq + 127) / 128, nk8 = (d->Tk + 127) / 128;
+    hipLaunchKernelGGL((attn_bwd_kernel<CT, DK, 8>), attn_grid(a, d, nq8 + nk8), dim3(512), 0, s, a, nq8);
+  } else {
+    const int nqb = (d->Tq + 63) / 64, nkb = (d->Tk + 63) / 64;
+    hipLaunchKernelGGL((attn_bwd_kernel<CT, DK, 4>), attn_grid(a, d, nqb + nkb), dim3(256), 0, s, a, nqb);
   }
-  const int nqb = (d->Tq + 63) / 64, nkb = (d->Tk + 63) / 64;
-  hipLaunchKernelGGL((attn_bwd_kernel<CT, DK, 4>), attn_grid(a, d, nqb + nkb), dim3(256), 0, s, a, nqb);
 }
 #define ATTN_BWD_MERGED(CTYPE, DKV) attn_bwd_merged_launch<CTYPE, DKV>(d, a, s)
 static int32_t attention_bwd_impl(const otr_attn_desc_t* d, AttnArgs& a, void* stream) {

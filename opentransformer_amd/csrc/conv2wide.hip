@@ -13,8 +13,8 @@
 // reloaded there with the next tap's, five chunks before they are used.  Accumulators: 8 x 16 registers per lane.  One workgroup per CU.
 // Measured (batch 32 x 1000 frames): 350 us against 485; the launch moves ~0.95 GB (g2 once per class, the act1 mask, dact1), ~200 us at
 // the HBM rate -- the rest is the 256-register budget of 8 waves per CU (accumulators 128 + row pieces 64 + fragments: the allocator
-// spills ~70 registers around the tap boundaries) and one barrier per 16 MFMAs.  otr_debug_set(32, v) ablates its parts (CwArgs.ablate):
-// no MFMAs 328, no fragment reads 342, no weight DMA 326, no row reloads 273, all four 218 us.
+// spills ~70 registers around the tap boundaries) and one barrier per 16 MFMAs.  Its parts ablated one at a time (a tuning
+// hook, since removed): no MFMAs 328, no fragment reads 342, no weight DMA 326, no row reloads 273, all four 218 us.
 // (The FORWARD of the same layer was built on this skeleton as well -- 9 taps, bias + ReLU epilogue -- and measured 330-430 us against
 //  the 320 us of gemm_kernel's im2col loader: not kept.)
 #include "common.h"
@@ -27,7 +27,6 @@ struct CwArgs {
   const uint16_t* mask;      // act1 (addressed like out)
   uint16_t* out;             // dact1 [B,T1,F1,256]
   int B, T1, F1, T2, F2;
-  int ablate;                // tuning hook (otr_debug_set(32, v)): 1 = no MFMAs, 2 = one fragment read per chunk, 4 = no weight DMA, 8 = no row reloads
   int wg0[5];                // parity class c = 2 pt + pf owns workgroups [wg0[c], wg0[c+1])
 };
 
@@ -138,7 +137,9 @@ __device__ __forceinline__ void cw_body(const CwArgs& p, uint4* wbuf, uint4* ebu
     const CwPix e = pix_of(me);                                 // (32-bit element offsets: the tensors hold < 2^31 elements, checked by the host)
     const int obase = (((e.b * p.T1 + 2 * e.i + PT) * p.F1) + 2 * e.j + PF) * CW_C + 8 * ehalf;
     int off_next_tile = 0;
-#pragma unroll
+    // the taps stay a loop: unrolled into one straight block per tile, the allocator spilled 236 bytes per lane and took 96 SGPRs (rolled:
+    // 36 and 77)
+#pragma unroll 1
     for (int tt = 0; tt < NT; ++tt) {
       int offn;
       bool okn;
@@ -156,7 +157,7 @@ __device__ __forceinline__ void cw_body(const CwArgs& p, uint4* wbuf, uint4* ebu
         if (filling && c < CW_AHEAD) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
         __syncthreads();                                        // chunk c is in LDS for everybody; the buffer of chunk c - 2 is free
-        if (!(p.ablate & 4)) dma_chunk(c + CW_AHEAD);
+        dma_chunk(c + CW_AHEAD);
         __builtin_amdgcn_sched_barrier(0);
         const uint4* af = wbuf + (c & (CW_NBUF - 1)) * CW_CHUNK + lane;
         // A fragments: a ring of CW_RING k-steps in registers, read CW_RING - 1 steps ahead of the MFMAs that use them (every index is a
@@ -168,17 +169,13 @@ __device__ __forceinline__ void cw_body(const CwArgs& p, uint4* wbuf, uint4* ebu
         for (int k8 = 0; k8 < 8; ++k8) {
           const int ks = kh * 8 + k8;
           if (s == 0 && !okc) bq[ks] = make_uint4(0u, 0u, 0u, 0u);
-          if (k8 + CW_RING - 1 < 8 && !(p.ablate & 2)) {
+          if (k8 + CW_RING - 1 < 8) {
             fr[(k8 + CW_RING - 1) % CW_RING][0] = af[(k8 + CW_RING - 1) * 64];
             fr[(k8 + CW_RING - 1) % CW_RING][1] = af[(8 + k8 + CW_RING - 1) * 64];
           }
-          if (!(p.ablate & 1)) {
-            mma32(acc[2 * s], fr[k8 % CW_RING][0], bq[ks]);
-            mma32(acc[2 * s + 1], fr[k8 % CW_RING][1], bq[ks]);
-          } else {
-            asm volatile("" ::"v"(fr[k8 % CW_RING][0].x), "v"(fr[k8 % CW_RING][1].w), "v"(bq[ks].x));
-          }
-          if (s == 3 && !(p.ablate & 8)) {                                        // the registers just consumed take the next tap's pieces: five chunks until they are used
+          mma32(acc[2 * s], fr[k8 % CW_RING][0], bq[ks]);
+          mma32(acc[2 * s + 1], fr[k8 % CW_RING][1], bq[ks]);
+          if (s == 3) {                                        // the registers just consumed take the next tap's pieces: five chunks until they are used
             if (tt == NT - 1) bq[ks] = ld_global_b128(p.mask + obase + ks * 16);      // ... or the ReLU-mask rows of this tile's pixels
             else bq[ks] = ld_global_b128(srcn + ks * 16);
           }
@@ -229,7 +226,6 @@ __global__ __launch_bounds__(512, 2) void conv2wide_dgrad_kernel(CwArgs p) {
 
 }  // namespace
 
-int g_otr_conv2wide_ablate = 0;
 int64_t conv2wide_workspace_bytes() { return (int64_t)9 * 8 * CW_CHUNK * 16; }
 
 // input gradient; wg0 = the parity classes' workgroup ranges (conv.hip conv2_dgrad_plan with one workgroup per CU)
@@ -237,7 +233,7 @@ int32_t conv2wide_dgrad(const void* g2, const void* w2r, const void* act1, void*
                         void* scratch, hipStream_t s) {
   CwArgs a{};
   a.in = reinterpret_cast<const uint16_t*>(g2); a.wp = reinterpret_cast<const uint4*>(scratch); a.mask = reinterpret_cast<const uint16_t*>(act1);
-  a.ablate = g_otr_conv2wide_ablate; a.out = reinterpret_cast<uint16_t*>(dact1); a.B = B; a.T1 = T1; a.F1 = F1; a.T2 = T2; a.F2 = F2;
+  a.out = reinterpret_cast<uint16_t*>(dact1); a.B = B; a.T1 = T1; a.F1 = F1; a.T2 = T2; a.F2 = F2;
   if ((int64_t)B * T1 * F1 * CW_C >= (1ll << 31)) return 1;
   for (int c = 0; c < 5; ++c) a.wg0[c] = wg0[c];
   if (a.wg0[4] <= 0) return 0;

@@ -43,7 +43,6 @@ struct E9Args {
   int B, H, T;
   int64_t q_bs, q_ts, k_bs, k_ts, v_bs, v_ts, o_bs, o_ts;
   float scale;
-  int ablate;               // tuning hook (otr_debug_set(33, 1 | 2 a)): a & 1 = no score-term loads, a & 2 = no d bias stores, a & 4 = neither orientation computes
 };
 
 __device__ __forceinline__ uint4 e9_frag(const unsigned char* img, int row, int hi, int ks) {
@@ -201,7 +200,7 @@ __global__ __launch_bounds__(512, 1) void encattn96_bwd_kernel(E9Args p) {
       float bz[16];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const e9_f32x4_a4 v4 = *reinterpret_cast<const e9_f32x4_a4*>(brow + ((p.ablate & 1) ? 0 : cc * 32 + 8 * q + 4 * hi));
+        const e9_f32x4_a4 v4 = *reinterpret_cast<const e9_f32x4_a4*>(brow + cc * 32 + 8 * q + 4 * hi);
         bz[4 * q] = v4.x; bz[4 * q + 1] = v4.y; bz[4 * q + 2] = v4.z; bz[4 * q + 3] = v4.w;
       }
       e9_stage_rm<false>(krm, gk, gk, nullptr, Ts, tid, c);
@@ -211,7 +210,7 @@ __global__ __launch_bounds__(512, 1) void encattn96_bwd_kernel(E9Args p) {
       __syncthreads();
       e9_transpose(kt, krm, c, tid & 255, 2 * (tid >> 8), 2);
       __syncthreads();
-      if (wave_live && !(p.ablate & 4)) {
+      if (wave_live) {
         const unsigned char* kr = krm + c * 32 * E9_HS;
         const unsigned char* vr = vrm + c * 32 * E9_HS;
         f32x16 st, dp;
@@ -299,7 +298,7 @@ __global__ __launch_bounds__(512, 1) void encattn96_bwd_kernel(E9Args p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int i = min(cc * 32 + 8 * (r >> 2) + 4 * hi + (r & 3), T - 1);
-        bz[r] = p.bias[(p.ablate & 1) ? bb : bcol + (int64_t)i * bstep];
+        bz[r] = p.bias[bcol + (int64_t)i * bstep];
       }
       e9_stage_rm<false>(qrm, gq, gq, nullptr, Ts, tid, c);
       e9_stage_rm<false>(dorm, gdo, gdo, nullptr, Ts, tid, c);
@@ -309,7 +308,7 @@ __global__ __launch_bounds__(512, 1) void encattn96_bwd_kernel(E9Args p) {
       if (tid < 256) e9_transpose(qt, qrm, c, tid, 0, 4);         // wave-uniform split: four waves per image
       else e9_transpose(dot, dorm, c, tid - 256, 0, 4);
       __syncthreads();
-      if (wave_live && !(p.ablate & 4)) {
+      if (wave_live) {
         const unsigned char* qr = qrm + c * 32 * E9_HS;
         const unsigned char* dr = dorm + c * 32 * E9_HS;
         f32x16 st, dp;
@@ -329,7 +328,7 @@ __global__ __launch_bounds__(512, 1) void encattn96_bwd_kernel(E9Args p) {
             dsv[r] = pv[r] * (dp[r] - de4[e]);
           }
         }
-        if (own < T && !(p.ablate & 2)) {                          // d bias: every in-range (query, key) pair, masked ones with 0
+        if (own < T) {                          // d bias: every in-range (query, key) pair, masked ones with 0
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int i = cc * 32 + 8 * (r >> 2) + 4 * hi + (r & 3);
@@ -380,7 +379,7 @@ int32_t encattn96_bwd_launch(const void* q, const void* k, const void* v, const 
   p.dq = (uint16_t*)dq; p.dk = (uint16_t*)dk; p.dv = (uint16_t*)dv; p.key_mask = key_mask; p.lse = lse;
   p.bias = bias; p.dbias = dbias; p.dbias_h16 = dbias_h16; p.bias_bs = bias_bs; p.bias_hs = bias_hs; p.bias_rs = bias_rs;
   p.B = B; p.H = H; p.T = T; p.q_bs = q_bs; p.q_ts = q_ts; p.k_bs = k_bs; p.k_ts = k_ts; p.v_bs = v_bs; p.v_ts = v_ts; p.o_bs = o_bs; p.o_ts = o_ts;
-  p.scale = scale; p.ablate = g_otr_attn_enc96 >> 1;
+  p.scale = scale;
   const unsigned nob = (unsigned)((T + E9_OWN - 1) / E9_OWN);
   const unsigned grid = 8u * 2u * nob * (unsigned)((H * B + 7) / 8);
   hipLaunchKernelGGL(encattn96_bwd_kernel, dim3(grid), dim3(512), 0, stream, p);

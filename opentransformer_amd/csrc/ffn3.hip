@@ -276,7 +276,7 @@ __device__ __forceinline__ void f3_store_slab(const f32x16 (&acc)[2][4], unsigne
   }
 }
 
-template <int D, int ABL, bool SAVE, bool SLAB = false>
+template <int D, bool TRACE, bool SAVE, bool SLAB = false>
 __global__ __launch_bounds__(256, 1) void ffn3_fwd_kernel(Ffn3FwdArgs p) {
   static_assert(D == 256, "two 128-column halves, 16 contraction steps");
   constexpr int NKS = D / 16;
@@ -294,9 +294,9 @@ __global__ __launch_bounds__(256, 1) void ffn3_fwd_kernel(Ffn3FwdArgs p) {
   if (rb * 128 >= p.M) return;                                   // whole workgroup: the grid is padded to whole XCD groups
   const int row0 = rb * 128 + wr * 64;
   int stamp_i = 0;
-#define F3_STAMP() if constexpr ((ABL & 16) != 0) { if (p.trace && tid == 0 && stamp_i < 48) p.trace[(int64_t)blockIdx.x * 48 + stamp_i++] = __builtin_amdgcn_s_memtime(); }
+#define F3_STAMP() if constexpr (TRACE) { if (p.trace && tid == 0 && stamp_i < 48) p.trace[(int64_t)blockIdx.x * 48 + stamp_i++] = __builtin_amdgcn_s_memtime(); }
   // the constant-rate clock all XCDs share (100 MHz): when each workgroup starts / ends, at [256 * 48 + 2 workgroup + 0 / 1]
-#define F3_REALTIME(K) if constexpr ((ABL & 16) != 0) { if (p.trace && tid == 0) p.trace[256 * 48 + 2 * (int64_t)blockIdx.x + (K)] = __builtin_amdgcn_s_memrealtime(); }
+#define F3_REALTIME(K) if constexpr (TRACE) { if (p.trace && tid == 0) p.trace[256 * 48 + 2 * (int64_t)blockIdx.x + (K)] = __builtin_amdgcn_s_memrealtime(); }
   F3_REALTIME(0)
   F3_STAMP()
   F3Sync sy{};
@@ -390,8 +390,6 @@ __global__ __launch_bounds__(256, 1) void ffn3_fwd_kernel(Ffn3FwdArgs p) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) uown[rt][j] = upart[rt][j] = make_uint4(0u, 0u, 0u, 0u);
 
-  constexpr bool no_dma = (ABL & 1) != 0, no_mma = (ABL & 2) != 0, no_st = (ABL & 4) != 0;   // ablations are compile-time: a run-time flag would split
-  // the G phase into basic blocks, and hipcc interleaves the GLU's VALU code with the MFMAs only inside one block
   uint4* my_u = reinterpret_cast<uint4*>(ubuf) + ((wr * 2 + wc) * 4) * 64 + lane;
   const uint4* partner_u = reinterpret_cast<const uint4*>(ubuf) + ((wr * 2 + (wc ^ 1)) * 4) * 64 + lane;
   // SAVE: row-major u leaves as whole 128-byte lines, one chunk late, from the hand-over buffer (ffn3_bwd_kernel: dh_store): a
@@ -409,7 +407,7 @@ __global__ __launch_bounds__(256, 1) void ffn3_fwd_kernel(Ffn3FwdArgs p) {
 
   // all eight DMAs of the scheduled phase go out right behind the FIRST MFMA group of a phase (not two behind every group): every
   // fragment then has three phases to land, which matters when the weights come from beyond the L2 (5.41 -> 5.39 ms per step)
-#define F3_ISSUE2(I) if constexpr (!no_dma) { if ((I) == 0) { issue2(0); issue2(1); issue2(2); issue2(3); } }
+#define F3_ISSUE2(I) if ((I) == 0) { issue2(0); issue2(1); issue2(2); issue2(3); }
   // accumulators of GEMM1 start from the biases (register r of lane (m, hi) is hidden unit 8 (r >> 2) + 4 hi + (r & 3) of the
   // sub-chunk, for both row tiles), so the GLU adds nothing
 #define F3_BIAS_INIT(CL)                                                                                       \
@@ -425,7 +423,7 @@ __global__ __launch_bounds__(256, 1) void ffn3_fwd_kernel(Ffn3FwdArgs p) {
   // GEMM1 over 8 contraction steps (HALF = 0: steps 0-7, 1: steps 8-15) of the phase in ring slot SLOT; the two DMAs of the
   // scheduled phase ride behind every group of 8 MFMAs
 #define F3_GEMM1(HALF, SLOT, STP, CHP)                                                                         \
-  if constexpr (!no_mma) {                                                                                     \
+  {                                                                                                            \
     const otr_u32x4* wb = reinterpret_cast<const otr_u32x4*>(ring + (SLOT) * F3_PHASE) + (wc * 2) * 64 + lane; \
     otr_u32x4 fr[2][4];                                                                                        \
     _Pragma("unroll") for (int j = 0; j < 4; ++j) fr[0][j] = wb[(((j >> 1)) * 4 + (j & 1)) * 64];               \
@@ -440,14 +438,9 @@ __global__ __launch_bounds__(256, 1) void ffn3_fwd_kernel(Ffn3FwdArgs p) {
         if (j & 1) { f3_mma_xa(hg[0], fr[g & 1][j], xf[0][ks]); f3_mma_xa(hg[1], fr[g & 1][j], xf[1][ks]); }   \
         else       { f3_mma_xa(hv[0], fr[g & 1][j], xf[0][ks]); f3_mma_xa(hv[1], fr[g & 1][j], xf[1][ks]); }   \
       }                                                                                                        \
-      if constexpr (SAVE && (STP) && !no_st) u_store(CHP, g);    /* the previous chunk's u */                    \
+      if constexpr (SAVE && (STP)) u_store(CHP, g);    /* the previous chunk's u */                             \
       F3_ISSUE2(g)                                                                                             \
       __builtin_amdgcn_sched_barrier(0);                                                                       \
-    }                                                                                                          \
-  } else {                                                                                                     \
-    _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                            \
-      if constexpr (SAVE && (STP) && !no_st) u_store(CHP, g);                                                  \
-      F3_ISSUE2(g)                                                                                             \
     }                                                                                                          \
   }
   // end of a phase: this wave's DMAs of the NEXT phase have landed, its LDS traffic is done; after the barrier the slot just
@@ -456,7 +449,7 @@ __global__ __launch_bounds__(256, 1) void ffn3_fwd_kernel(Ffn3FwdArgs p) {
   // group may still fly -- the 16 DMAs of the two phases after it plus EXTRA = the global stores of those two phases (SAVE: 12
   // per G phase, unconditional so that the count is exact)
 #define F3_PHASE_END(EXTRA)                                                                                    \
-  if constexpr (no_dma) f3_wait_vm<0>(); else f3_wait_vm<16 + (EXTRA)>();                                      \
+  f3_wait_vm<16 + (EXTRA)>();                                                                                 \
   f3_wait_lds();                                                                                               \
   f3_barrier();                                                                                                \
   schedule(slot);                                                                                              \
@@ -469,7 +462,7 @@ __global__ __launch_bounds__(256, 1) void ffn3_fwd_kernel(Ffn3FwdArgs p) {
   // quarter's ~45 VALU instructions pinned between them (sched_group_barrier: 1 MFMA, then 6 VALU), so the matrix pipe runs
   // during the VALU phase.
 #define F3_PHASE_G(G2, GLU, SLOT, CHUNK)                                                                              \
-  if constexpr (!no_mma) {                                                                                     \
+  {                                                                                                            \
     const uint4* wb = reinterpret_cast<const uint4*>(ring + (SLOT) * F3_PHASE) + (wc * 16) * 64 + lane;        \
     uint4 fr[2][4];                                                                                            \
     if constexpr (GLU) F3_MFMA_DRAIN();      /* GEMM1's asm MFMAs -> the GLU's VALU reads (also behind the barrier) */ \
@@ -498,7 +491,7 @@ __global__ __launch_bounds__(256, 1) void ffn3_fwd_kernel(Ffn3FwdArgs p) {
         const uint4 nu = make_uint4(pack2h(u[0], u[1]), pack2h(u[2], u[3]), pack2h(u[4], u[5]), pack2h(u[6], u[7])); \
         uown[rt][kk & 1] = nu;               /* kept for GEMM2 of this chunk one iteration later ... */            \
         my_u[(rt * 2 + (kk & 1)) * 64] = nu; /* ... and handed to the partner wave */                            \
-        if constexpr (SAVE && !no_st) {      /* 2 global stores per quarter (row-major u: u_store) */              \
+        if constexpr (SAVE) {                /* 2 global stores per quarter (row-major u: u_store) */              \
           uint4* hs = p.hsave + ((int64_t)(((rb * 4 + sl) * NC + (CHUNK)) * 4 + wid) * 8) * 64 + lane;         \
           F3_ST_SAVE(hs + (rt * 2 + (kk & 1)) * 64,                                                            \
                          make_uint4(pack2h(hv[rt][j0], hv[rt][j0 + 1]), pack2h(hv[rt][j0 + 2], hv[rt][j0 + 3]), \
@@ -517,8 +510,6 @@ __global__ __launch_bounds__(256, 1) void ffn3_fwd_kernel(Ffn3FwdArgs p) {
       if constexpr (GLU) { F3_ISSUE2(kk) }   /* the closing phase (no GLU) schedules nothing */                  \
       __builtin_amdgcn_sched_barrier(0);                                                                       \
     }                                                                                                          \
-  } else if constexpr (GLU) {                                                                                  \
-    _Pragma("unroll") for (int kk = 0; kk < 4; ++kk) { F3_ISSUE2(kk) }                                         \
   }
   // the partner's u of the previous chunk: written before the barrier that closed G(C-1), rewritten in G(C) behind the
   // barrier that closes this phase B(C)
@@ -554,7 +545,7 @@ __global__ __launch_bounds__(256, 1) void ffn3_fwd_kernel(Ffn3FwdArgs p) {
   // ---- closing phase: GEMM2 of chunk NC-1 (its w_2 took the place of a phase A(NC)); the partners' ids travel meanwhile
   if constexpr (!SLAB) f3_sync_read_ids(sy);
   F3_READ_PARTNER()
-  if constexpr (SAVE && !no_st) {
+  if constexpr (SAVE) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) u_store(NC - 1, g);              // the last chunk's u
   }
@@ -745,7 +736,7 @@ __device__ __forceinline__ void f3_mma_acc(f32x16& acc, const otr_u32x4& w, cons
 }
 __device__ __forceinline__ float f3_h2f_lo(uint32_t w) { return h2f_lo(w); }
 
-template <int D, int ABL, bool SLAB = false>
+template <int D, bool TRACE, bool SLAB = false>
 __global__ __launch_bounds__(256, 1) void ffn3_bwd_kernel(Ffn3BwdArgs p) {
   static_assert(D == 256, "two 128-column halves, 16 contraction steps");
   constexpr int NKS = D / 16;
@@ -763,13 +754,12 @@ __global__ __launch_bounds__(256, 1) void ffn3_bwd_kernel(Ffn3BwdArgs p) {
   if (rb * 128 >= p.M) return;
   const int row0 = rb * 128 + wr * 64;
   int stamp_i = 0;
-#define F3B_STAMP() if constexpr ((ABL & 16) != 0) { if (p.trace && tid == 0 && stamp_i < 48) p.trace[(int64_t)blockIdx.x * 48 + stamp_i++] = __builtin_amdgcn_s_memtime(); }
+#define F3B_STAMP() if constexpr (TRACE) { if (p.trace && tid == 0 && stamp_i < 48) p.trace[(int64_t)blockIdx.x * 48 + stamp_i++] = __builtin_amdgcn_s_memtime(); }
   F3B_STAMP()
   F3Sync sy{};
   if constexpr (!SLAB) f3_sync_begin(sy, p.sync + 8 * rb, p.coh_only ? 16 + sl : f3_xcc_id());
   const int nchunk = p.F / 32, per = nchunk / 4, NC = per >> 1;
   const int c_base = sl * per;
-  constexpr bool no_dma = (ABL & 1) != 0, no_mma = (ABL & 2) != 0, no_st = (ABL & 4) != 0, no_hl = (ABL & 8) != 0;
 
   // ---- DMA schedule (see ffn3_fwd_kernel).  Phase 3C + k: k = 0: D(C) = w_2^T of chunk C (fragment f = ks*2 + wcc); k = 1 / 2:
   // XA / XB of chunk C-1 = w_1^T fragments for the OWN / PARTNER step: f = (wcc*4 + ctl)*4 + j4 -- column tile 4 wcc + ctl,
@@ -802,7 +792,7 @@ __global__ __launch_bounds__(256, 1) void ffn3_bwd_kernel(Ffn3BwdArgs p) {
     ffn_dma(psrc + ((uint64_t)o << 10), lane_off, pdst + (uint32_t)(2 * i) * 1024u);
     ffn_dma(psrc + ((uint64_t)(o + pc) << 10), lane_off, pdst + (uint32_t)(2 * i + 1) * 1024u);
   };
-#define F3B_ISSUE2(I) if constexpr (!no_dma) { if ((I) == 0) { issue2(0); issue2(1); issue2(2); issue2(3); } }   /* see ffn3_fwd_kernel */
+#define F3B_ISSUE2(I) if ((I) == 0) { issue2(0); issue2(1); issue2(2); issue2(3); }   /* see ffn3_fwd_kernel */
 
   schedule(0);
 #pragma unroll
@@ -887,7 +877,7 @@ __global__ __launch_bounds__(256, 1) void ffn3_bwd_kernel(Ffn3BwdArgs p) {
 
   // D: du = w_2^T . dy over 16 contraction steps, 8 MFMAs per group of 4 fragments, two DMAs behind every group
 #define F3B_PHASE_D(SLOT, STP, CHP)                                                                            \
-  if constexpr (!no_mma) {                                                                                     \
+  {                                                                                                            \
     _Pragma("unroll") for (int rt = 0; rt < 2; ++rt)                                                           \
       _Pragma("unroll") for (int r = 0; r < 16; ++r) du[rt][r] = 0.f;                                          \
     asm volatile("s_nop 3" ::: "memory");                                                                      \
@@ -903,18 +893,13 @@ __global__ __launch_bounds__(256, 1) void ffn3_bwd_kernel(Ffn3BwdArgs p) {
         f3_mma_acc(du[0], fr[g & 1][j], dyf[0][4 * g + j]);                                                    \
         f3_mma_acc(du[1], fr[g & 1][j], dyf[1][4 * g + j]);                                                    \
       }                                                                                                        \
-      if constexpr ((STP) && !no_st) { dh_store(CHP, 2 * g); dh_store(CHP, 2 * g + 1); }   /* the previous chunk's dh */ \
+      if constexpr (STP) { dh_store(CHP, 2 * g); dh_store(CHP, 2 * g + 1); }   /* the previous chunk's dh */     \
       F3B_ISSUE2(g)                                                                                            \
       __builtin_amdgcn_sched_barrier(0);                                                                       \
     }                                                                                                          \
-  } else {                                                                                                     \
-    _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                            \
-      if constexpr ((STP) && !no_st) { dh_store(CHP, 2 * g); dh_store(CHP, 2 * g + 1); }                       \
-      F3B_ISSUE2(g)                                                                                            \
-    }                                                                                                          \
   }
 #define F3B_PHASE_END(KEEP)                                                                                    \
-  if constexpr (no_dma) f3_wait_vm<0>(); else f3_wait_vm<(KEEP)>();                                            \
+  f3_wait_vm<(KEEP)>();                                                                                       \
   f3_wait_lds();                                                                                               \
   f3_barrier();                                                                                                \
   schedule(slot);                                                                                              \
@@ -943,19 +928,17 @@ __global__ __launch_bounds__(256, 1) void ffn3_bwd_kernel(Ffn3BwdArgs p) {
   // the phase's last DMA pair
 #define F3B_STORE_LOAD(RT, CH, NDH)                                                                            \
   {                                                                                                            \
-    if constexpr (!no_hl) hload((CH) + 1 < NC ? (CH) + 1 : (CH), RT);   /* past the end: a reload of valid tiles, never used */ \
+    hload((CH) + 1 < NC ? (CH) + 1 : (CH), RT);   /* past the end: a reload of valid tiles, never used */   \
   }
   // X phase: 32 MFMAs in 4 steps (j4) of 8 over w_1^T fragments [(wc*4 + ctl)*4 + j4] with the dh fragments DHF[rt][j4], the GLU'
   // quarters Q0 / Q1 (row tile RTQ) of chunk CH beside steps 0-1 / 2-3
 #define F3B_PHASE_X(X, GLUQ, SLOT, DHF, RTQ, CH, NDH)                                                          \
-  if constexpr (!no_mma) {                                                                                     \
+  {                                                                                                            \
     const uint4* wb = reinterpret_cast<const uint4*>(ring + (SLOT) * F3_PHASE) + (wc * 16) * 64 + lane;        \
     uint4 fr[2][4];                                                                                            \
     if constexpr (GLUQ) {                                                                                      \
       F3_MFMA_DRAIN();                                                                                         \
-      if constexpr (!no_dma && !no_hl) { f3_wait_vm_for<20>(hp[4 * (RTQ)], hp[4 * (RTQ) + 1], hp[4 * (RTQ) + 2], hp[4 * (RTQ) + 3]); } \
-      else if constexpr (no_hl) { }                                                                            \
-      else { f3_wait_vm_for<0>(hp[4 * (RTQ)], hp[4 * (RTQ) + 1], hp[4 * (RTQ) + 2], hp[4 * (RTQ) + 3]); }      \
+      f3_wait_vm_for<20>(hp[4 * (RTQ)], hp[4 * (RTQ) + 1], hp[4 * (RTQ) + 2], hp[4 * (RTQ) + 3]);              \
     }                                                                                                          \
     if constexpr (X) {                                                                                         \
       _Pragma("unroll") for (int ct = 0; ct < 4; ++ct) fr[0][ct] = wb[(ct * 4 + 0) * 64];                      \
@@ -982,8 +965,6 @@ __global__ __launch_bounds__(256, 1) void ffn3_bwd_kernel(Ffn3BwdArgs p) {
       if constexpr (GLUQ) { F3B_ISSUE2(j4) }                                                                   \
       __builtin_amdgcn_sched_barrier(0);                                                                       \
     }                                                                                                          \
-  } else if constexpr (GLUQ) {                                                                                 \
-    _Pragma("unroll") for (int j4 = 0; j4 < 4; ++j4) { F3B_ISSUE2(j4) }                                        \
   }
 #define F3B_READ_PARTNER()                                                                                     \
   _Pragma("unroll") for (int rt = 0; rt < 2; ++rt)                                                             \
@@ -1031,12 +1012,10 @@ __global__ __launch_bounds__(256, 1) void ffn3_bwd_kernel(Ffn3BwdArgs p) {
   // partners' ids travel meanwhile
   if constexpr (!SLAB) f3_sync_read_ids(sy);
   F3B_READ_PARTNER()
-  if constexpr (!no_st) {
 #pragma unroll
-    for (int t = 0; t < 8; ++t) dh_store(NC - 1, t);             // the last chunk's dh
-  }
+  for (int t = 0; t < 8; ++t) dh_store(NC - 1, t);               // the last chunk's dh
   F3B_PHASE_X(true, false, slot, dho, 0, 0, dhn)
-  if constexpr (no_dma) f3_wait_vm<0>(); else f3_wait_vm<8>();    // of the last X phase: its 4 tile reloads + 4 of its DMAs at most
+  f3_wait_vm<8>();    // of the last X phase: its 4 tile reloads + 4 of its DMAs at most
   f3_wait_lds();
   f3_barrier();
   slot = (slot + 1) & 3;
@@ -1097,8 +1076,6 @@ __global__ __launch_bounds__(256, 1) void ffn3_bwd_kernel(Ffn3BwdArgs p) {
 
 }  // namespace
 
-extern int g_otr_ffn2_ablate;
-
 // hidden slices x row blocks, padded to whole XCD groups (f3_block_map)
 extern int g_otr_ffn_map;   // api.hip (otr_debug_set(15, v))
 static inline unsigned f3_grid(int64_t M, int S) {
@@ -1111,20 +1088,10 @@ extern int32_t* g_otr_fault;
 extern int g_otr_ffn_coh_only;
 extern unsigned long long* g_otr_trace;
 
-#define F3_LAUNCH_FWD_SLAB(SAVE)                                                                                   \
-  switch (g_otr_ffn2_ablate & 31) {                                                                                      \
-    case 16: hipLaunchKernelGGL((ffn3_fwd_kernel<256, 16, SAVE, true>), dim3(f3_grid(M, S)), dim3(256), 0, stream, p); break; \
-    default: hipLaunchKernelGGL((ffn3_fwd_kernel<256, 0, SAVE, true>), dim3(f3_grid(M, S)), dim3(256), 0, stream, p); break;  \
-  }
-#define F3_LAUNCH_FWD(SAVE)                                                                                        \
-  switch (g_otr_ffn2_ablate & 31) {                                                                                      \
-    case 16: hipLaunchKernelGGL((ffn3_fwd_kernel<256, 16, SAVE>), dim3(f3_grid(M, S)), dim3(256), 0, stream, p); break; \
-    case 0: hipLaunchKernelGGL((ffn3_fwd_kernel<256, 0, SAVE>), dim3(f3_grid(M, S)), dim3(256), 0, stream, p); break;   \
-    case 1: hipLaunchKernelGGL((ffn3_fwd_kernel<256, 1, SAVE>), dim3(f3_grid(M, S)), dim3(256), 0, stream, p); break;   \
-    case 2: hipLaunchKernelGGL((ffn3_fwd_kernel<256, 2, SAVE>), dim3(f3_grid(M, S)), dim3(256), 0, stream, p); break;   \
-    case 4: hipLaunchKernelGGL((ffn3_fwd_kernel<256, 4, SAVE>), dim3(f3_grid(M, S)), dim3(256), 0, stream, p); break;   \
-    default: hipLaunchKernelGGL((ffn3_fwd_kernel<256, 3, SAVE>), dim3(f3_grid(M, S)), dim3(256), 0, stream, p); break;  \
-  }
+// the stamped instantiations run only while otr_debug_trace has set a buffer
+#define F3_LAUNCH_FWD(SAVE, SLAB)                                                                                  \
+  if (g_otr_trace) hipLaunchKernelGGL((ffn3_fwd_kernel<256, true, SAVE, SLAB>), dim3(f3_grid(M, S)), dim3(256), 0, stream, p); \
+  else hipLaunchKernelGGL((ffn3_fwd_kernel<256, false, SAVE, SLAB>), dim3(f3_grid(M, S)), dim3(256), 0, stream, p);
 
 // scratch bytes / sync ints of the fused form for M rows (S = 4); bytes of the saved (value, sigmoid) tiles; padded rows of u / dh
 int64_t ffn3_scratch_bytes(int64_t M) { return ((M + 127) / 128) * (int64_t)(4 * 4 * 32768); }
@@ -1143,7 +1110,7 @@ int32_t ffn3_ln_fwd_launch(const float* x, const void* x16, const void* w1_pack,
   p.x = x; p.b2 = b2; p.gamma = gamma; p.beta = beta; p.seed = seed; p.y = y; p.y16 = (uint16_t*)y16; p.z = z; p.mean = mean; p.rstd = rstd;
   p.sync = sync; p.fault = g_otr_fault; p.spin_limit = g_otr_spin_limit; p.coh_only = g_otr_ffn_coh_only; p.map = g_otr_ffn_map; p.eps = eps; p.p_drop = p_drop; p.rng_offset = rng_offset;
   p.hsave = (uint4*)hsave; p.usave = (uint16_t*)usave; p.trace = g_otr_trace;
-  if (hsave) { F3_LAUNCH_FWD(true) } else { F3_LAUNCH_FWD(false) }
+  if (hsave) { F3_LAUNCH_FWD(true, false) } else { F3_LAUNCH_FWD(false, false) }
   return otr_check_launch("ffn3_ln_fwd");
 }
 
@@ -1155,7 +1122,7 @@ int32_t ffn3_fwd_slab_launch(const void* x16, const void* w1_pack, const float* 
   p.x16 = (const uint16_t*)x16; p.p1 = (const uint4*)w1_pack; p.b1 = b1; p.p2 = (const uint4*)w2_pack;
   p.M = (int)M; p.F = F; p.S = S; p.map = g_otr_ffn_map;
   p.hsave = (uint4*)hsave; p.usave = (uint16_t*)usave; p.slab = (uint16_t*)slab; p.trace = g_otr_trace;
-  if (hsave) { F3_LAUNCH_FWD_SLAB(true) } else { F3_LAUNCH_FWD_SLAB(false) }
+  if (hsave) { F3_LAUNCH_FWD(true, true) } else { F3_LAUNCH_FWD(false, true) }
   return otr_check_launch("ffn3_fwd_slab");
 }
 
@@ -1165,15 +1132,7 @@ int32_t ffn3_bwd_launch(const void* dy16, const void* hsave, const void* w2t_pac
   p.dy16 = (const uint16_t*)dy16; p.hsave = (const uint4*)hsave; p.p3 = (const uint4*)w2t_pack; p.p4 = (const uint4*)w1t_pack;
   p.dh = (uint16_t*)dh; p.skip = skip; p.dx = dx; p.scratch = scratch; p.sync = sync; p.fault = g_otr_fault;
   p.spin_limit = g_otr_spin_limit; p.coh_only = g_otr_ffn_coh_only; p.map = g_otr_ffn_map; p.M = (int)M; p.F = F;
-  switch (g_otr_ffn2_ablate & 15) {
-    case 0: hipLaunchKernelGGL((ffn3_bwd_kernel<256, 0>), dim3(f3_grid(M, 4)), dim3(256), 0, stream, p); break;
-    case 1: hipLaunchKernelGGL((ffn3_bwd_kernel<256, 1>), dim3(f3_grid(M, 4)), dim3(256), 0, stream, p); break;
-    case 2: hipLaunchKernelGGL((ffn3_bwd_kernel<256, 2>), dim3(f3_grid(M, 4)), dim3(256), 0, stream, p); break;
-    case 4: hipLaunchKernelGGL((ffn3_bwd_kernel<256, 4>), dim3(f3_grid(M, 4)), dim3(256), 0, stream, p); break;
-    case 8: hipLaunchKernelGGL((ffn3_bwd_kernel<256, 8>), dim3(f3_grid(M, 4)), dim3(256), 0, stream, p); break;
-    case 12: hipLaunchKernelGGL((ffn3_bwd_kernel<256, 12>), dim3(f3_grid(M, 4)), dim3(256), 0, stream, p); break;
-    default: hipLaunchKernelGGL((ffn3_bwd_kernel<256, 3>), dim3(f3_grid(M, 4)), dim3(256), 0, stream, p); break;
-  }
+  hipLaunchKernelGGL((ffn3_bwd_kernel<256, false>), dim3(f3_grid(M, 4)), dim3(256), 0, stream, p);
   return otr_check_launch("ffn3_bwd");
 }
 
@@ -1183,8 +1142,8 @@ int32_t ffn3_bwd_slab_launch(const void* dy16, const void* hsave, const void* w2
   p.dy16 = (const uint16_t*)dy16; p.hsave = (const uint4*)hsave; p.p3 = (const uint4*)w2t_pack; p.p4 = (const uint4*)w1t_pack;
   p.dh = (uint16_t*)dh; p.slab = (uint16_t*)slab; p.map = g_otr_ffn_map; p.M = (int)M; p.F = F;
   p.trace = g_otr_trace;
-  if ((g_otr_ffn2_ablate & 31) == 16) hipLaunchKernelGGL((ffn3_bwd_kernel<256, 16, true>), dim3(f3_grid(M, 4)), dim3(256), 0, stream, p);
-  else hipLaunchKernelGGL((ffn3_bwd_kernel<256, 0, true>), dim3(f3_grid(M, 4)), dim3(256), 0, stream, p);
+  if (g_otr_trace) hipLaunchKernelGGL((ffn3_bwd_kernel<256, true, true>), dim3(f3_grid(M, 4)), dim3(256), 0, stream, p);
+  else hipLaunchKernelGGL((ffn3_bwd_kernel<256, false, true>), dim3(f3_grid(M, 4)), dim3(256), 0, stream, p);
   return otr_check_launch("ffn3_bwd_slab");
 }
 

@@ -379,7 +379,6 @@ struct FfnBwdArgs {
   const float* skip;       // [M, D] f32 or NULL, added to dx (the skip-connection gradient of y = LN(x + f(x)))
   float* dx;               // [M, D] f32 out (may alias skip)
   int M, F;
-  int ablate;              // tuning hook (otr_debug_set(4, v)): bit 2 = no bias-gradient reduction; 0 in production
 };
 
 template <int D>
@@ -478,11 +477,9 @@ __global__ __launch_bounds__(256, 1) void ffn_bwd_kernel(FfnBwdArgs p) {
         store_tile_row(p.u + crow * p.F + c * 32, u0, u1, hi, live);
         store_tile_row(p.dh + crow * (2 * (int64_t)p.F) + c * 32, hf[0], hf[1], hi, live);
         store_tile_row(p.dh + crow * (2 * (int64_t)p.F) + p.F + c * 32, hf[2], hf[3], hi, live);
-        if (!(p.ablate & 4)) {
-          float* bp = p.bpart + (int64_t)blockIdx.x * (2 * p.F) + c * 32;    // this wave owns chunk c of the block's row
-          tile_colsum_store(da_, bp, lane, hi, live);
-          tile_colsum_store(dg_, bp + p.F, lane, hi, live);
-        }
+        float* bp = p.bpart + (int64_t)blockIdx.x * (2 * p.F) + c * 32;    // this wave owns chunk c of the block's row
+        tile_colsum_store(da_, bp, lane, hi, live);
+        tile_colsum_store(dg_, bp + p.F, lane, hi, live);
       }
     }
     c = cn;
@@ -518,7 +515,6 @@ __global__ __launch_bounds__(256, 1) void ffn_bwd_kernel(FfnBwdArgs p) {
 }
 
 // ------------------------------------------------------------------------------------------------ C ABI
-extern int g_otr_ffn2_ablate;
 int32_t ffn3_takes(int32_t F, int32_t S);                // ffn3.hip
 int32_t ffn3_debug_block_map(int64_t M, int32_t map, int32_t* out, int32_t cap);
 int64_t ffn3_scratch_bytes(int64_t M);
@@ -615,7 +611,7 @@ extern "C" int32_t otr_ffn_bwd(const void* x16, const void* dy16, const void* w1
   FfnBwdArgs p{};
   p.x16 = (const uint16_t*)x16; p.dy16 = (const uint16_t*)dy16; p.p1 = (const uint4*)w1_pack; p.b1 = b1;
   p.p3 = (const uint4*)w2t_pack; p.p4 = (const uint4*)w1t_pack; p.dh = (uint16_t*)dh; p.u = (uint16_t*)u; p.bpart = db1_part; p.skip = skip; p.dx = dx;
-  p.M = (int)M; p.F = F; p.ablate = g_otr_ffn2_ablate;
+  p.M = (int)M; p.F = F;
   hipLaunchKernelGGL(ffn_bwd_kernel<256>, dim3((unsigned)((M + FF_RB - 1) / FF_RB)), dim3(256), 0, (hipStream_t)stream, p);
   return otr_check_launch("ffn_bwd");
 }

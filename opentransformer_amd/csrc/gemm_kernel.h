@@ -489,7 +489,6 @@ template <class OT> __device__ __noinline__ void store_tail_acc(OT* dst, const O
 // 42 MB with this map, profiles/r05_pmc_conformer.txt).  Here positions that are EQUAL modulo 8 walk the column tiles of the same row blocks: row blocks
 // 8g + (position % 8), column tile fastest.  A bijection of [0, tiles_m * tiles_n) (the last tiles_m % 8 row blocks keep the natural
 // order), so the persistent loop (stride = a multiple of 8) and split-K are untouched.
-extern int g_otr_gemm_xcd_map;   // api.hip (otr_debug_set(26, v)): 0 = the natural order
 __device__ __forceinline__ void gemm_tile_of(int t, int tiles_m, int tiles_n, bool xmap, int& tm, int& tn) {
   const int full = xmap ? (tiles_m >> 3) * 8 * tiles_n : 0;
   if (t < full) {
@@ -1076,11 +1075,8 @@ __global__ __launch_bounds__(256, 2) void gemm_batched_kernel(GemmArgs p) {
 // only when the output grid alone cannot fill the chip and a workspace was provided.
 extern int g_otr_force_tile;    // 0 = heuristic, 64 / 128 = forced (tuning hook: otr_debug_set(0, v))
 extern int g_otr_force_ksplit;  // 0 = heuristic, n = forced                  (otr_debug_set(1, v))
-extern int g_otr_force_generic; // 1 = never use the branch-free FAST loaders  (otr_debug_set(2, v))
-extern int g_otr_no_persist;    // 1 = one workgroup per tile even without split-K (otr_debug_set(3, v))
-extern int g_otr_gemm_resident64;      // api.hip (otr_debug_set(28, v))
-extern int g_otr_im2k_fast;            // api.hip (otr_debug_set(34, v)): conv2 forward's implicit-im2col loader on unconditional loads
-constexpr int OTR_RESIDENT_WG = 512;   // 256 CUs x 2 workgroups (launch_bounds(256, 2), 64 KB LDS each)
+constexpr int OTR_RESIDENT_WG = 512;     // 256 CUs x 2 workgroups (launch_bounds(256, 2), 64 KB LDS each)
+constexpr int OTR_RESIDENT_WG64 = 1024;  // 64-wide tiles: 256 CUs x 4 workgroups (see gemm_launch_tiles)
 
 template <class CT, class AT, class BT, class OT, int AMODE, int BMODE>
 static int32_t gemm_launch_tiles(GemmArgs a, hipStream_t s) {
@@ -1148,22 +1144,21 @@ static int32_t gemm_launch_tiles(GemmArgs a, hipStream_t s) {
     ks = (nk + per - 1) / per;
   }
   a.ksplit = ks;
-  a.xcd_map = g_otr_gemm_xcd_map;
+  a.xcd_map = 1;
   // branch-free loaders need aligned rows and whole chunks / whole row groups (see TileLoader)
   constexpr int CE = GemmCfg<CT>::CE, PM = GemmCfg<CT>::PM;
   auto side_fast = [&](int mode, int vec, int rows) {
     if (mode == MODE_KC) return vec && (a.K % CE == 0) && rows > 0;
     if (mode == MODE_MC) return vec && (rows % PM == 0) && (a.K % CE == 0);
     if (mode == MODE_IM2K)   // raw 16-bit path only (same-type operands); rows = output pixels: any count
-      return sizeof(CT) == 2 && std::is_same<AT, CT>::value && vec && (a.K % CE == 0) && (a.cg.C1 % CE == 0) && a.cg.a1_elems >= CE && rows > 0 &&
-             g_otr_im2k_fast != 0;
+      return sizeof(CT) == 2 && std::is_same<AT, CT>::value && vec && (a.K % CE == 0) && (a.cg.C1 % CE == 0) && a.cg.a1_elems >= CE && rows > 0;
     if (mode == MODE_IM2M)   // raw bf16 path only (same-type operands)
       return sizeof(CT) == 2 && std::is_same<BT, CT>::value && vec && (rows % PM == 0) && (a.K % CE == 0) && (a.cg.C1 % PM == 0) &&
              a.cg.a1_elems >= PM;
     return false;
   };
   const bool fast = (AMODE == MODE_KC || AMODE == MODE_MC || AMODE == MODE_IM2K) && (BMODE == MODE_KC || BMODE == MODE_MC || BMODE == MODE_IM2M) &&
-                    side_fast(AMODE, a.a_vec, a.M) && side_fast(BMODE, a.b_vec, a.N) && g_otr_force_generic == 0 &&
+                    side_fast(AMODE, a.a_vec, a.M) && side_fast(BMODE, a.b_vec, a.N) &&
                     (a.ksplit > 1 ||          // split-K slabs go to the workspace; C is written by the reduce kernel
                      (((uintptr_t)a.C % 16 == 0) && (a.ldc % (16 / (int)sizeof(OT)) == 0) && !(a.accumulate && sizeof(OT) == 2)));
   const int64_t ntiles = big ? t128 : t64;
@@ -1171,10 +1166,10 @@ static int32_t gemm_launch_tiles(GemmArgs a, hipStream_t s) {
   // (transposing operands: the cross-tile prefetch on top of their ring does not fit 256 VGPRs -- spills -- so they
   //  keep one workgroup per tile)
   constexpr bool CAN_PERSIST = (AMODE == MODE_KC && BMODE == MODE_KC);
-  const bool persist = CAN_PERSIST && fast && a.ksplit == 1 && g_otr_no_persist == 0;
-  // (64-wide tiles: 106 VGPRs and 32 KB of LDS -- FOUR workgroups fit a CU, so up to g_otr_gemm_resident64 = 1024 of them are resident:
+  const bool persist = CAN_PERSIST && fast && a.ksplit == 1;
+  // (64-wide tiles: 106 VGPRs and 32 KB of LDS -- FOUR workgroups fit a CU, so up to OTR_RESIDENT_WG64 = 1024 of them are resident:
   //  the Conformer's 7968 x 384 outputs are 750 tiles, which 512 workgroups walked as two rounds with the second one half empty)
-  const int64_t resident = big ? OTR_RESIDENT_WG : g_otr_gemm_resident64;
+  const int64_t resident = big ? OTR_RESIDENT_WG : OTR_RESIDENT_WG64;
   const dim3 grid((unsigned)(persist && ntiles > resident ? resident : ntiles), a.ksplit);
   if (a.act == OTR_ACT_GLU_FWD || a.act == OTR_ACT_GLU_BWD) {   // fused FFN epilogues: own (non-persistent) instantiations
     if constexpr (CAN_PERSIST && std::is_same<CT, bf16_t>::value && std::is_same<AT, bf16_t>::value &&

@@ -617,8 +617,6 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void rb_linear_ln_bwd_kernel(RbLin
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ C ABI
-extern int g_otr_rb_waves8;        // api.hip (otr_debug_set(19, v)): 8-wave workgroups for the 256-column row-block kernels
-extern int g_otr_rb_nsplit;        // api.hip (otr_debug_set(18, v)): the 768-column projection on two workgroups per row block
 extern "C" int32_t otr_rb_linear(const void* x16, int64_t ldx, const void* w_pack, const float* bias, const float* skip, int64_t lds,
                                  void* out, int32_t out_dtype, int64_t ldo, int64_t M, int32_t N, int32_t K, void* stream) {
   OTR_REQUIRE(x16 && w_pack && out, "rb_linear: null pointer");
@@ -636,8 +634,7 @@ extern "C" int32_t otr_rb_linear(const void* x16, int64_t ldx, const void* w_pac
   const dim3 grid((unsigned)((M + RB - 1) / RB));
   hipStream_t s = (hipStream_t)stream;
   if (K == 256 && N == 256) hipLaunchKernelGGL((rb_linear_kernel<256, 2>), grid, dim3(256), 0, s, p);
-  else if (K == 256 && g_otr_rb_nsplit) hipLaunchKernelGGL((rb_linear_kernel<256, 3, 2>), dim3(grid.x, 2), dim3(256), 0, s, p);
-  else if (K == 256) hipLaunchKernelGGL((rb_linear_kernel<256, 6>), grid, dim3(256), 0, s, p);
+  else if (K == 256) hipLaunchKernelGGL((rb_linear_kernel<256, 3, 2>), dim3(grid.x, 2), dim3(256), 0, s, p);   // two workgroups per row block
   else hipLaunchKernelGGL((rb_linear_kernel<768, 2>), grid, dim3(256), 0, s, p);
   return otr_check_launch("rb_linear");
 }
@@ -657,8 +654,7 @@ extern "C" int32_t otr_rb_linear_ln(const otr_dec_ln_t* ln, const void* w_pack, 
   p.ln.beta = ln->beta; p.ln.seed = ln->seed; p.ln.p_drop = ln->p_drop; p.ln.eps = ln->eps; p.ln.rng_offset = ln->rng_offset;
   p.ln.y = ln->y; p.ln.y16 = (uint16_t*)ln->y16; p.ln.z = ln->z; p.ln.mean = ln->mean; p.ln.rstd = ln->rstd; p.ln.R = M;
   p.pw = reinterpret_cast<const uint4*>(w_pack); p.bias = bias; p.out = out; p.ldo = ldo; p.M = (int)M; p.out_h16 = out_dtype == OTR_H16;
-  if (g_otr_rb_waves8) hipLaunchKernelGGL((rb_linear_ln_kernel<3, 1, 8>), dim3((unsigned)((M + RB - 1) / RB), 1), dim3(512), 0, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL((rb_linear_ln_kernel<3, 2, 4>), dim3((unsigned)((M + RB - 1) / RB), 2), dim3(256), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL((rb_linear_ln_kernel<3, 1, 8>), dim3((unsigned)((M + RB - 1) / RB), 1), dim3(512), 0, (hipStream_t)stream, p);
   return otr_check_launch("rb_linear_ln");
 }
 
@@ -687,8 +683,7 @@ extern "C" int32_t otr_proj_ln_fwd(const float* x, const void* c16, int64_t ldc,
   p.beta = beta; p.seed = seed; p.y = y; p.y16 = reinterpret_cast<uint16_t*>(y16); p.z = z; p.mean = mean; p.rstd = rstd;
   p.ldc = ldc; p.M = (int)M; p.eps = eps; p.p_drop = p_drop; p.rng_offset = rng_offset;
   p.touch = take_touch_hint();
-  if (g_otr_rb_waves8) hipLaunchKernelGGL(proj_ln_fwd_kernel<8>, dim3((unsigned)((M + RB - 1) / RB)), dim3(512), 0, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(proj_ln_fwd_kernel<4>, dim3((unsigned)((M + RB - 1) / RB)), dim3(256), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(proj_ln_fwd_kernel<8>, dim3((unsigned)((M + RB - 1) / RB)), dim3(512), 0, (hipStream_t)stream, p);
   return otr_check_launch("proj_ln_fwd");
 }
 
@@ -708,8 +703,7 @@ extern "C" int32_t otr_ln_bwd_proj(const float* dy, const float* z, const float*
   p.dx = dx; p.da16 = reinterpret_cast<uint16_t*>(da16); p.dc16 = reinterpret_cast<uint16_t*>(dc16); p.partial = partial;
   p.ldc = ldc; p.M = (int)M; p.p_drop = p_drop; p.rng_offset = rng_offset;
   p.touch = take_touch_hint();
-  if (g_otr_rb_waves8) hipLaunchKernelGGL(ln_bwd_proj_kernel<8>, dim3((unsigned)((M + RB - 1) / RB)), dim3(512), 0, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(ln_bwd_proj_kernel<4>, dim3((unsigned)((M + RB - 1) / RB)), dim3(256), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(ln_bwd_proj_kernel<8>, dim3((unsigned)((M + RB - 1) / RB)), dim3(512), 0, (hipStream_t)stream, p);
   return otr_check_launch("ln_bwd_proj");
 }
 
@@ -729,8 +723,7 @@ extern "C" int32_t otr_ln_bwd_proj_slabs(const float* dskip, const void* slabs, 
   p.dx = dx; p.da16 = reinterpret_cast<uint16_t*>(da16); p.dc16 = reinterpret_cast<uint16_t*>(dc16); p.partial = partial;
   p.ldc = ldc; p.M = (int)M; p.p_drop = p_drop; p.rng_offset = rng_offset;
   p.touch = take_touch_hint();
-  if (g_otr_rb_waves8) hipLaunchKernelGGL(ln_bwd_proj_kernel<8>, dim3((unsigned)((M + RB - 1) / RB)), dim3(512), 0, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(ln_bwd_proj_kernel<4>, dim3((unsigned)((M + RB - 1) / RB)), dim3(256), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(ln_bwd_proj_kernel<8>, dim3((unsigned)((M + RB - 1) / RB)), dim3(512), 0, (hipStream_t)stream, p);
   return otr_check_launch("ln_bwd_proj_slabs");
 }
 
@@ -772,12 +765,7 @@ extern "C" int32_t otr_rb_linear_ln_bwd_pf(const void* g16, int64_t ldg, const v
   }
   const dim3 grid((unsigned)((M + RB - 1) / RB));
   hipStream_t s = (hipStream_t)stream;
-  if (g_otr_rb_waves8) {
-    if (K == 768) hipLaunchKernelGGL((rb_linear_ln_bwd_kernel<768, 8>), grid, dim3(512), 0, s, p);
-    else hipLaunchKernelGGL((rb_linear_ln_bwd_kernel<256, 8>), grid, dim3(512), 0, s, p);
-  } else {
-    if (K == 768) hipLaunchKernelGGL((rb_linear_ln_bwd_kernel<768, 4>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((rb_linear_ln_bwd_kernel<256, 4>), grid, dim3(256), 0, s, p);
-  }
+  if (K == 768) hipLaunchKernelGGL((rb_linear_ln_bwd_kernel<768, 8>), grid, dim3(512), 0, s, p);
+  else hipLaunchKernelGGL((rb_linear_ln_bwd_kernel<256, 8>), grid, dim3(512), 0, s, p);
   return otr_check_launch("rb_linear_ln_bwd");
 }

@@ -119,7 +119,7 @@ struct Stager {                 // this lane's share of the two DMA instructions
   int64_t pix_bytes;            // C1 * 2
   FastDiv divF2, divT2;
   // NTA / NTB: the operand strip is read by this tile only -> non-temporal, it stays out of the L2 the shared strips live in
-  template <bool NTA, bool NTB, bool SKIPB = false, bool CONV = false> __device__ __forceinline__ void issue(int slab, int slot) {
+  template <bool NTA, bool NTB, bool CONV = false> __device__ __forceinline__ void issue(int slab, int slot) {
     const bool ok = slab * SLAB_ROWS + row0 < M;
     const unsigned char* pa = ok && col_a ? base_a + slab * step_a : zeros;
     const unsigned char* pb;
@@ -133,8 +133,7 @@ struct Stager {                 // this lane's share of the two DMA instructions
       pb = ok && col_b ? base_b + slab * step_b : zeros;
     }
     if constexpr (NTA) dma16_nt(pa, (uint32_t)(slot * SLAB_BYTES) + dst); else dma16(pa, (uint32_t)(slot * SLAB_BYTES) + dst);
-    if constexpr (SKIPB) dma16(zeros, (uint32_t)(slot * SLAB_BYTES) + 8192u + dst);        // ablation 6: the x part is not fetched (one line, L1-hot)
-    else if constexpr (NTB) dma16_nt(pb, (uint32_t)(slot * SLAB_BYTES) + 8192u + dst);
+    if constexpr (NTB) dma16_nt(pb, (uint32_t)(slot * SLAB_BYTES) + 8192u + dst);
     else dma16(pb, (uint32_t)(slot * SLAB_BYTES) + 8192u + dst);
   }
 };
@@ -144,13 +143,12 @@ struct Stager {                 // this lane's share of the two DMA instructions
 // Per slab and wave: 8 MFMAs of the current fragments with the two DMA instructions of slab i+6 and the 12 reads of slab
 // i+1 spread between them, then the counted wait that retires slab i+2 and the barrier that publishes it.  Two slabs per
 // trip (static register sets); the steady-state trips carry no conditionals.
-template <bool NTA, bool NTB, int ABL, bool BIAS, bool CONV = false>
+template <bool NTA, bool NTB, bool BIAS, bool CONV = false>
 __device__ __forceinline__ void stream_piece(Stager& sg, f32x16 (&acc)[4][2], float (&cs)[4], int wc, int sb, int P, int rot,
                                              uint32_t a_off, uint32_t b_off) {
-  constexpr bool no_mma = (ABL & 1) && ABL != 6, no_dma = (ABL & 2) && ABL != 6;
   int stage = rot;                                     // next slab to stage, relative to sb, walks rot .. P-1, 0 .. rot-1
   auto issue_next = [&](int slot) {
-    sg.issue<NTA, NTB, ABL == 6, CONV>(sb + stage, slot);
+    sg.issue<NTA, NTB, CONV>(sb + stage, slot);
     stage = stage + 1 == P ? 0 : stage + 1;
   };
   // ---- prologue: slabs 0 .. AHEAD-1 in flight, slabs 0 and 1 landed, fragments of slab 0 in registers
@@ -165,17 +163,13 @@ __device__ __forceinline__ void stream_piece(Stager& sg, f32x16 (&acc)[4][2], fl
   read_frags_lo(f0, 0u, a_off, b_off);
   read_frags_hi(f0, 0u, a_off, b_off);
 #define W256_MMA(A, CUR)                                                                                     \
-  if constexpr (!no_mma) {                                                                                   \
-    mma32(acc[A][0], CUR.a[A], CUR.b[0]);                                                                    \
-    mma32(acc[A][1], CUR.a[A], CUR.b[1]);                                                                    \
-  } else {                                                                                                   \
-    asm volatile("" ::"v"(CUR.a[A].x), "v"(CUR.b[0].x), "v"(CUR.b[1].w), "v"(CUR.a[A].w));                   \
-  }                                                                                                          \
+  mma32(acc[A][0], CUR.a[A], CUR.b[0]);                                                                      \
+  mma32(acc[A][1], CUR.a[A], CUR.b[1]);                                                                      \
   __builtin_amdgcn_sched_barrier(0);
 #define W256_PHASE(Q, CUR, NXT, ST)                                                                          \
   {                                                                                                          \
     const int q_ = (Q);                                                                                      \
-    const bool more_ = ((ST) || q_ + AHEAD < P) && !no_dma, next_ = (ST) || q_ + 1 < P;                      \
+    const bool more_ = (ST) || q_ + AHEAD < P, next_ = (ST) || q_ + 1 < P;                      \
     const uint32_t nslab_ = (uint32_t)(((q_ + 1) & (RING - 1)) * SLAB_BYTES);                                \
     W256_MMA(0, CUR)                                                                                         \
     if (more_) issue_next((q_ + AHEAD) & (RING - 1));                                                        \
@@ -291,7 +285,7 @@ __global__ void wgrad256_init_kernel(int* flags, int n, uint32_t* zeros) {
   if (threadIdx.x < 16) zeros[threadIdx.x] = 0u;
 }
 
-template <int ABL, bool CONV = false>
+template <bool CONV = false>
 __global__ __launch_bounds__(512) void wgrad256_kernel(W256Args g) {
   __shared__ __attribute__((aligned(1024))) unsigned char smem[LDS_BYTES];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -405,13 +399,13 @@ __global__ __launch_bounds__(512) void wgrad256_kernel(W256Args g) {
     float cs[4] = {0.f, 0.f, 0.f, 0.f};
     const bool bias = pr.dbias != nullptr && tk == 0;
     // the dy strip of this tile is shared with the other tk tiles of its problem, the x strip with the other tn tiles
-    const bool nt_a = (g.policy & 1) && tiles_k == 1, nt_b = (g.policy & 1) && pr.N <= 256;
+    const bool nt_a = tiles_k == 1, nt_b = pr.N <= 256;
 #define W256_RUN(A, B)                                                                                       \
   {                                                                                                          \
-    if (bias) stream_piece<A, B, ABL, true>(sg, acc, cs, wc, sb, P, rot, a_off, b_off);                     \
-    else stream_piece<A, B, ABL, false>(sg, acc, cs, wc, sb, P, rot, a_off, b_off);                          \
+    if (bias) stream_piece<A, B, true>(sg, acc, cs, wc, sb, P, rot, a_off, b_off);                     \
+    else stream_piece<A, B, false>(sg, acc, cs, wc, sb, P, rot, a_off, b_off);                               \
   }
-    if constexpr (CONV) stream_piece<false, false, ABL, false, true>(sg, acc, cs, wc, sb, P, rot, a_off, b_off);
+    if constexpr (CONV) stream_piece<false, false, false, true>(sg, acc, cs, wc, sb, P, rot, a_off, b_off);
     else if (nt_a && nt_b) W256_RUN(true, true)
     else if (nt_a) W256_RUN(true, false)
     else if (nt_b) W256_RUN(false, true)
@@ -440,7 +434,6 @@ __global__ __launch_bounds__(512) void wgrad256_kernel(W256Args g) {
     if constexpr (CONV) {
       // this row range's partial tile: stored (nobody else writes slab `slice`), summed by w256_reduce_kernel
       flush_tile<false, true>(acc, g.split_ws + (int64_t)slice * pr.N * pr.ldw, pr.ldw, pr.N, pr.K, n_base, k_base, scr, lane);
-    } else if constexpr ((ABL & 4) != 0 && ABL != 6) {
     } else if (nslices == 1) {
       if (pr.flag0 & (1 << 30)) flush_tile<false, true>(acc, dw, pr.ldw, pr.N, pr.K, n_base, k_base, scr, lane);
       else flush_tile<false>(acc, dw, pr.ldw, pr.N, pr.K, n_base, k_base, scr, lane);
@@ -533,7 +526,7 @@ static int32_t wgrad256_plan(const W256Item* it, int n, int grid_cap, W256Args& 
   return 0;
 }
 
-int32_t wgrad256_launch(const W256Item* it, int n, void* workspace, int64_t workspace_bytes, int grid_cap, int ablate, hipStream_t s) {
+int32_t wgrad256_launch(const W256Item* it, int n, void* workspace, int64_t workspace_bytes, int grid_cap, hipStream_t s) {
   if (n <= 0) return 0;
   W256Args g{};
   int grid = 0, flags = 0;
@@ -543,20 +536,10 @@ int32_t wgrad256_launch(const W256Item* it, int n, void* workspace, int64_t work
     otr_set_error("wgrad256: workspace of %lld bytes, need %lld", (long long)workspace_bytes, (long long)need);
     return -1;
   }
-  g.ablate = ablate & 7; g.policy = ablate >> 3 ? (ablate >> 3) - 1 : 1;   // (ablate >> 3) - 1: bit 0 non-temporal strips
   g.zeros = workspace;
   g.flags = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(workspace) + 64);
   hipLaunchKernelGGL(wgrad256_init_kernel, dim3(1), dim3(256), 0, s, g.flags, flags, reinterpret_cast<uint32_t*>(workspace));
-  switch (ablate & 7) {
-    case 0: hipLaunchKernelGGL(wgrad256_kernel<0>, dim3((unsigned)grid), dim3(512), 0, s, g); break;
-    case 1: hipLaunchKernelGGL(wgrad256_kernel<1>, dim3((unsigned)grid), dim3(512), 0, s, g); break;
-    case 2: hipLaunchKernelGGL(wgrad256_kernel<2>, dim3((unsigned)grid), dim3(512), 0, s, g); break;
-    case 3: hipLaunchKernelGGL(wgrad256_kernel<3>, dim3((unsigned)grid), dim3(512), 0, s, g); break;
-    case 4: hipLaunchKernelGGL(wgrad256_kernel<4>, dim3((unsigned)grid), dim3(512), 0, s, g); break;
-    case 5: hipLaunchKernelGGL(wgrad256_kernel<5>, dim3((unsigned)grid), dim3(512), 0, s, g); break;
-    case 6: hipLaunchKernelGGL(wgrad256_kernel<6>, dim3((unsigned)grid), dim3(512), 0, s, g); break;
-    default: hipLaunchKernelGGL(wgrad256_kernel<7>, dim3((unsigned)grid), dim3(512), 0, s, g); break;
-  }
+  hipLaunchKernelGGL(wgrad256_kernel<>, dim3((unsigned)grid), dim3(512), 0, s, g);
   return otr_check_launch("wgrad256");
 }
 
@@ -592,13 +575,13 @@ int32_t wgrad256_conv_launch(const void* g2, const void* act1, float* dw2r, int 
   p.dy = reinterpret_cast<const uint16_t*>(g2); p.x = reinterpret_cast<const uint16_t*>(act1); p.dw = dw2r; p.dbias = nullptr;
   p.M = (int)M; p.N = C2; p.K = (int)K; p.ldy = C2; p.ldx = C1; p.ldw = (int)K; p.start = 0; p.flag0 = 0;
   g.nprob = 1; g.total = tiles * R; g.chunk = R; g.mode = 2; g.nfull = 0; g.rem_tiles = tiles; g.parts = parts;
-  g.spin_limit = g_otr_spin_limit; g.fault = g_otr_fault; g.ablate = 0; g.policy = 1;
+  g.spin_limit = g_otr_spin_limit; g.fault = g_otr_fault;
   g.cT1 = T1; g.cF1 = F1; g.cT2 = T2; g.cF2 = F2; g.cC1 = C1; g.cdivF2 = make_fastdiv((uint32_t)F2); g.cdivT2 = make_fastdiv((uint32_t)T2);
   g.zeros = workspace; g.flags = nullptr;
   g.split_ws = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(workspace) + head);
   hipLaunchKernelGGL(wgrad256_init_kernel, dim3(1), dim3(256), 0, s, nullptr, 0, reinterpret_cast<uint32_t*>(workspace));   // the zero line
   const int grid = (tiles * parts + 7) / 8 * 8;               // whole XCD groups (the slot <-> block map); the extra ones leave at once
-  hipLaunchKernelGGL((wgrad256_kernel<0, true>), dim3((unsigned)grid), dim3(512), 0, s, g);
+  hipLaunchKernelGGL((wgrad256_kernel<true>), dim3((unsigned)grid), dim3(512), 0, s, g);
   if (int32_t e = otr_check_launch("wgrad256(conv)")) return e;
   hipLaunchKernelGGL(w256_reduce_kernel, dim3((unsigned)((elems / 4 + 255) / 256)), dim3(256), 0, s, g.split_ws, parts, elems, dw2r);
   return otr_check_launch("wgrad256(conv reduce)");

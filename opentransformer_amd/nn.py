@@ -27,7 +27,6 @@ from . import ops
 _MASK_FOLD = True  # ... and the convolution branch's row mask applied by that launch
 _LN2 = True                   # ... and post_ffn_norm + final_norm in one launch each way
 _POS_TABLES = True    # ConformerEncoder: the relative-position tables of all blocks in two batched launches (ops.relpos_tables)
-_LN16 = True          # ... the inner LayerNorms' outputs leave as the 16-bit tensor alone (ops.ResidualLnFn lp_only): 16-bit input gradients back
 _LN3 = True           # ... and the next block's macaron LayerNorm in the closing launches of the block below (ops.ResidualLn3Fn)
 _RES_LN = True     # ConformerEncoderBlock: residual adds fused into the LayerNorms that follow them
 
@@ -164,12 +163,7 @@ class MultiHeadedSelfAttention(nn.Module):
         qkv = ops.linear(x, self.qvk_proj.weight, self.qvk_proj.bias, out_dtype=ops.act_dtype(), link=link)
         if self.share_qvk_proj:          # query = key = value = the one projection (module/attention.py:71-72); rare: packed by copy
             qkv = torch.cat((qkv, qkv, qkv), dim=-1)
-        ctx = ops.SelfAttentionFn.apply(qkv, _key_mask(mask, B, T), self.nheads, causal)
-        if qkv.is_contiguous() and ctx.requires_grad:
-            ctx._otr_touch = qkv          # what the attention's backward launch reads first (ops.ProjLnFn has the launch before it touch it)
-            wp = ops.lin_packs(self.qvk_proj.weight) if not self.share_qvk_proj else None
-            ctx._otr_touch_w = wp[1] if wp is not None else None      # the input-gradient pack the launch after that one streams
-        return ctx
+        return ops.SelfAttentionFn.apply(qkv, _key_mask(mask, B, T), self.nheads, causal)
 
     def forward(self, x, mask, causal=False, defer_bias=False, link=None):
         """defer_bias: the caller feeds the result to _post_norm(..., a_bias=self.output_proj.bias); link: ops.ResidualLink
@@ -535,11 +529,11 @@ class ConformerEncoderBlock(nn.Module):
             link = ops.new_prenorm_link()
             a = self.pre_ffn(self._ln(self.macaron_ffn_norm, x, link), branch=True)
         n = self.mha_norm
-        x, h = ops.residual_layernorm(x, a, self.ffn_scale, p, n.weight, n.bias, n.eps, link, lp_only=_LN16)
+        x, h = ops.residual_layernorm(x, a, self.ffn_scale, p, n.weight, n.bias, n.eps, link, lp_only=True)
         km = ops._mask_u8(mask, mask.shape[0], mask.shape[1]).unsqueeze(1)
         a = self.mha(h, km, pos)[0] if self.relative_positional else self.mha(h, km)[0]
         n = self.conv_norm
-        x, h = ops.residual_layernorm(x, a, 1.0, p, n.weight, n.bias, n.eps, lp_only=_LN16)
+        x, h = ops.residual_layernorm(x, a, 1.0, p, n.weight, n.bias, n.eps, lp_only=True)
         am = ops._mask_u8(mask, mask.shape[0], mask.shape[1]).reshape(-1) if _MASK_FOLD else None
         a = self.conv(h, mask, mask_out=am is None)      # the padded frames' rows are zeroed by the residual launch below
         n, n2 = self.post_ffn_norm, self.final_norm

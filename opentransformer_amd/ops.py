@@ -590,9 +590,6 @@ def gradients_written(ptrs):
     accumulates instead of storing"""
     _wq_excl['written'].update(ptrs)
 
-_FUSE_BIAS_COLSUM = True
-_DEBUG_WQ = False
-
 
 def defer_weight_grads(on):
     _wq['on'] = bool(on)
@@ -635,13 +632,6 @@ def flush_weight_grads():
     if _wq.get('keep_last'):            # bench.py re-times the grouped launch on the items of the last backward
         _wq['last'] = (list(w), list(b))
     lib = L.load()
-    if _DEBUG_WQ and (w or b) and _wq.get('dumped', 0) < 4:   # listing of the first flushes' deferred work (tuning aid)
-        _wq['dumped'] = _wq.get('dumped', 0) + 1
-        print('wq flush', _wq['dumped'], flush=True)
-        for dy2, x2, out in w:
-            print('wq w', tuple(dy2.shape), dy2.dtype, dy2.stride(0), tuple(x2.shape), x2.dtype, flush=True)
-        for a2, out in b:
-            print('wq b', tuple(a2.shape), a2.dtype, a2.stride(0), flush=True)
     if w:
         items = (L.WgradItem * len(w))()
         seen = {}
@@ -658,7 +648,7 @@ def flush_weight_grads():
             it.overwrite = int(_WG_OVERWRITE and ptr in sw and ptr not in written and seen[ptr] == 1
                                and here is not None and cleared_in.get(ptr) == here)
         written.update(seen)
-        if b and _FUSE_BIAS_COLSUM:
+        if b:
             # a bias gradient whose matrix is the dy operand of a weight gradient the 256-wide kernel takes rides along with
             # it (the kernel reads that matrix anyway): one less pass over it by the column-sum launch
             by_dy = {}
@@ -949,9 +939,7 @@ def rb_linear_pending_raw(pend, pack, N, bias, out_dtype):
 def rb_linear_ln_bwd_raw(g2, wt_pack, skip, saved, prefetch=None):
     """(d z f32, d a 16-bit, partial [blocks, 3*256]) of the LayerNorm y = LN(z) whose output gradient is skip + g2 . W"""
     z, mean, rstd, gamma, seed, p_drop, off = saved
-    pf_t, pf_n, pf_h = prefetch if prefetch is not None else (None, 0, None)
-    if pf_h is not None:
-        L.check(L.load().otr_touch_hint(_p(pf_h), pf_h.numel() * pf_h.element_size(), None, 0), 'otr_touch_hint')
+    pf_t, pf_n = prefetch if prefetch is not None else (None, 0)
     M, K = g2.shape
     d = 256
     lib = L.load()
@@ -1041,7 +1029,7 @@ class LinearFn(torch.autograd.Function):
         dy2 = _rows(dy) if dyp16 is None else dyp16
         if ctx.relu:
             dy2 = relu_bwd_raw(y, dy2.contiguous())
-        if (_DY16_WIDE and dyp16 is None and dy2.dtype == torch.float32 and is_half() and ctx.perm is not None and x2.dtype == half_dtype()
+        if (dyp16 is None and dy2.dtype == torch.float32 and is_half() and ctx.perm is not None and x2.dtype == half_dtype()
                 and dy2.shape[0] >= 1024 and _wq['on'] and _in_backward() and getattr(ctx.w_ref, '_otr_regroup_grad', None) is not None
                 and grad_target(ctx.w_ref) is not None):
             # r06: an fp32 gradient in front of the frontend's output layer (the Conformer: a LayerNorm sits behind it; C2 gets the 16-bit
@@ -1142,7 +1130,7 @@ def linear(x, w, b=None, relu=False, out_dtype=None, perm=None, defer_bias=False
     if _G16 and not relu and out_dtype == torch.float32 and is_half() and _wq['on'] and torch.is_grad_enabled():
         if perm is not None and getattr(w, '_otr_regroup_grad', None) is not None:
             g16 = _Grad16Link()                       # the frontend's output layer <- PosEncFn.backward
-        elif perm is None and _G16_LOSS and getattr(w, '_otr_pad', None) is not None:
+        elif perm is None and getattr(w, '_otr_pad', None) is not None:
             g16 = _Grad16Link()                       # the row-padded output layer <- LabelSmoothingLossFusedFn.backward
     y = LinearFn.apply(x, w, b, relu, out_dtype, perm, defer_bias, link, g16)
     if g16 is not None and g16.armed:
@@ -1745,14 +1733,12 @@ class ProjLnFn(torch.autograd.Function):
     affine gradients join the grouped launches at the end of the pass."""
 
     @staticmethod
-    def forward(ctx, x, c, w, b, gamma, beta, p_drop, eps, packs, link, ilink=None, touch=None, touch_w=None):
+    def forward(ctx, x, c, w, b, gamma, beta, p_drop, eps, packs, link, ilink=None):
         _cuda(x, c, w, gamma, beta)
         ctx.set_materialize_grads(False)
         materialize(x)
         ctx.link = link
         ctx.ilink = ilink
-        ctx.touch = touch           # the attention launch's saved q|k|v: this Function's backward launch touches it for the one that follows
-        ctx.touch_w = touch_w       # the q|k|v projection's input-gradient pack (read two launches later)
         if ilink is not None:
             ilink.armed = any(ctx.needs_input_grad)
         if link is not None:            # the branch's first Linear armed it under ITS conditions (fp32 x, no perm, no relu): keep them
@@ -1788,7 +1774,7 @@ class ProjLnFn(torch.autograd.Function):
         if ctx.ilink is not None:
             stash, ctx.ilink.result = ctx.ilink.result, None
         if dy is None and stash is None:
-            return (None,) * 13
+            return (None,) * 11
         z, mean, rstd, gamma, seed, c2 = ctx.saved_tensors
         w, b, g_ref, b_ref = ctx.refs
         M, d, p_drop, off, xshape, cshape, packs = ctx.cfg
@@ -1798,13 +1784,6 @@ class ProjLnFn(torch.autograd.Function):
         dc = torch.empty((M, d), dtype=half_dtype(), device=dev)
         nrow = L.load().otr_ln_bwd_proj_partial_rows(M)
         part = torch.empty((nrow, 3 * d), dtype=torch.float32, device=dev)
-        if ctx.touch_w is not None and _QKV_W_TOUCH and not (ctx.touch is not None and _ATTN_PREFETCH):
-            tw = ctx.touch_w
-            L.check(L.load().otr_touch_hint(_p(tw), tw.numel() * tw.element_size(), None, 0), 'otr_touch_hint')
-        if ctx.touch is not None and _ATTN_PREFETCH:
-            # the attention backward launch runs next and would fetch its saved q|k|v and context (c2) cold: csrc/rowblock.hip RbTouch
-            t = ctx.touch
-            L.check(L.load().otr_touch_hint(_p(t), t.numel() * t.element_size(), _p(c2), c2.numel() * c2.element_size()), 'otr_touch_hint')
         if stash is not None:           # see LnInLink: the FFN's backward launch left (skip-path gradient, four slabs)
             dskip, bslabs = stash
             if dy is not None and not _is_zero_placeholder(dy):
@@ -1839,7 +1818,7 @@ class ProjLnFn(torch.autograd.Function):
             ctx.link.buf = dx           # the branch's first Linear adds its input gradient into this and returns the sum
             _park(ctx.link)
             dx_ret = None
-        return (dx_ret, dc.view(cshape), None if gw is not None else dw, dbias, dgamma, dbeta, None, None, None, None, None, None, None)
+        return (dx_ret, dc.view(cshape), None if gw is not None else dw, dbias, dgamma, dbeta, None, None, None, None, None)
 
 
 def proj_ln_packs(x, c, w, gamma):
@@ -1851,13 +1830,10 @@ def proj_ln_packs(x, c, w, gamma):
     return lin_packs(w)
 
 
-_FFN_FWD_TOUCH = True
-
-
 def touch_ffn_packs_next(ff, x):
     """the next otr_proj_ln_fwd launch (the attention sub-layer's closing launch) touches the two forward packs of the split FFN that
     follows it (3 MB the FFN launch's 252 workgroups would all wait for, cold, at their first phases): 4.43 -> 4.37 ms per step"""
-    if not _FFN_FWD_TOUCH or ff is None or getattr(ff, 'activation', None) != 'glu' or x.numel() // 256 < _FFN_SPLIT_MIN_ROWS:
+    if ff is None or getattr(ff, 'activation', None) != 'glu' or x.numel() // 256 < _FFN_SPLIT_MIN_ROWS:
         return
     packs = ffn_packs(ff.w_1.weight, ff.w_2.weight)
     if packs is None or packs[1].data_ptr() != packs[0].data_ptr() + packs[0].numel() * packs[0].element_size():
@@ -1867,8 +1843,7 @@ def touch_ffn_packs_next(ff, x):
 
 def proj_add_layernorm(x, c, w, b, gamma, beta, p_drop, eps, packs, link=None):
     ilink = LnInLink() if (_FFN_SLAB and torch.is_grad_enabled()) else None
-    y, ylp = ProjLnFn.apply(x, c, w, b, gamma, beta, float(p_drop), float(eps), packs, link, ilink, getattr(c, '_otr_touch', None),
-                            getattr(c, '_otr_touch_w', None))
+    y, ylp = ProjLnFn.apply(x, c, w, b, gamma, beta, float(p_drop), float(eps), packs, link, ilink)
     if ilink is not None and ilink.armed:
         y._otr_inlink = ilink
     return attach_lp(y, ylp)
@@ -1898,7 +1873,7 @@ class FeedForwardGLUFn(torch.autograd.Function):
         F = F2 // 2
         h = None
         u = torch.empty((M, F), dtype=adt, device=x.device)
-        if adt != torch.float32 and x2.dtype == adt and w1.dtype == adt and _FUSED_GLU_FWD:
+        if adt != torch.float32 and x2.dtype == adt and w1.dtype == adt:
             h = torch.empty((M, F2), dtype=adt, device=x.device)
             rc = L.load().otr_ffn_glu_fwd(_p(x2), x2.stride(0), _p(w1), w1.stride(0), _p(b1), _p(h), _p(u), M, F,
                                           x2.shape[1], _stream())
@@ -1926,7 +1901,7 @@ class FeedForwardGLUFn(torch.autograd.Function):
         db2 = None if ctx.defer_b2 else colsum_raw(dy2, out=gb2)
         dh = torch.empty_like(h)
         part = None
-        if ctx.w2t is not None and dy2.dtype == half_dtype() and h.dtype == dy2.dtype and is_half() and _FUSED_GLU_BWD:
+        if ctx.w2t is not None and dy2.dtype == half_dtype() and h.dtype == dy2.dtype and is_half():
             # one launch: du = dy . w2 stays in registers / LDS, GLU backward and the bias partials in the GEMM epilogue
             cap = (M + 63) // 64
             part = torch.empty((cap, 2 * F), dtype=torch.float32, device=dy.device)
@@ -1971,13 +1946,6 @@ _FUSED_FFN_MIN_ROWS = 1024   # below: too few 32-row workgroups to fill the chip
 _FFN_SPLIT = True
 # the split kernels in slab mode (no in-launch exchange; the LayerNorm moves into the next launch's prologue) where the caller allows it
 _FFN_SLAB = True
-_FFN_PREFETCH = True
-_Z_TOUCH = False
-_QKV_W_TOUCH = False              # experiment: ln_bwd_proj touches the q|k|v input-gradient pack
-_FFN_HSAVE_TOUCH = False      # experiment: the saved tiles (65 MB) as well
-# the same for the attention backward launch's saved q|k|v + context, touched by the LayerNorm-backward launch before it (otr_touch_hint):
-# -3.6 us per launch in tools/encattn_prefetch_probe.py, nothing measurable in the step (4.478 vs 4.471 / 4.500 ms on one box): off
-_ATTN_PREFETCH = False
 _FFN_SPLIT_MIN_ROWS = 2048
 _FFN_SYNC_INTS = 1 << 14
 
@@ -2132,13 +2100,10 @@ class FfnLnFn(torch.autograd.Function):
         ctx.olink = olink
         if olink is not None and need_grad:        # see LnOutLink: the next layer's first Linear may run this LayerNorm's backward
             olink.saved, olink.params, olink.armed = (z, mean, rstd, gamma, seed, p_drop, off), (gamma, beta, b2), True
-            if ctx.split and _FFN_PREFETCH and packs[3].data_ptr() == packs[2].data_ptr() + packs[2].numel() * packs[2].element_size():
+            if ctx.split and packs[3].data_ptr() == packs[2].data_ptr() + packs[2].numel() * packs[2].element_size():
                 # that launch is followed by THIS sub-layer's backward launch, whose two packs (adjacent in the pack buffer) it
                 # would fetch cold: have them touched on the way (otr_rb_linear_ln_bwd_pf)
-                extra = hsave if (_FFN_HSAVE_TOUCH and hsave is not None) else None
-                if extra is None and _Z_TOUCH and ilink is not None:
-                    extra = ilink.z          # experiment: the saved pre-norm sums of the attention sub-layer's LayerNorm (read two launches later)
-                olink.prefetch = (packs[2], (packs[2].numel() + packs[3].numel()) * packs[2].element_size(), extra)
+                olink.prefetch = (packs[2], (packs[2].numel() + packs[3].numel()) * packs[2].element_size())
         y16 = y16.view(x.shape)
         ctx.mark_non_differentiable(y16)
         return y.view(x.shape), y16
@@ -2291,8 +2256,6 @@ class GLUFn(torch.autograd.Function):
 
 
 GLU_RPB = 32        # rows per workgroup of otr_glu_bwd (csrc/elementwise.hip)
-_FUSED_GLU_BWD = True     # A/B switches for tuning runs
-_FUSED_GLU_FWD = True
 
 
 # ---------------------------------------------------------------------------------------- fused decoder stack
@@ -2300,7 +2263,6 @@ _FUSED_GLU_FWD = True
 # launches per layer and direction, cut along (utterance group, head) / (row block, hidden slice) instead of along operators
 # (csrc/declayer.hip).  A sub-layer leaves PARTIAL sums ("slabs") and the next launch finishes the LayerNorm in its prologue.
 _DEC_FUSED = True
-_DEC_TOUCH = True
 _DEC_FFN_SLICES = 8
 _EMBED_SINK = True     # A/B: the decoder stack's input gradient summed by the embedding's backward
 DEC_LAYER_PARAMS = 18      # qvk w,b | out w,b | norm1 w,b | q w,b | out w,b | norm2 w,b | w_1 w,b | w_2 w,b | norm3 w,b
@@ -2372,7 +2334,7 @@ class DecoderStackFn(torch.autograd.Function):
         layers, packs_all = [], []
         y_in, y_in16, pending = xres, x16, None          # pending = (slabs, nslab, bias, gamma, beta) of the FFN sub-layer below
         F = params[12].shape[0] // 2
-        if _DEC_TOUCH and need:
+        if need:
             # every packed weight of the stack (forward and input-gradient packs, ~40 MB) read once: the 36 launches of the forward and
             # backward pass then find them in the memory-side cache instead of HBM (csrc/elementwise.hip: otr_touch)
             rng = []
@@ -2544,7 +2506,6 @@ class _Grad16Link:
 
 
 _G16 = True
-_G16_LOSS = True      # A/B: the loss launch's gradient as a 16-bit operand of the output layer
 
 
 class PosEncFn(torch.autograd.Function):
@@ -2730,7 +2691,6 @@ def conv_geometry(T, F):
     return T1, F1, T2, F2
 
 
-_CONV2_WIDE = True                 # 256 -> 256 channels: conv2 input gradient on csrc/conv2wide.hip
 _CONV2_IMPLICIT_DGRAD = True       # tests switch it off to compare with the explicit (column matrix) path
 
 
@@ -2815,7 +2775,7 @@ class ConvSubsampleFn(torch.autograd.Function):
         L.check(lib.otr_conv2_wgrad(C.byref(desc), _p(g2), _p(act1), _p(dw2r), _p(_workspace(x.device)), _WS_BYTES, _stream()),
                 'otr_conv2_wgrad')
         rc = 1
-        if _CONV2_IMPLICIT_DGRAD and _CONV2_WIDE and C1 == 256 and C2 == 256:
+        if _CONV2_IMPLICIT_DGRAD and C1 == 256 and C2 == 256:
             rc = lib.otr_conv2_dgrad_wide(C.byref(desc), _p(g2), _p(w2r), _p(act1), _p(dact1), _p(_workspace(x.device)), _WS_BYTES, _stream())
         if rc == 1:
             rc = lib.otr_conv2_dgrad(C.byref(desc), _p(g2), _p(w2r), _p(act1), _p(dact1), _stream()) if _CONV2_IMPLICIT_DGRAD else 1
@@ -2874,8 +2834,6 @@ def _gemm_ptr(kind, M, N, K, x, w, y, bias=None, accumulate=0):
 _GEMM_BATCHED = True
 _BN_PART = True          # ConformerConvFn: BatchNorm batch statistics through per-workgroup sums
 _DW_PART = True      # ConformerConvFn: depthwise-conv parameter gradients through per-workgroup sums
-_DY16_WIDE = True           # LinearFn.backward: cast an fp32 gradient of the frontend's output layer to 16 bits once
-_ADD2_COLSUM = True         # RelPosAttentionFn.backward: d(q+u) + d(q+v) and the two column sums in one pass
 _CONV_MID_FUSED = True      # ConformerConvFn.backward: BatchNorm apply + depthwise conv + GLU backward in one launch
 _POS_DEFER = True      # RelPosAttentionFn: the per-head dp products join the grouped weight-gradient launch
 
@@ -3000,9 +2958,6 @@ def _dp_from_pool(Pp, d, device):
 _DBD_PERSIST = True        # tests flip it to compare with a fresh tensor per backward pass
 
 
-_DBD16 = True              # RelPosAttentionFn: the score term's gradient tensor in the 16-bit type (16-bit modes)
-
-
 def _persistent_dbd(owner, like, dtype=None):
     """The gradient tensor of the relative-position score term, [B, T, H, Pp] fp32 (64 MB per Conformer block at the bench batch).  Only its
     band (column j - i + T - 1 of row i) is ever non-zero, and the attention backward rewrites EVERY in-range band entry (masked pairs
@@ -3122,7 +3077,7 @@ class RelPosAttentionFn(torch.autograd.Function):
         dout = dout.contiguous()
         # r06: the score term's gradient travels 16-bit in the 16-bit modes (it is written once by the attention backward and read by two
         # GEMMs: 64 MB per block in fp32); the forward tensor bd stays fp32 (it is part of the logits' arithmetic)
-        dbd = _persistent_dbd(pos_w, bd, half_dtype() if (_DBD16 and adt == half_dtype()) else torch.float32)
+        dbd = _persistent_dbd(pos_w, bd, half_dtype() if adt == half_dtype() else torch.float32)
         dquv = torch.empty_like(quv)
         dqkv = torch.empty_like(qkv)
         delta = torch.empty_like(lse)
@@ -3151,7 +3106,7 @@ class RelPosAttentionFn(torch.autograd.Function):
                 _gemm_ptr('wgrad', M, Pp, dk, (quv, d + h * dk, 2 * d), (dp, h * dk, d), (dbd, h * Pp, H * Pp))
         dq2 = dquv.view(M, 2 * d)
         inpl_uv = gu is not None and gv is not None and gu.is_contiguous() and gv.is_contiguous()
-        if inpl_uv and _ADD2_COLSUM:
+        if inpl_uv:
             # r06: the sum and the two column sums in one pass (otr_add2_strided_colsum): per-workgroup partials [M / 32][2 d] join the
             # grouped column sums instead of the two [M, d] operands (147 MB per step re-read)
             part = torch.empty((lib.otr_add2_colsum_partial_rows(M), 2 * d), dtype=torch.float32, device=qkv.device)
@@ -3163,14 +3118,6 @@ class RelPosAttentionFn(torch.autograd.Function):
         else:
             L.check(lib.otr_add2_strided(_p(dquv), 2 * d, _p(dquv, d), 2 * d, _p(dqkv), d3, _code(adt), M, d, _stream()),
                     'otr_add2_strided')
-        if inpl_uv and _ADD2_COLSUM:
-            pass
-        elif inpl_uv:
-            # the two column sums join the grouped launch at the end of backward (they were 2 launches + 2 gradient adds per block)
-            colsum_raw(dq2[:, :d], out=gu.view(-1))
-            colsum_raw(dq2[:, d:], out=gv.view(-1))
-            du = dv = None
-        else:
             du, dv = colsum_raw(dq2[:, :d]).view(1, 1, H, dk), colsum_raw(dq2[:, d:]).view(1, 1, H, dk)
         if deferred:
             _wq['post'].append(lambda: linear_wgrad_raw(dp, pe, pos_w, out=gw))      # queued again: one more grouped launch for all blocks

@@ -24,8 +24,6 @@ from . import ops
 from .nn import (BOS, EOS, PAD, LabelSmoothingLoss, PositionalEncoding, TransformerEncoderLayer)
 
 _DECODE_STEP_FUSED = True   # cached beam step on otr_dec_self_step + the fused tail
-_DECODE_FFN16 = True
-_DECODE_FORK = True   # cached beam step: the LM chain on a side stream (CachedBeamState) -- only where the pair launches below do not apply
 _DECODE_LAGGED_STOP = True   # cached beam search: the all-finished test lags one step behind the launches (CachedBeamState.run); False = sync after every step
 _DECODE_PAIR = True   # cached beam step: the LM's layers ride in the decoder's launches (otr_dec_*_pair): one chain, no branch in the graph
 
@@ -401,7 +399,7 @@ class CachedBeamState:
         # the fused launches, the LM's layers are the SECOND problem of the decoder's own launches instead (otr_dec_self_step_pair,
         # otr_dec_ffn_fwd_pair, otr_dec_ln_pair: _fused_stacks_paired): the same concurrency, one chain, 23 nodes.
         self.paired = bool(_DECODE_PAIR and self.fused_dec and self.fused_lm and not self.lm_recurrent)
-        self.side = torch.cuda.Stream(device=dev) if (lm is not None and _DECODE_FORK and dev.type == 'cuda' and not self.paired) else None
+        self.side = torch.cuda.Stream(device=dev) if (lm is not None and dev.type == 'cuda' and not self.paired) else None
         self.side_ws = ops.new_workspace(dev) if self.side is not None else None
 
     def load_memory(self, memory, memory_mask):
@@ -562,7 +560,7 @@ class CachedBeamState:
             F = ff.w_2.weight.shape[1]
             # a few row blocks only: cut the hidden units 16 ways (a workgroup streams its slice of w_1 / w_2 at what ONE CU ingests,
             # 24 workgroups of 393 KB at S = 8); otr_dec_self_step and otr_dec_ln take up to 16 slabs
-            S = 16 if (_DECODE_FFN16 and F % 2048 == 0 and R <= 128) else ops.dec_ffn_slices(F)
+            S = 16 if (F % 2048 == 0 and R <= 128) else ops.dec_ffn_slices(F)
             packs = ops.ffn_packs(ff.w_1.weight, ff.w_2.weight)
             slC = h16(S, R, d)
             L.check(lib.otr_dec_ffn_fwd(C.byref(ln), R, ops._p(packs[0]), ops._p(ff.w_1.bias), ops._p(packs[1]), F, S, ops._p(slC), None, st),
@@ -633,7 +631,7 @@ class CachedBeamState:
             def ffn_item(self):
                 ff = self.blocks[self.li].feed_forward
                 F = ff.w_2.weight.shape[1]
-                self.S = 16 if (_DECODE_FFN16 and F % 2048 == 0 and R <= 128) else ops.dec_ffn_slices(F)
+                self.S = 16 if (F % 2048 == 0 and R <= 128) else ops.dec_ffn_slices(F)
                 packs = ops.ffn_packs(ff.w_1.weight, ff.w_2.weight)
                 self.slC = h16(self.S, R, d)
                 it = L.DecFfnFwd()

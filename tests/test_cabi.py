@@ -202,6 +202,18 @@ def test_wgrad256_eligibility_rule_is_host_logic():
             lib.otr_debug_set(6, -1)
 
 
+def test_debug_set_refuses_retired_keys():
+    """otr_debug_set (no GPU needed): a retired tuning key is refused like an unknown one (-1 and an error string), so an
+    OTR_DEBUG_SET naming it makes _lib.load() raise instead of measuring the default twice; a kept key is still accepted."""
+    from opentransformer_amd import _lib as L
+    for kind in ('bf16', 'fp16'):
+        lib = L.load(kind)
+        for key in (19, 4, 32):
+            assert lib.otr_debug_set(key, 0) == -1
+            assert b'unknown key %d' % key in lib.otr_last_error_string()
+        assert lib.otr_debug_set(6, -1) == 0
+
+
 def _wgrad256_pieces(plan, starts, Ms):
     """tests' replay of wgrad256_kernel's work decoding (csrc/wgrad256.hip: slot <- block, pieces of a slot)"""
     mode, G, chunk, nfull, rem, parts, total, n = plan

@@ -1,6 +1,5 @@
-"""tuning aid: the conv2wide launch alone (conv2 input gradient at the Conformer bench shape), timed with events, under otr_debug_set(32, v)"""
+"""tuning aid: the conv2wide launch alone (conv2 input gradient at the Conformer bench shape), timed with events"""
 import ctypes as C
-import sys
 import torch
 from opentransformer_amd import _lib as L, ops
 
@@ -20,21 +19,17 @@ desc = L.ConvDesc(B, T, Fd, C1, C2, T1, F1, T2, F2, ops._code(adt), ops._compute
 ws = ops._workspace(act1.device)
 
 
-def run(which):
+def run():
     return lib.otr_conv2_dgrad_wide(C.byref(desc), ops._p(g2), ops._p(w2r), ops._p(act1), ops._p(dact1), ops._p(ws), ops._WS_BYTES, ops._stream())
 
 
-for abl in [int(a) for a in (sys.argv[1:] or ['0'])]:
-    lib.otr_debug_set(32, abl)
-    for which in ('dgrad',):
-        for _ in range(3):
-            assert run(which) == 0
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(10):
-            run(which)
-        e1.record()
-        torch.cuda.synchronize()
-        print('ablate %2d %-5s %.1f us' % (abl, which, e0.elapsed_time(e1) * 100), flush=True)
-lib.otr_debug_set(32, 0)
+for _ in range(3):
+    assert run() == 0
+torch.cuda.synchronize()
+e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+e0.record()
+for _ in range(10):
+    run()
+e1.record()
+torch.cuda.synchronize()
+print('dgrad %.1f us' % (e0.elapsed_time(e1) * 100), flush=True)

@@ -1,7 +1,6 @@
 """tuning aid: otr_attention_bias_bwd at the Conformer bench shape (B 32, T' 249, 4 heads x 96), timed with events, under otr_debug_set(33, v):
-0 = the streamed dQ + dK/dV pair, 1 = csrc/encattn96.hip, 1 | 2a = its ablations (a & 1 no score-term loads, a & 2 no d bias stores, a & 4 no tiles)"""
+0 = the streamed dQ + dK/dV pair, 1 = csrc/encattn96.hip"""
 import ctypes as C
-import sys
 import torch
 from opentransformer_amd import _lib as L, ops
 
@@ -34,7 +33,7 @@ def run():
                                       ops._p(dkv, 2 * d), ops._stream())
 
 
-for v in [int(a) for a in (sys.argv[1:] or ['1', '0'])]:
+for v in (1, 0):
     lib.otr_debug_set(33, v)
     for _ in range(3):
         assert run() == 0
@@ -45,5 +44,5 @@ for v in [int(a) for a in (sys.argv[1:] or ['1', '0'])]:
         run()
     e1.record()
     torch.cuda.synchronize()
-    print('debug_set(33, %2d): %.1f us' % (v, e0.elapsed_time(e1) * 50), flush=True)
+    print('debug_set(33, %d): %.1f us' % (v, e0.elapsed_time(e1) * 50), flush=True)
 lib.otr_debug_set(33, 1)

@@ -26,7 +26,7 @@ def run():
     L.check(lib.otr_ffn_bwd_split_slab(p(da), p(hsave), p(P[2]), p(P[3]), p(dh), p(bsl), M, F, d, st()), 'bwd')
 for _ in range(3): run()
 tr = torch.zeros(256 * 48, dtype=torch.int64, device=dev)
-lib.otr_debug_set(4, 16); lib.otr_debug_trace(p(tr)); run(); torch.cuda.synchronize(); lib.otr_debug_trace(None); lib.otr_debug_set(4, 0)
+lib.otr_debug_trace(p(tr)); run(); torch.cuda.synchronize(); lib.otr_debug_trace(None)   # a set buffer selects the stamped kernels
 t = tr.cpu().numpy().reshape(256, 48)
 t = t[t[:, 0] > 0]
 n = int((t[0] > 0).sum())

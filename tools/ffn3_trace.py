@@ -36,7 +36,7 @@ def run():
                                      p(z), p(mean), p(rstd), p(hsave) if save else None, p(usave) if save else None, p(scratch), nb, p(sync), sync.numel(), M, F, d, st()), 'fwd3')
 for _ in range(3): run()
 tr = torch.zeros(256 * 48 + 512, dtype=torch.int64, device=dev)
-lib.otr_debug_set(4, 16); lib.otr_debug_trace(p(tr)); run(); torch.cuda.synchronize(); lib.otr_debug_trace(None); lib.otr_debug_set(4, 0)
+lib.otr_debug_trace(p(tr)); run(); torch.cuda.synchronize(); lib.otr_debug_trace(None)   # a set buffer selects the stamped kernels
 rt = tr.cpu().numpy()[256 * 48:].reshape(256, 2)
 t = tr.cpu().numpy()[:256 * 48].reshape(256, 48)
 live = t[:, 0] > 0

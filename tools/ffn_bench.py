@@ -110,16 +110,6 @@ def main():
     res['split_vs_v1_dx_rel'] = float((dx3 - dxz).norm() / dxz.norm())
     res['split_vs_v1_dh_rel'] = float((dh3[:M].float() - dh.float()).norm() / dh.float().norm())
     res['split_vs_v1_u_rel'] = float((usave[:M].float() - u.float()).norm() / u.float().norm())
-    for ab in (1, 2, 3):
-        lib.otr_debug_set(4, ab)
-        res['split_fwd_ablate%d_us' % ab] = timeit(lambda: fwd3(0.0), a.iters)
-        res['split_bwd_ablate%d_us' % ab] = timeit(bwd3, a.iters)
-    for ab in (4, 8, 12):     # 4 = no global stores of the saved tiles / dh, 8 = no tile loads (backward), 12 = neither
-        lib.otr_debug_set(4, ab)
-        if ab == 4:
-            res['split_fwd_save_ablate4_us'] = timeit(lambda: fwd3(0.0, True), a.iters)
-        res['split_bwd_ablate%d_us' % ab] = timeit(bwd3, a.iters)
-    lib.otr_debug_set(4, 0)
     # in the step every layer saves into its own buffers (12 x 98 MB) and the backward kernels read them back much later: the
     # same launches cycling through N distinct (hsave, usave / dh) sets
     for ncyc in (2, 12):
@@ -183,10 +173,6 @@ def main():
                                          sync.numel(), M, F, d, st()), 'fwd3')
     res['split_fwd_nosave_cold_us'] = timeit(fwd_wn, 48)
     res['split_fwd_nosave_coldx_warmw_us'] = timeit(fwd_xn, 48)
-    lib.otr_debug_set(4, 1)
-    res['split_fwd_save_cold_nodma_us'] = timeit(fwd_w, 48)
-    res['split_bwd_cold_nodma_us'] = timeit(bwd_w, 48)
-    lib.otr_debug_set(4, 0)
     del Ps, hs, us, ds, xs
     res['split_fwd_tflops'] = 2.0 * M * 3 * F * d / res['split_fwd_us'] / 1e6
     res['split_bwd_tflops'] = 2.0 * M * 3 * F * d / res['split_bwd_us'] / 1e6

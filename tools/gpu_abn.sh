@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B/C... on one box: the timed region of bench.py under several values of ONE environment variable, two alternating rounds
-# usage: gpu_abn.sh TAG VAR VALUE...     e.g.  gpu_abn.sh s1 OTR_SWITCHES ops._DEC_TOUCH=1 ops._DEC_TOUCH=0 ops._DEC_FFN_SLICES=16
+# usage: gpu_abn.sh TAG VAR VALUE...     e.g.  gpu_abn.sh s1 OTR_SWITCHES ops._FFN_SLAB=1 ops._FFN_SLAB=0 ops._DEC_FFN_SLICES=16
 TAG=$1; VAR=$2; shift 2
 OUT=gpurun_out/$TAG
 mkdir -p $OUT

@@ -19,13 +19,10 @@ def main():
     ap.add_argument('--grids', default='0')
     ap.add_argument('--layers', type=int, default=12)
     ap.add_argument('--rows', type=int, default=7968)
-    ap.add_argument('--ablate', default='')
-    ap.add_argument('--base', type=int, default=0, help='otr_debug_set(8, v) for the main runs (0 = shipped policy)')
     ap.add_argument('--alias', action='store_true', help='every layer reads the SAME operand tensors (cache-resident working set)')
     a = ap.parse_args()
     ops.set_compute_dtype(a.mode)
     lib = L.load()
-    lib.otr_debug_set(8, a.base)
     dev = 'cuda:0'
     adt = ops.act_dtype()
     M = a.rows
@@ -85,13 +82,6 @@ def main():
         err = max(float((o - r).abs().max()) / float(r.abs().max()) for (_, _, o), r in zip(items, ref))
         t = timed(1, grid)
         out['wgrad256_grid%d' % grid] = {'ms': t, 'tflops': flops / t / 1e9, 'tb_per_s': nbytes / t / 1e9, 'max_rel_err_vs_128': err}
-    for ab in [int(v) for v in a.ablate.split(',') if v]:
-        lib.otr_debug_set(8, ab)
-        out['ablate%d_grid-248_ms' % ab] = timed(1, -248)
-        if ab >= 8:
-            out['ablate%d_grid0_ms' % ab] = timed(1, 0)
-    lib.otr_debug_set(8, a.base)
-    lib.otr_debug_set(8, 0)
     lib.otr_debug_set(6, -1)
     lib.otr_debug_set(7, 0)
     print(json.dumps(out))

@@ -32,8 +32,6 @@ for i in range(6):
 items.append((rnd(M, 256), rnd(M, 608), torch.zeros(256, 608, device=dev)))
 lib.otr_debug_set(6, 1)
 lib.otr_debug_set(7, grid)
-if len(sys.argv) > 3:
-    lib.otr_debug_set(8, int(sys.argv[3]))
 for _ in range(n):
     ops._wq['w'], ops._wq['b'] = list(items), []
     ops.flush_weight_grads()
