@@ -41,8 +41,6 @@ int g_otr_force_ksplit = 0;
 int g_otr_conv2_wgrad256 = 1;       // conv2 weight gradient of a C1 % 256 == 0 frontend on wgrad256.hip's gather form (otr_debug_set(29, 0) = the transposing GEMM)
 int g_otr_attn_enc96 = 1;          // encattn96.hip: the Conformer's attention backward on the whole-utterance kernel (otr_debug_set(33, 0) = the streamed dQ / dK,dV pair)
 int g_otr_wgrad256 = -1;     // 256x256-tile weight-gradient launch (wgrad256.hip): -1 = environment OTR_WGRAD256 (default on), 0 / 1 (otr_debug_set(6, v))
-extern int g_otr_conv2_dgrad_wide;     // conv.hip (otr_debug_set(30, v))
-extern int g_otr_conv2_wide;           // conv.hip (otr_debug_set(31, v))
 int g_otr_wgrad256_grid = 0; // workgroups of that launch; 0 = one per CU (otr_debug_set(7, v))
 int g_otr_conv2_fwd_direct = 1;  // conv2 forward on the weight-stationary kernel where it serves (otr_debug_set(22, v))
 int g_otr_attn_enc = 1;          // encoder-shape attention backward with the whole (utterance, head) in LDS (otr_debug_set(21, v))

@@ -816,7 +816,6 @@ static int32_t fill_args(const otr_attn_desc_t* d, AttnArgs& a) {
   a.causal = d->causal; a.scale = d->scale;
   return 0;
 }
-extern int g_otr_attn_xmap;        // api.hip (otr_debug_set(16, v)): XCD-aware workgroup mapping of the attention launches
 static dim3 attn_grid(AttnArgs& a, const otr_attn_desc_t* d, int nx) {
   a.xmap = g_otr_attn_xmap;
   return a.xmap ? dim3((unsigned)(8 * nx * ((d->H * d->B + 7) / 8))) : dim3((unsigned)nx, d->H, d->B);
@@ -930,8 +929,6 @@ extern "C" int32_t otr_attention_bwd(const otr_attn_desc_t* d, const void* q, co
   return attention_bwd_impl(d, a, stream);
 }
 
-extern int g_otr_attn_bwd_split;   // api.hip (otr_debug_set(13, 1)): the two-launch form, for A/B runs
-extern int g_otr_attn_enc;         // api.hip (otr_debug_set(21, v)): the whole-utterance-in-LDS backward kernel (encattn.hip) where it serves
 bool encattn_bwd_takes(int dtype_is_h16, int dk, int Tq, int Tk, int causal, int has_bias, int vec);
 // encattn96.hip: the Conformer's relative-position self-attention backward (head dim 96, score term) on the whole-utterance design
 bool encattn96_bwd_takes(int dtype_is_h16, int dk, int Tq, int Tk, int causal, int has_bias, int rel_shift, int bias_vec4, int has_dbias, int vec);

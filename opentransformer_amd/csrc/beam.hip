@@ -10,7 +10,6 @@
 
 #define NEG_INF (-__builtin_huge_valf())
 constexpr int MAXK = 16;
-extern int g_otr_beam_reg;     // api.hip (otr_debug_set(25, v)): 1 = the register-resident top-k kernel where the vocabulary fits
 
 __device__ __forceinline__ void block_lse(const float* x, int V, float* sh, float& mx, float& lse) {
   float m = NEG_INF;

@@ -48,6 +48,30 @@ void otr_zero_f32(float* p, int64_t n, hipStream_t s);
     }                                   \
   } while (0)
 
+// ---------------------------------------------------------------- runtime settings (host)
+// Defined in api.hip (conv.hip: the two conv2_*wide switches) and set through otr_debug_set / otr_debug_trace /
+// otr_set_fault_counter; the otr_debug_set key of each is noted at its definition.
+extern int g_otr_force_tile;           // GEMM tile: 0 = heuristic, 64 / 128 = forced
+extern int g_otr_force_ksplit;         // GEMM split-K: 0 = heuristic, n = forced
+extern int g_otr_conv2_wgrad256;
+extern int g_otr_attn_enc96;
+extern int g_otr_wgrad256;
+extern int g_otr_wgrad256_grid;
+extern int g_otr_conv2_dgrad_wide;
+extern int g_otr_conv2_wide;
+extern int g_otr_conv2_fwd_direct;
+extern int g_otr_attn_enc;
+extern int g_otr_attn_xmap;
+extern int g_otr_attn_bwd_split;
+extern int g_otr_beam_reg;
+extern int g_otr_decode_attn64;
+extern int g_otr_dec_group;
+extern int g_otr_ffn_map;
+extern int g_otr_ffn_coh_only;
+extern int g_otr_spin_limit;           // bound of every in-kernel turnstile / arrival spin
+extern int32_t* g_otr_fault;           // sticky device fault word the spin-bounded kernels add 1 to when they give up, or NULL
+extern unsigned long long* g_otr_trace;  // clock-stamp buffer of the tuning hooks, or NULL
+
 // ---------------------------------------------------------------- explicit global-memory accesses
 // A pointer that reaches a kernel through a table in memory (grouped GEMM) has no known address space and its
 // accesses compile to flat_load / flat_store, which count on lgkmcnt as well: every LDS wait then also waits for
@@ -117,6 +141,70 @@ __device__ __forceinline__ void mma32(f32x16& acc, const uint4& a, const uint4& 
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
 #endif
 }
+
+// The same MFMA as an asm statement with the register classes spelled out: the accumulator in VGPRs, one operand in the
+// ACCUMULATOR half of the register file ("a": it is an MFMA operand only).  With the builtin hipcc keeps both operands in
+// VGPRs, and a kernel whose resident operands fill the architectural registers then shuttles them through AGPRs (ffn3.hip's
+// first build: 160 v_accvgpr moves per 32 MFMAs) or has none left to read the other operand ahead (conv2fwd.hip: every MFMA
+// waited for its own ds_read).  Hazards (hipcc pads nothing inside asm, cdna_hip_programming.md 5.7): the accumulate chain
+// D -> C of the next MFMA needs no wait states; VALU readers of the result must wait themselves (>= 12 states); and every
+// statement opens with `s_nop 1`: hipcc is free to place a VALU write of an operand (a register copy of a bias-initialised
+// accumulator, seen in one build of ffn3.hip: the first chunk's row tile 0 came out wrong) directly in front of the statement,
+// and a VALU write -> MFMA read needs two wait states.  Inside a back-to-back MFMA stream the two states hide behind the busy pipe.
+#ifdef OTR_HALF_FP16
+#define OTR_MFMA32_OP "v_mfma_f32_32x32x16_f16"
+#else
+#define OTR_MFMA32_OP "v_mfma_f32_32x32x16_bf16"
+#endif
+__device__ __forceinline__ void mma32_agpr_b(f32x16& acc, const otr_u32x4& a, const otr_u32x4& b_acc) {   // B in AGPRs
+  asm volatile("s_nop 1\n\t" OTR_MFMA32_OP " %0, %1, %2, %0" : "+v"(acc) : "v"(a), "a"(b_acc));
+}
+__device__ __forceinline__ void mma32_agpr_a(f32x16& acc, const otr_u32x4& a_acc, const otr_u32x4& b) {   // A in AGPRs
+  asm volatile("s_nop 1\n\t" OTR_MFMA32_OP " %0, %1, %2, %0" : "+v"(acc) : "a"(a_acc), "v"(b));
+}
+
+// ---------------------------------------------------------------- direct-to-LDS DMA and explicit waits
+// One wave instruction: 64 lanes x 16 B from global memory -> LDS [lds_dst, lds_dst + 1024) lane-linear, asynchronous (vmcnt).
+// Inline asm, not __builtin_amdgcn_global_load_lds: with the builtin hipcc tracks the pending LDS write and puts
+// `s_waitcnt vmcnt(0)` in front of the next ds_read of ANY address -- i.e. it waited for the chunk it had just started to
+// fetch before multiplying the current one (seen in the ISA: the whole DMA latency exposed per chunk).  The asm form is
+// invisible to that bookkeeping; the kernels wait themselves (wait_vm + barrier before a buffer is read).
+// M0 carries the wave-uniform LDS byte address (lds_dst) and is restored afterwards (cdna_hip_programming.md 5.7).
+typedef __attribute__((address_space(3))) unsigned char lds_byte;    // (uint32_t)(uintptr_t)(lds_byte*)p: LDS byte address of p
+
+// per-lane source address; NT = non-temporal (a stream nobody else reads)
+template <bool NT = false> __device__ __forceinline__ void lds_dma(const void* src, uint32_t lds_dst) {
+  uint32_t keep;
+  if constexpr (NT)
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(src), "s"(lds_dst) : "memory");
+  else
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(src), "s"(lds_dst) : "memory");
+}
+// wave-uniform source (SGPR base) + 32-bit per-lane byte offset: scalar address arithmetic only, and no per-lane 64-bit address
+// for hipcc to hoist out of a loop as a loop invariant (conv2wide.hip: 288 registers for 36 chunks)
+__device__ __forceinline__ void lds_dma_sbase(const void* uniform_src, uint32_t lane_off, uint32_t lds_dst) {
+  uint32_t keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(lane_off), "s"(uniform_src), "s"(lds_dst) : "memory");
+}
+template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+__device__ __forceinline__ void wait_lds() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+
+// ---------------------------------------------------------------- clock stamps (tuning hook, otr_debug_trace)
+// Thread 0 of a workgroup stamps the shader clock into trace[OTR_STAMP_BASE + (kernel id * 256 + unit) * 16 + k], unit < 256,
+// k < 16, when TRACE is set and LIVE holds (the caller's own condition, e.g. that its unit is below 256); the first
+// OTR_STAMP_BASE entries are the GEMM kernels' region of the same buffer (gemm_kernel.h).  Kernel ids: declayer.hip 0-5 (one per
+// launch), encattn.hip 6-7 (6 + orientation), conv2fwd.hip 9.  tools/dec_trace.py, encattn_trace.py and conv2fwd_trace.py
+// decode the region.
+constexpr int OTR_STAMP_BASE = 16384;
+constexpr int OTR_KID_DECLAYER = 0, OTR_KID_ENCATTN = 6, OTR_KID_CONV2FWD = 9;
+#define OTR_STAMP(TRACE, KID, UNIT, K, LIVE)                                                                    \
+  do {                                                                                                          \
+    if ((TRACE) && threadIdx.x == 0 && (LIVE))                                                                  \
+      (TRACE)[OTR_STAMP_BASE + ((KID) * 256 + (UNIT)) * 16 + (K)] = __builtin_amdgcn_s_memtime();               \
+  } while (0)
 
 template <class T> struct ElemIO;
 template <> struct ElemIO<float> {

@@ -329,7 +329,6 @@ extern "C" int32_t otr_conv2_col2im(const otr_conv_desc_t* d, const void* dcol, 
 // ReLU mask of act1 is applied.  Nothing like the [pixels, 9*C1] column matrix of the explicit form is written or read
 // (184 MB each way at the AISHELL shapes: the GEMM + col2im pair took 77 + 70 us).  Workgroups are persistent, belong to one
 // class (their A fragments never change) and the classes get workgroups in proportion to pixels x taps.
-extern unsigned long long* g_otr_trace;   // api.hip (otr_debug_trace)
 int g_otr_conv2_dgrad_wide = 1;           // the sliced form for 256-channel outputs (otr_debug_set(30, 0) = column matrix + col2im)
 struct Conv2DgArgs {
   const uint16_t* g2; const uint16_t* w2r; const uint16_t* act1; uint16_t* dact1;

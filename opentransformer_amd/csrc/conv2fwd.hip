@@ -18,26 +18,14 @@ constexpr int C2F_PS = 144;               // bytes per staged pixel (64 channels
 constexpr int C2F_LDS = 108 * 1024;        // 2 RPI + 2 staged rows: the fused form's last work item of an utterance computes one row more
 constexpr int C2F_NT = 5;                 // 32-pixel tiles per work item
 
-// The MFMA with the register classes spelled out (as csrc/ffn3.hip): the weight fragment lives in the ACCUMULATOR half of the register
-// file (it is an MFMA operand only), which leaves the architectural registers to the accumulators and a ring of B operands read
-// ahead from LDS.  (With the builtin, hipcc kept the 144 weight registers in VGPRs, had none left to read ahead, and every MFMA
-// waited for its own ds_read: 50 us.)  `s_nop 1`: hipcc pads nothing in front of an asm statement (VALU write -> MFMA read hazard).
-#ifdef OTR_HALF_FP16
-#define C2F_MFMA_OP "v_mfma_f32_32x32x16_f16"
-#else
-#define C2F_MFMA_OP "v_mfma_f32_32x32x16_bf16"
-#endif
-typedef uint32_t c2f_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void c2f_mma(f32x16& acc, const c2f_u32x4& w_acc, const c2f_u32x4& b) {
-  asm volatile("s_nop 1\n\t" C2F_MFMA_OP " %0, %1, %2, %0" : "+v"(acc) : "a"(w_acc), "v"(b));
-}
-__device__ __forceinline__ c2f_u32x4 c2f_lds(const unsigned char* p) {
+// The MFMA is mma32_agpr_a (common.h): the weight fragments live in the ACCUMULATOR half of the register file, which leaves the
+// architectural registers to the accumulators and a ring of B operands read ahead from LDS.  (With the builtin, hipcc kept the 144
+// weight registers in VGPRs, had none left to read ahead, and every MFMA waited for its own ds_read: 50 us.)
+__device__ __forceinline__ otr_u32x4 c2f_lds(const unsigned char* p) {
   const uint4 t = *reinterpret_cast<const uint4*>(p);
-  return c2f_u32x4{t.x, t.y, t.z, t.w};
+  return otr_u32x4{t.x, t.y, t.z, t.w};
 }
 
-// tuning hook (otr_debug_trace): thread 0 stamps the shader clock into trace[16384 + (9 * 256 + workgroup) * 16 + k]
-#define C2F_STAMP(K) do { if (p.trace && threadIdx.x == 0) p.trace[16384 + (9 * 256 + (int)blockIdx.x) * 16 + (K)] = __builtin_amdgcn_s_memtime(); } while (0)
 struct Conv2FwdArgs {
   unsigned long long* trace;
   const uint16_t* act1; const uint16_t* w2r; const float* b2; uint16_t* act2;
@@ -61,7 +49,7 @@ __global__ __launch_bounds__(256, 1) void conv2_fwd_kernel(Conv2FwdArgs p) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[C2F_LDS];
   const int tid = threadIdx.x, lane = tid & 63, m = lane & 31, hi = lane >> 5;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  C2F_STAMP(0);
+  OTR_STAMP(p.trace, OTR_KID_CONV2FWD, (int)blockIdx.x, 0, true);
 
   // the padding pixels, once: nothing ever overwrites them
   for (int i = tid; i < (NIN + 1) * 18; i += 256) {
@@ -69,13 +57,13 @@ __global__ __launch_bounds__(256, 1) void conv2_fwd_kernel(Conv2FwdArgs p) {
     *reinterpret_cast<uint4*>(smem + r * RS + (side ? (F1 + 1) * C2F_PS : 0) + c * 16) = make_uint4(0u, 0u, 0u, 0u);
   }
   // this wave's weights: fragment (tap, ks): lane (m, hi) holds W[32 wid + m][tap][16 ks + 8 hi .. + 7]
-  c2f_u32x4 wf[36];
+  otr_u32x4 wf[36];
 #pragma unroll
   for (int t = 0; t < 9; ++t)
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       const uint4 q = ld_global_b128(p.w2r + ((int64_t)(32 * wid + m) * 9 + t) * C1 + 16 * ks + 8 * hi);
-      wf[t * 4 + ks] = c2f_u32x4{q.x, q.y, q.z, q.w};
+      wf[t * 4 + ks] = otr_u32x4{q.x, q.y, q.z, q.w};
     }
 #pragma unroll
   for (int i = 0; i < 36; ++i) asm volatile("" : "+a"(wf[i]));        // pinned to the accumulator registers
@@ -120,7 +108,7 @@ __global__ __launch_bounds__(256, 1) void conv2_fwd_kernel(Conv2FwdArgs p) {
     const int t2_0 = blk * RPI, r0 = 2 * t2_0;
     const uint16_t* src = p.act1 + (int64_t)b * p.T1 * (F1 * C1);
     __syncthreads();                                               // the previous item's reads are done
-    if (item == (int)blockIdx.x) C2F_STAMP(1);
+    if (item == (int)blockIdx.x) OTR_STAMP(p.trace, OTR_KID_CONV2FWD, (int)blockIdx.x, 1, true);
     int nst = 0;
     uint16_t* a1 = nullptr;
     auto store_act1 = [&](int i0, int i1) {
@@ -179,7 +167,7 @@ __global__ __launch_bounds__(256, 1) void conv2_fwd_kernel(Conv2FwdArgs p) {
         }
       }
       __syncthreads();
-      if (item == (int)blockIdx.x) C2F_STAMP(2);
+      if (item == (int)blockIdx.x) OTR_STAMP(p.trace, OTR_KID_CONV2FWD, (int)blockIdx.x, 2, true);
       if (item + (int)gridDim.x < p.nitems) load_x(item + (int)gridDim.x);
       // act1 for the backward pass: the rows this item OWNS (the first 2 RPI of its window; the last item of an utterance: all that
       // are left), as whole 128-byte pixel rows
@@ -207,14 +195,14 @@ __global__ __launch_bounds__(256, 1) void conv2_fwd_kernel(Conv2FwdArgs p) {
       }
     }
     __syncthreads();
-    if (item == (int)blockIdx.x) C2F_STAMP(2);
+    if (item == (int)blockIdx.x) OTR_STAMP(p.trace, OTR_KID_CONV2FWD, (int)blockIdx.x, 2, true);
     }
     uint16_t* dst = p.act2 + ((int64_t)b * p.T2 + t2_0) * (F2 * C2) + 32 * wid + 4 * hi;
     // the 5 x 36 (tile, tap, step) products as ONE stream with the B operands read PD steps ahead (across tile boundaries)
     constexpr int PD = 8, NSTEP = C2F_NT * 36;
     auto b_of = [&](int g) { const int pt = g / 36, s = g % 36, t = s >> 2, ks = s & 3;
                              return c2f_lds(smem + boff[pt] + (t / 3) * RS + (t % 3) * C2F_PS + ks * 32); };
-    c2f_u32x4 ring[PD];
+    otr_u32x4 ring[PD];
 #pragma unroll
     for (int g = 0; g < PD; ++g) ring[g] = b_of(g);
 #pragma unroll
@@ -225,7 +213,7 @@ __global__ __launch_bounds__(256, 1) void conv2_fwd_kernel(Conv2FwdArgs p) {
 #pragma unroll
       for (int s = 0; s < 36; ++s) {
         const int g = pt * 36 + s;
-        c2f_mma(acc, wf[s], ring[g % PD]);
+        mma32_agpr_a(acc, wf[s], ring[g % PD]);
         if (g + PD < NSTEP) ring[g % PD] = b_of(g + PD);
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -240,15 +228,12 @@ __global__ __launch_bounds__(256, 1) void conv2_fwd_kernel(Conv2FwdArgs p) {
       }
     }
     if constexpr (FUSE1) store_act1(4 * C2F_NT, 4 * C2F_NT + 8);      // the last item of an utterance owns up to two rows more
-    if (item == (int)blockIdx.x) C2F_STAMP(3);
+    if (item == (int)blockIdx.x) OTR_STAMP(p.trace, OTR_KID_CONV2FWD, (int)blockIdx.x, 3, true);
   }
-  C2F_STAMP(4);
+  OTR_STAMP(p.trace, OTR_KID_CONV2FWD, (int)blockIdx.x, 4, true);
 }
 
 }  // namespace
-
-extern unsigned long long* g_otr_trace;
-extern int g_otr_conv2_fwd_direct;         // api.hip (otr_debug_set(22, v)): 0 = the implicit-GEMM path everywhere
 
 // 0 = launched, 1 = not served (the caller takes the implicit-GEMM path)
 int32_t conv2_fwd_direct(const void* act1, const void* w2r, const float* b2, void* act2, int B, int T1, int F1, int T2, int F2, int C1, int C2,

@@ -30,16 +30,6 @@ struct CwArgs {
   int wg0[5];                // parity class c = 2 pt + pf owns workgroups [wg0[c], wg0[c+1])
 };
 
-typedef __attribute__((address_space(3))) unsigned char cw_lds_byte;
-// one wave instruction: 64 lanes x 16 B, per-lane global source -> LDS [dst, dst + 1024) lane-linear (see wgrad256.hip dma16)
-// (scalar base + 32-bit lane offset: per-lane 64-bit addresses of every chunk are loop invariants that hipcc hoists out of the tile loop --
-//  288 registers for the forward's 36 chunks)
-__device__ __forceinline__ void cw_dma16(const void* sbase, uint32_t voff, uint32_t lds_dst) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-
 constexpr int CW_C = 256, CW_KS = 16, CW_CHUNK = 1024, CW_RING = 3;   // CW_CHUNK: uint4 entries per (tap, k half, slice) chunk = 16 KB
 constexpr int CW_NBUF = 8, CW_AHEAD = 6;                              // LDS ring of chunks; how many chunks ahead the DMA runs      // channels (both sides); k-steps per tap; uint4 entries per (tap, slice) chunk
 
@@ -106,11 +96,11 @@ __device__ __forceinline__ void cw_body(const CwArgs& p, uint4* wbuf, uint4* ebu
   // chunk, those of the 5 chunks after it (10) and at least one group of 8 row pieces (every 4th chunk issues one): vmcnt(18) never lets
   // chunk c itself stay in flight -- except while the pipeline fills (the first tile's first chunks: drained with vmcnt(0)).  The waits
   // hipcc adds for the loads it knows (row pieces, masks, bias) count too few instructions and therefore only ever wait longer.
-  const uint32_t wdst = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(cw_lds_byte*)reinterpret_cast<unsigned char*>(wbuf) + (uint32_t)(wid * 1024));
+  const uint32_t wdst = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_byte*)reinterpret_cast<unsigned char*>(wbuf) + (uint32_t)(wid * 1024));
   auto dma_chunk = [&](int c) {
     const uint4* src = chunk_of(c % NCH);
 #pragma unroll
-    for (int q = 0; q < 2; ++q) cw_dma16(src, (uint32_t)((tid + 512 * q) * 16), wdst + (uint32_t)(((c & (CW_NBUF - 1)) * CW_CHUNK + 512 * q) * 16));
+    for (int q = 0; q < 2; ++q) lds_dma_sbase(src, (uint32_t)((tid + 512 * q) * 16), wdst + (uint32_t)(((c & (CW_NBUF - 1)) * CW_CHUNK + 512 * q) * 16));
   };
   uint4 bq[CW_KS];                                              // B operand: this lane's pieces of its pixel's row of the current tap
   CwPix px = pix_of(w * 256 + wid * 32 + pl);

@@ -24,10 +24,8 @@
 // z / mean / rstd for the backward pass.  Weights are the fragment-major packs the row-block kernels use (otr_pack_frags):
 // a head's columns are whole 32-row tiles of the q|k|v pack, and its share of the output projection is 4 of the 16 contraction
 // steps of that pack.  d_model = 256, 4 heads of 64, 16-bit operands.
-#include "ffn_frag.h"
+#include "tile32.h"
 #include "ln_pro.h"
-
-extern int g_otr_dec_group;     // api.hip (otr_debug_set(23, v)): cap on the utterances per attention workgroup, 0 = dl_group_size's choice
 
 namespace {
 
@@ -36,13 +34,7 @@ constexpr int DL_YS = DL_D * 2 + 16;      // bytes per row of the [32][256] 16-b
 constexpr int DL_HS = DL_DK * 2 + 16;     // bytes per row of a [32][64] 16-bit head image (q, k, context)
 constexpr int DL_VT = DL_RB * 2 + 8;      // bytes per row of a transposed [64][32] value image
 constexpr int DL_RS = DL_D + 4;           // floats per row of the fp32 output staging tile
-// tuning hook (otr_debug_trace): thread 0 of every workgroup stamps the shader clock into trace[16384 + (kernel id * 256 + workgroup) * 16 + k]
-// (the first 16384 entries are the GEMM kernels' region of the same buffer)
-#define DL_STAMP(KID, K) do { if (p.trace && threadIdx.x == 0) p.trace[16384 + ((KID) * 256 + ((int)blockIdx.x & 255)) * 16 + (K)] = __builtin_amdgcn_s_memtime(); } while (0)
-
-__device__ __forceinline__ uint4 dl_frag(const unsigned char* img, int stride, int m, int hi, int ks) {
-  return *reinterpret_cast<const uint4*>(img + m * stride + (2 * ks + hi) * 16);
-}
+// tuning hook (otr_debug_trace): OTR_STAMP with kernel id OTR_KID_DECLAYER + launch (0 .. 5), unit = workgroup & 255
 
 // acc[i] += W[tile t0 + i tstep][contraction steps ks0 .. ks0 + NK) . (the 32 rows of `img`)^T; fragment (tile, ks) of the pack sits at
 // ((tile nks + ks) 64 + lane) uint4.  fill() starts the stream (the first PD fragments travel under whatever the caller does
@@ -66,7 +58,7 @@ template <int TPW, int NK, int PD> struct DlStream {
     uint4 xb;
 #pragma clang loop unroll(full)
     for (int s = 0; s < STEPS; ++s) {
-      if (s % TPW == 0) xb = dl_frag(img, stride, m, hi, xk0 + s / TPW);
+      if (s % TPW == 0) xb = frag_rm(img, stride, m, hi, xk0 + s / TPW);
       const uint4 w = ring[s % PD];
       mma32(acc[s % TPW], w, xb);
       if (s + PD < STEPS) ring[s % PD] = ld_global_b128(fptr(s + PD));
@@ -74,21 +66,6 @@ template <int TPW, int NK, int PD> struct DlStream {
     }
   }
 };
-
-template <int N> __device__ __forceinline__ void dl_zero(f32x16 (&acc)[N]) {
-#pragma unroll
-  for (int i = 0; i < N; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-}
-
-// accumulator tile (columns col0 + 8q + 4hi + (r&3) of row m) -> red[m][..] (row stride DL_RS floats)
-__device__ __forceinline__ void dl_put_tile(float* red, const f32x16& a, int col0, int lane) {
-  const int m = lane & 31, hi = lane >> 5;
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-    *reinterpret_cast<float4*>(red + m * DL_RS + col0 + 8 * q + 4 * hi) = make_float4(a[4 * q], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3]);
-}
 
 // red[32][256] -> slab rows, rounded to 16 bits (whole 512-byte rows per wave instruction).  Every slab of this file is 16-bit: a
 // launch's prologue is bound by what its CU can ingest (~22 B/clk: the slabs + residual rows of 32 rows were 160 KiB of a 256 KiB
@@ -154,7 +131,7 @@ __global__ __launch_bounds__(256, 1) void dec_self_fwd_kernel(DlSelfArgs p) {
   int u0, nrows;
   int64_t row0;
   dl_group(p.g, gi, u0, row0, nrows);
-  DL_STAMP(0, 0);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 0, (int)blockIdx.x & 255, 0, true);
   DlPro<4, 8> pro;                                                     // its loads go out first: vmcnt retires in order
   pro.issue(p.ln, row0, nrows, tid);
   DlStream<2, 16, 32> sq;                                             // all 32 fragments of a wave in flight: one round trip
@@ -167,19 +144,19 @@ __global__ __launch_bounds__(256, 1) void dec_self_fwd_kernel(DlSelfArgs p) {
       for (int q = 0; q < 4; ++q) bq4[t][q] = *reinterpret_cast<const float4*>(p.bqkv + wid * DL_D + DL_DK * h + 32 * t + 8 * q + 4 * (lane >> 5));
   }
 #ifdef DL_PROBE      // tuning build only (make DEFS=-DDL_PROBE): where the prologue's cycles go -- loads issued / everything landed / LayerNorm done
-  DL_STAMP(0, 8);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 0, (int)blockIdx.x & 255, 8, true);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  DL_STAMP(0, 9);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 0, (int)blockIdx.x & 255, 9, true);
 #endif
   pro.finish(p.ln, nrows, h == 0, [&](int r, int ch, const uint4& v) { *reinterpret_cast<uint4*>(ys + r * DL_YS + ch * 16) = v; }, tid);
 #ifdef DL_PROBE
-  DL_STAMP(0, 10);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 0, (int)blockIdx.x & 255, 10, true);
 #endif
   __syncthreads();
-  DL_STAMP(0, 1);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 0, (int)blockIdx.x & 255, 1, true);
   if (wid < 3) {
     f32x16 acc[2];
-    dl_zero(acc);
+    tile_zero(acc);
     sq.run(acc, ys, DL_YS, 0, lane);
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -202,13 +179,13 @@ __global__ __launch_bounds__(256, 1) void dec_self_fwd_kernel(DlSelfArgs p) {
   DlStream<2, 4, 8> so;
   so.fill(p.wo, 16, 2 * wid, 1, 4 * h, lane);                         // this head's 4 contraction steps of the output projection
   __syncthreads();
-  DL_STAMP(0, 2);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 0, (int)blockIdx.x & 255, 2, true);
   if (wid == 0) {
     // S^T = K Q^T for the 32 rows of the group: rows = keys j, columns = queries i; lane (i, hi) holds j = 8q + 4hi + (r & 3)
     f32x16 st[1];
-    dl_zero(st);
+    tile_zero(st);
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) mma32(st[0], dl_frag(ks_, DL_HS, m, hi, ks), dl_frag(qs, DL_HS, m, hi, ks));
+    for (int ks = 0; ks < 4; ++ks) mma32(st[0], frag_rm(ks_, DL_HS, m, hi, ks), frag_rm(qs, DL_HS, m, hi, ks));
     const int i = m, ui = i / p.g.L;
     float s[16], mx = -INFINITY;
 #pragma unroll
@@ -233,7 +210,7 @@ __global__ __launch_bounds__(256, 1) void dec_self_fwd_kernel(DlSelfArgs p) {
                           pack2h(s[8 * k2 + 4] * inv, s[8 * k2 + 5] * inv), pack2h(s[8 * k2 + 6] * inv, s[8 * k2 + 7] * inv));
     // O^T = V^T P^T: contraction slot (hi, e) of step k2 is key 16 k2 + 4 hi + e (e < 4) / 16 k2 + 8 + 4 hi + e - 4
     f32x16 ot[2];
-    dl_zero(ot);
+    tile_zero(ot);
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
@@ -253,16 +230,16 @@ __global__ __launch_bounds__(256, 1) void dec_self_fwd_kernel(DlSelfArgs p) {
       }
   }
   __syncthreads();
-  DL_STAMP(0, 3);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 0, (int)blockIdx.x & 255, 3, true);
   f32x16 acc[2];
-  dl_zero(acc);
+  tile_zero(acc);
   so.run(acc, cs, DL_HS, 0, lane);
-  dl_put_tile(red, acc[0], (2 * wid) * 32, lane);
-  dl_put_tile(red, acc[1], (2 * wid + 1) * 32, lane);
+  put_tile<DL_RS>(red, acc[0], (2 * wid) * 32, lane);
+  put_tile<DL_RS>(red, acc[1], (2 * wid + 1) * 32, lane);
   __syncthreads();
-  DL_STAMP(0, 4);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 0, (int)blockIdx.x & 255, 4, true);
   dl_store_slab<4>(p.slabs + (int64_t)h * p.ln.R * DL_D, red, row0, nrows, tid);
-  DL_STAMP(0, 5);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 0, (int)blockIdx.x & 255, 5, true);
 }
 
 // ------------------------------------------------------------------------------------------------ self-attention launch, cached decoding
@@ -391,7 +368,7 @@ __device__ __forceinline__ void dec_self_step_body(const DlStepArgs& p, const in
   __syncthreads();
   if (wid < 6) {
     f32x16 acc[1];
-    dl_zero(acc);
+    tile_zero(acc);
     sq.run(acc, ys, DL_YS, 0, lane);
     unsigned char* img = part == 0 ? qs : part == 1 ? ks_ : vs;
     uint16_t* cache = part == 1 ? p.kc : p.vc;
@@ -479,9 +456,9 @@ __device__ __forceinline__ void dec_self_step_body(const DlStepArgs& p, const in
   }
   __syncthreads();
   f32x16 acc[1];
-  dl_zero(acc);
+  tile_zero(acc);
   so.run(acc, cs, DL_HS, 0, lane);
-  dl_put_tile(red, acc[0], wid * 32, lane);
+  put_tile<DL_RS>(red, acc[0], wid * 32, lane);
   __syncthreads();
   dl_store_slab<8>(p.slabs + (int64_t)h * p.ln.R * DL_D, red, row0, nrows, tid);
 }
@@ -549,7 +526,7 @@ __global__ __launch_bounds__(512, 1) void dec_cross_fwd_kernel(DlCrossArgs p) {
   int64_t row0;
   dl_group(p.g, gi, u0, row0, nrows);
   const int nutt = nrows / p.g.L, ntile = (p.Tk + 31) >> 5, nit = nutt * ntile;
-  DL_STAMP(1, 0);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 1, (int)blockIdx.x & 255, 0, true);
   DlPro<8, 4> pro;
   pro.issue(p.ln, row0, nrows, tid);
   // the first key / value tile of this wave travels under the prologue and the q projection (it does not depend on them)
@@ -571,10 +548,10 @@ __global__ __launch_bounds__(512, 1) void dec_cross_fwd_kernel(DlCrossArgs p) {
     alt = DlKvTile{};
   }
   __syncthreads();
-  DL_STAMP(1, 1);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 1, (int)blockIdx.x & 255, 1, true);
   if (wid < 2) {
     f32x16 acc[1];
-    dl_zero(acc);
+    tile_zero(acc);
     sq.run(acc, ys, DL_YS, 0, lane);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -586,17 +563,17 @@ __global__ __launch_bounds__(512, 1) void dec_cross_fwd_kernel(DlCrossArgs p) {
     }
   }
   __syncthreads();
-  DL_STAMP(1, 2);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 1, (int)blockIdx.x & 255, 2, true);
   // ---- flash attention: this wave takes (utterance, key tile) pairs wid, wid + 8, ...; the queries are the group's 32 rows, of which
   // only the rows of that utterance take part (the others see -inf scores and keep their state).  Two tile register sets take
   // turns (no copies: a copy of registers that a load still has to fill waits for the load, which serialised the loop)
   uint4 qf[4];
 #pragma unroll
-  for (int ks = 0; ks < 4; ++ks) qf[ks] = dl_frag(qs, DL_HS, m, hi, ks);
+  for (int ks = 0; ks < 4; ++ks) qf[ks] = frag_rm(qs, DL_HS, m, hi, ks);
   const int i = m, ui = i / p.g.L;
   float mrun = -INFINITY, lrun = 0.f;
   f32x16 o[2];
-  dl_zero(o);
+  tile_zero(o);
   unsigned char* vt = vtw + wid * (DL_DK * DL_VT);
   auto load_tile = [&](DlKvTile& t, int it) {
     const int itc = min(it, nit - 1);                                   // past the end: a valid tile, loaded and never used
@@ -614,7 +591,7 @@ __global__ __launch_bounds__(512, 1) void dec_cross_fwd_kernel(DlCrossArgs p) {
         *reinterpret_cast<uint16_t*>(vt + (c0 + e) * DL_VT + j * 2) = (uint16_t)((e & 1) ? (w[e >> 1] >> 16) : (w[e >> 1] & 0xffffu));
     }
     f32x16 st[1];
-    dl_zero(st);
+    tile_zero(st);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) mma32(st[0], t.k[ks], qf[ks]);
     float s[16], tmax = -INFINITY;
@@ -644,7 +621,7 @@ __global__ __launch_bounds__(512, 1) void dec_cross_fwd_kernel(DlCrossArgs p) {
     for (int k2 = 0; k2 < 2; ++k2)
       pb[k2] = make_uint4(pack2h(s[8 * k2], s[8 * k2 + 1]), pack2h(s[8 * k2 + 2], s[8 * k2 + 3]),
                           pack2h(s[8 * k2 + 4], s[8 * k2 + 5]), pack2h(s[8 * k2 + 6], s[8 * k2 + 7]));
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                // this wave's own LDS writes of the value tile (in order, same wave)
+    wait_lds();                // this wave's own LDS writes of the value tile (in order, same wave)
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
@@ -653,7 +630,7 @@ __global__ __launch_bounds__(512, 1) void dec_cross_fwd_kernel(DlCrossArgs p) {
         const uint2 lo = *reinterpret_cast<const uint2*>(vr), up = *reinterpret_cast<const uint2*>(vr + 16);
         mma32(o[ct], make_uint4(lo.x, lo.y, up.x, up.y), pb[k2]);
       }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                // the tile is read before the next round overwrites it
+    wait_lds();                // the tile is read before the next round overwrites it
   };
   for (int it = wid; it < nit; it += 16) {
     consume(cur, it);
@@ -663,7 +640,7 @@ __global__ __launch_bounds__(512, 1) void dec_cross_fwd_kernel(DlCrossArgs p) {
       load_tile(alt, it + 24);
     }
   }
-  DL_STAMP(1, 3);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 1, (int)blockIdx.x & 255, 3, true);
   // ---- the eight waves' partial results meet in LDS
   if (hi == 0) { mb[wid * DL_RB + i] = mrun; lb[wid * DL_RB + i] = lrun; }
 #pragma unroll
@@ -673,7 +650,7 @@ __global__ __launch_bounds__(512, 1) void dec_cross_fwd_kernel(DlCrossArgs p) {
       *reinterpret_cast<float4*>(ob + (wid * DL_RB + i) * OS + 32 * ct + 8 * q + 4 * hi) =
           make_float4(o[ct][4 * q], o[ct][4 * q + 1], o[ct][4 * q + 2], o[ct][4 * q + 3]);
   __syncthreads();
-  DL_STAMP(1, 4);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 1, (int)blockIdx.x & 255, 4, true);
   {
     const int r = tid >> 4, c = (tid & 15) * 4;                        // 512 threads: row r, four columns of the head
     float M = -INFINITY;
@@ -700,14 +677,14 @@ __global__ __launch_bounds__(512, 1) void dec_cross_fwd_kernel(DlCrossArgs p) {
     }
   }
   __syncthreads();
-  DL_STAMP(1, 5);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 1, (int)blockIdx.x & 255, 5, true);
   f32x16 acc[1];
-  dl_zero(acc);
+  tile_zero(acc);
   so.run(acc, cs, DL_HS, 0, lane);
-  dl_put_tile(red, acc[0], wid * 32, lane);
+  put_tile<DL_RS>(red, acc[0], wid * 32, lane);
   __syncthreads();
   dl_store_slab<8>(p.slabs + (int64_t)h * p.ln.R * DL_D, red, row0, nrows, tid);
-  DL_STAMP(1, 6);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 1, (int)blockIdx.x & 255, 6, true);
 }
 
 // ------------------------------------------------------------------------------------------------ FFN launch
@@ -761,7 +738,7 @@ __device__ __forceinline__ void dec_ffn_fwd_body(const DlFfnArgs& p, const int b
     const int t = s - 2 * NKS;
     return P2 + (int64_t)((t >> 1) * (2 * nchunk) + 2 * c + (t & 1)) * 64;
   };
-  DL_STAMP(2, 0);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 2, (int)blockIdx.x & 255, 0, true);
   DlPro<4, 4> pro;
   pro.issue(p.ln, row0, nrows, tid);
   uint4 ring[PD];
@@ -771,9 +748,9 @@ __device__ __forceinline__ void dec_ffn_fwd_body(const DlFfnArgs& p, const int b
   __builtin_amdgcn_sched_barrier(0);
   pro.finish(p.ln, nrows, sl == 0, [&](int r, int ch, const uint4& v) { *reinterpret_cast<uint4*>(ys + r * DL_YS + ch * 16) = v; }, tid);
   __syncthreads();
-  DL_STAMP(2, 1);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 2, (int)blockIdx.x & 255, 1, true);
   f32x16 yacc[NT];
-  dl_zero(yacc);
+  tile_zero(yacc);
   for (int it = 0; it < nit; ++it) {
     const int cn = chunk_of(min(it + 1, nit - 1));
     float4 bv[4], bg[4];
@@ -783,14 +760,14 @@ __device__ __forceinline__ void dec_ffn_fwd_body(const DlFfnArgs& p, const int b
       bg[q] = *reinterpret_cast<const float4*>(p.b1 + p.F + c * 32 + 8 * q + 4 * hi);
     }
     f32x16 av, ag;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { av[r] = 0.f; ag[r] = 0.f; }
+    tile_zero(av);
+    tile_zero(ag);
     uint4 xb, uf0, uf1;
 #pragma clang loop unroll(full)
     for (int s = 0; s < STEPS; ++s) {
       const uint4 w = ring[s % PD];
       if (s < 2 * NKS) {
-        if ((s & 1) == 0) xb = dl_frag(ys, DL_YS, m, hi, s >> 1);
+        if ((s & 1) == 0) xb = frag_rm(ys, DL_YS, m, hi, s >> 1);
         if (s & 1) mma32(ag, w, xb); else mma32(av, w, xb);
       } else {
         const int t = s - 2 * NKS;
@@ -817,11 +794,11 @@ __device__ __forceinline__ void dec_ffn_fwd_body(const DlFfnArgs& p, const int b
     }
     c = cn;
   }
-  DL_STAMP(2, 2);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 2, (int)blockIdx.x & 255, 2, true);
 #pragma unroll
-  for (int nt = 0; nt < NT; ++nt) dl_put_tile(red + wid * DL_RB * DL_RS, yacc[nt], nt * 32, lane);
+  for (int nt = 0; nt < NT; ++nt) put_tile<DL_RS>(red + wid * DL_RB * DL_RS, yacc[nt], nt * 32, lane);
   __syncthreads();
-  DL_STAMP(2, 3);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 2, (int)blockIdx.x & 255, 3, true);
   dl_store_slab16(p.slabs + (int64_t)sl * p.ln.R * D, red, row0, nrows, wid, lane);
 }
 
@@ -1098,7 +1075,7 @@ __global__ __launch_bounds__(256, 1) void dec_ffn_bwd_kernel(DlFfnBwdArgs p) {
     const int ksf = (j4 < 2) ? 2 * c + j4 : 2 * nchunk + 2 * c + (j4 - 2);
     return P4 + (int64_t)((t >> 2) * (4 * nchunk) + ksf) * 64;
   };
-  DL_STAMP(3, 0);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 3, (int)blockIdx.x & 255, 0, true);
   DlProB<4, 4> pro;
   pro.issue(p.ln, row0, nrows, tid);
   uint4 ring[PD];
@@ -1108,9 +1085,9 @@ __global__ __launch_bounds__(256, 1) void dec_ffn_bwd_kernel(DlFfnBwdArgs p) {
   __builtin_amdgcn_sched_barrier(0);
   pro.finish(p.ln, nrows, rb, sl == 0, ds, stage, tid);
   __syncthreads();
-  DL_STAMP(3, 1);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 3, (int)blockIdx.x & 255, 1, true);
   f32x16 xacc[NT];
-  dl_zero(xacc);
+  tile_zero(xacc);
   const bool live = m < nrows;
   const int64_t crow = row0 + min(m, nrows - 1);
   for (int it = 0; it < nit; ++it) {
@@ -1118,14 +1095,13 @@ __global__ __launch_bounds__(256, 1) void dec_ffn_bwd_kernel(DlFfnBwdArgs p) {
     const uint4* hs = p.hsave + (((int64_t)rb * nchunk + c) * 4) * 64 + lane;
     const uint4 a0 = ld_global_b128(hs), a1 = ld_global_b128(hs + 64), g0 = ld_global_b128(hs + 128), g1 = ld_global_b128(hs + 192);
     f32x16 du;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) du[r] = 0.f;
+    tile_zero(du);
     uint4 ob, hf[4];
 #pragma clang loop unroll(full)
     for (int s = 0; s < STEPS; ++s) {
       const uint4 w = ring[s % PD];
       if (s < S2) {
-        ob = dl_frag(ds, DL_YS, m, hi, s);
+        ob = frag_rm(ds, DL_YS, m, hi, s);
         mma32(du, w, ob);
       } else {
         const int t = s - S2;
@@ -1158,11 +1134,11 @@ __global__ __launch_bounds__(256, 1) void dec_ffn_bwd_kernel(DlFfnBwdArgs p) {
     }
     c = cn;
   }
-  DL_STAMP(3, 2);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 3, (int)blockIdx.x & 255, 2, true);
   __syncthreads();                                          // every wave is done with the operand image
-  DL_STAMP(3, 3);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 3, (int)blockIdx.x & 255, 3, true);
 #pragma unroll
-  for (int nt = 0; nt < NT; ++nt) dl_put_tile(red + wid * DL_RB * DL_RS, xacc[nt], nt * 32, lane);
+  for (int nt = 0; nt < NT; ++nt) put_tile<DL_RS>(red + wid * DL_RB * DL_RS, xacc[nt], nt * 32, lane);
   __syncthreads();
   dl_store_slab16(p.slabs + (int64_t)sl * p.ln.R * D, red, row0, nrows, wid, lane);
 }
@@ -1175,7 +1151,7 @@ __device__ __forceinline__ void dl_dctx(DlStream<1, 16, 16>& sdo, const unsigned
                                         float* dpart, const uint16_t* ctx16, int64_t row0, int nrows, int h, int wid, int lane) {
   const int m = lane & 31, hi = lane >> 5;
   f32x16 acc[1];
-  dl_zero(acc);
+  tile_zero(acc);
   sdo.run(acc, img, DL_YS, 0, lane);
   float dsum = 0.f;
 #pragma unroll
@@ -1196,15 +1172,6 @@ __device__ __forceinline__ void dl_dctx(DlStream<1, 16, 16>& sdo, const unsigned
 }
 
 // two 8-byte pieces of row `rowp` of a transposed image: contraction slots of step k2 in accumulator order
-__device__ __forceinline__ uint4 dl_tfrag(const unsigned char* timg, int row, int hi, int k2) {
-  const unsigned char* vr = timg + row * DL_VT + (16 * k2 + 4 * hi) * 2;
-  const uint2 lo = *reinterpret_cast<const uint2*>(vr), up = *reinterpret_cast<const uint2*>(vr + 16);
-  return make_uint4(lo.x, lo.y, up.x, up.y);
-}
-__device__ __forceinline__ uint4 dl_pack8(const float* v) {
-  return make_uint4(pack2h(v[0], v[1]), pack2h(v[2], v[3]), pack2h(v[4], v[5]), pack2h(v[6], v[7]));
-}
-
 // ------------------------------------------------------------------------------------------------ cross-attention backward launch
 struct DlCrossBwdArgs {
   unsigned long long* trace;
@@ -1266,7 +1233,7 @@ __global__ __launch_bounds__(512, 1) void dec_cross_bwd_kernel(DlCrossBwdArgs p)
   int64_t row0;
   dl_group(p.g, gi, u0, row0, nrows);
   const int nutt = nrows / p.g.L, ntile = (p.Tk + 31) >> 5, nit = nutt * ntile;
-  DL_STAMP(4, 0);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 4, (int)blockIdx.x & 255, 0, true);
   DlProB<8, 8> pro;
   pro.issue(p.ln, row0, nrows, tid);
   auto load_tile = [&](DlKvRows& t, int it) {
@@ -1280,7 +1247,7 @@ __global__ __launch_bounds__(512, 1) void dec_cross_bwd_kernel(DlCrossBwdArgs p)
   load_tile(cur, slot);                                                 // under the d-context GEMM
   load_tile(alt, slot + 4);
   __syncthreads();
-  DL_STAMP(4, 1);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 4, (int)blockIdx.x & 255, 1, true);
   if (wid < 2) {
     dl_dctx(sdo, ys, dos, dot, dpart, p.ctx16, row0, nrows, h, wid, lane);
   } else if (wid == 2) {
@@ -1305,7 +1272,7 @@ __global__ __launch_bounds__(512, 1) void dec_cross_bwd_kernel(DlCrossBwdArgs p)
     }
   }
   __syncthreads();
-  DL_STAMP(4, 2);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 4, (int)blockIdx.x & 255, 2, true);
   if (tid < DL_RB) dels[tid] = dpart[tid] + dpart[DL_RB + tid];
   __syncthreads();
   // (the Q / dO operand fragments are re-read from LDS for every tile: held in registers across the loops they pushed the wave
@@ -1314,7 +1281,7 @@ __global__ __launch_bounds__(512, 1) void dec_cross_bwd_kernel(DlCrossBwdArgs p)
   if (orient == 0) {
     // ---- lane = query i, registers = keys j -> dq
     f32x16 dq[2];
-    dl_zero(dq);
+    tile_zero(dq);
     const float my_lse = lses[m], my_del = dels[m];
     const int my_u = m / p.g.L;
     unsigned char* kt = ktw + slot * SM_T;
@@ -1329,9 +1296,9 @@ __global__ __launch_bounds__(512, 1) void dec_cross_bwd_kernel(DlCrossBwdArgs p)
           *reinterpret_cast<uint16_t*>(kt + (16 * ks + 8 * hi + e) * DL_VT + m * 2) = (uint16_t)((e & 1) ? (w[e >> 1] >> 16) : (w[e >> 1] & 0xffffu));
       }
       f32x16 st[1], dp[1];
-      dl_zero(st); dl_zero(dp);
+      tile_zero(st); tile_zero(dp);
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) { mma32(st[0], t.k[ks], dl_frag(qs, DL_HS, m, hi, ks)); mma32(dp[0], t.v[ks], dl_frag(dos, DL_HS, m, hi, ks)); }
+      for (int ks = 0; ks < 4; ++ks) { mma32(st[0], t.k[ks], frag_rm(qs, DL_HS, m, hi, ks)); mma32(dp[0], t.v[ks], frag_rm(dos, DL_HS, m, hi, ks)); }
       const bool mine = my_u == u && m < nrows;
       float dsv[16];
 #pragma unroll
@@ -1341,14 +1308,14 @@ __global__ __launch_bounds__(512, 1) void dec_cross_bwd_kernel(DlCrossBwdArgs p)
         const float pr = ok ? __expf(st[0][r] * p.scale - my_lse) : 0.f;
         dsv[r] = pr * (dp[0][r] - my_del);
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      wait_lds();
 #pragma unroll
       for (int k2 = 0; k2 < 2; ++k2) {
-        const uint4 pb = dl_pack8(dsv + 8 * k2);
+        const uint4 pb = frag_pack8(dsv + 8 * k2);
 #pragma unroll
-        for (int ct = 0; ct < 2; ++ct) mma32(dq[ct], dl_tfrag(kt, 32 * ct + m, hi, k2), pb);
+        for (int ct = 0; ct < 2; ++ct) mma32(dq[ct], frag_tr(kt, DL_VT, 32 * ct + m, 0, hi, k2), pb);
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      wait_lds();
     };
     for (int it = slot; it < nit; it += 8) {
       consume(cur, it);
@@ -1370,9 +1337,9 @@ __global__ __launch_bounds__(512, 1) void dec_cross_bwd_kernel(DlCrossBwdArgs p)
     auto consume = [&](const DlKvRows& t, int it) {
       const int u = it / ntile, b = u0 + u, j0 = (it % ntile) * 32, ulo = u * p.g.L;      // the utterance's rows: ulo .. ulo + L - 1
       f32x16 st[1], dp[1];
-      dl_zero(st); dl_zero(dp);
+      tile_zero(st); tile_zero(dp);
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) { mma32(st[0], dl_frag(qs, DL_HS, m, hi, ks), t.k[ks]); mma32(dp[0], dl_frag(dos, DL_HS, m, hi, ks), t.v[ks]); }
+      for (int ks = 0; ks < 4; ++ks) { mma32(st[0], frag_rm(qs, DL_HS, m, hi, ks), t.k[ks]); mma32(dp[0], frag_rm(dos, DL_HS, m, hi, ks), t.v[ks]); }
       const bool keyok = (t.valid >> m) & 1u;
       float pv[16], dsv[16];
 #pragma unroll
@@ -1386,11 +1353,11 @@ __global__ __launch_bounds__(512, 1) void dec_cross_bwd_kernel(DlCrossBwdArgs p)
       // lines per store instruction); staged, an instruction writes 8 whole 128-byte rows.  dv first, then dk: one pair of
       // accumulator tiles live at a time (the wave has 256 registers)
       {
-        const uint4 pb0 = dl_pack8(pv), pb1 = dl_pack8(pv + 8);
+        const uint4 pb0 = frag_pack8(pv), pb1 = frag_pack8(pv + 8);
         f32x16 dv[2];
-        dl_zero(dv);
+        tile_zero(dv);
 #pragma unroll
-        for (int ct = 0; ct < 2; ++ct) { mma32(dv[ct], dl_tfrag(dot, 32 * ct + m, hi, 0), pb0); mma32(dv[ct], dl_tfrag(dot, 32 * ct + m, hi, 1), pb1); }
+        for (int ct = 0; ct < 2; ++ct) { mma32(dv[ct], frag_tr(dot, DL_VT, 32 * ct + m, 0, hi, 0), pb0); mma32(dv[ct], frag_tr(dot, DL_VT, 32 * ct + m, 0, hi, 1), pb1); }
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
@@ -1400,11 +1367,11 @@ __global__ __launch_bounds__(512, 1) void dec_cross_bwd_kernel(DlCrossBwdArgs p)
       }
       __builtin_amdgcn_sched_barrier(0);
       {
-        const uint4 sb0 = dl_pack8(dsv), sb1 = dl_pack8(dsv + 8);
+        const uint4 sb0 = frag_pack8(dsv), sb1 = frag_pack8(dsv + 8);
         f32x16 dk[2];
-        dl_zero(dk);
+        tile_zero(dk);
 #pragma unroll
-        for (int ct = 0; ct < 2; ++ct) { mma32(dk[ct], dl_tfrag(qt, 32 * ct + m, hi, 0), sb0); mma32(dk[ct], dl_tfrag(qt, 32 * ct + m, hi, 1), sb1); }
+        for (int ct = 0; ct < 2; ++ct) { mma32(dk[ct], frag_tr(qt, DL_VT, 32 * ct + m, 0, hi, 0), sb0); mma32(dk[ct], frag_tr(qt, DL_VT, 32 * ct + m, 0, hi, 1), sb1); }
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
@@ -1412,7 +1379,7 @@ __global__ __launch_bounds__(512, 1) void dec_cross_bwd_kernel(DlCrossBwdArgs p)
             *reinterpret_cast<uint2*>(og + m * DL_HS + (32 * ct + 8 * q + 4 * hi) * 2) =
                 make_uint2(pack2h(dk[ct][4 * q], dk[ct][4 * q + 1]), pack2h(dk[ct][4 * q + 2], dk[ct][4 * q + 3]));
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      wait_lds();
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int j = 8 * q + (lane >> 3), ch = lane & 7;
@@ -1422,7 +1389,7 @@ __global__ __launch_bounds__(512, 1) void dec_cross_bwd_kernel(DlCrossBwdArgs p)
           st_global_b128(orow + p.voff, *reinterpret_cast<const uint4*>(og + SM_H + j * DL_HS + ch * 16));
         }
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      wait_lds();
     };
     for (int it = slot; it < nit; it += 8) {
       consume(cur, it);
@@ -1433,7 +1400,7 @@ __global__ __launch_bounds__(512, 1) void dec_cross_bwd_kernel(DlCrossBwdArgs p)
       }
     }
   }
-  DL_STAMP(4, 3);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 4, (int)blockIdx.x & 255, 3, true);
   // ---- the four orientation-0 waves' dq partials: sum -> 16-bit image + memory
   DlStream<1, 4, 4> sdy;                                                // (filled here: inside the loops its 16 registers spilled)
   sdy.fill(p.wq_t, 16, wid, 1, 4 * h, lane);
@@ -1451,14 +1418,14 @@ __global__ __launch_bounds__(512, 1) void dec_cross_bwd_kernel(DlCrossBwdArgs p)
     if (r < nrows) *reinterpret_cast<uint2*>(p.dq16 + (row0 + r) * DL_D + DL_DK * h + c) = pk;
   }
   __syncthreads();
-  DL_STAMP(4, 4);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 4, (int)blockIdx.x & 255, 4, true);
   f32x16 acc[1];
-  dl_zero(acc);
+  tile_zero(acc);
   sdy.run(acc, dqs, DL_HS, 0, lane);
-  dl_put_tile(red, acc[0], wid * 32, lane);
+  put_tile<DL_RS>(red, acc[0], wid * 32, lane);
   __syncthreads();
   dl_store_slab<8>(p.slabs + (int64_t)h * p.ln.R * DL_D, red, row0, nrows, tid);
-  DL_STAMP(4, 5);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 4, (int)blockIdx.x & 255, 5, true);
 }
 
 // ------------------------------------------------------------------------------------------------ self-attention backward launch
@@ -1498,7 +1465,7 @@ __global__ __launch_bounds__(256, 1) void dec_self_bwd_kernel(DlSelfBwdArgs p) {
   int u0, nrows;
   int64_t row0;
   dl_group(p.g, gi, u0, row0, nrows);
-  DL_STAMP(5, 0);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 5, (int)blockIdx.x & 255, 0, true);
   DlProB<4, 4> pro;
   pro.issue(p.ln, row0, nrows, tid);
   DlStream<1, 16, 16> sdo;
@@ -1534,21 +1501,21 @@ __global__ __launch_bounds__(256, 1) void dec_self_bwd_kernel(DlSelfBwdArgs p) {
     }
   }
   __syncthreads();
-  DL_STAMP(5, 1);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 5, (int)blockIdx.x & 255, 1, true);
   if (wid < 2) dl_dctx(sdo, ys, dos, dot, dpart, p.ctx16, row0, nrows, h, wid, lane);
   __syncthreads();
-  DL_STAMP(5, 2);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 5, (int)blockIdx.x & 255, 2, true);
   if (tid < DL_RB) dels[tid] = dpart[tid] + dpart[DL_RB + tid];
   __syncthreads();
   if (wid == 0) {
     // orientation 1: lane = query i, registers = keys j -> dq
     f32x16 st[1], dp[1];
-    dl_zero(st); dl_zero(dp);
+    tile_zero(st); tile_zero(dp);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      const uint4 qb = dl_frag(qs, DL_HS, m, hi, ks), ob_ = dl_frag(dos, DL_HS, m, hi, ks);
-      mma32(st[0], dl_frag(ks_, DL_HS, m, hi, ks), qb);
-      mma32(dp[0], dl_frag(vs, DL_HS, m, hi, ks), ob_);
+      const uint4 qb = frag_rm(qs, DL_HS, m, hi, ks), ob_ = frag_rm(dos, DL_HS, m, hi, ks);
+      mma32(st[0], frag_rm(ks_, DL_HS, m, hi, ks), qb);
+      mma32(dp[0], frag_rm(vs, DL_HS, m, hi, ks), ob_);
     }
     const int i = m, ui = i / p.g.L;
     const float my_lse = lses[i], my_del = dels[i];
@@ -1561,12 +1528,12 @@ __global__ __launch_bounds__(256, 1) void dec_self_bwd_kernel(DlSelfBwdArgs p) {
       dsv[r] = pr * (dp[0][r] - my_del) * p.scale;
     }
     f32x16 dq[2];
-    dl_zero(dq);
+    tile_zero(dq);
 #pragma unroll
     for (int k2 = 0; k2 < 2; ++k2) {
-      const uint4 pb = dl_pack8(dsv + 8 * k2);
+      const uint4 pb = frag_pack8(dsv + 8 * k2);
 #pragma unroll
-      for (int ct = 0; ct < 2; ++ct) mma32(dq[ct], dl_tfrag(kt, 32 * ct + m, hi, k2), pb);
+      for (int ct = 0; ct < 2; ++ct) mma32(dq[ct], frag_tr(kt, DL_VT, 32 * ct + m, 0, hi, k2), pb);
     }
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct)
@@ -1580,12 +1547,12 @@ __global__ __launch_bounds__(256, 1) void dec_self_bwd_kernel(DlSelfBwdArgs p) {
   } else if (wid == 1) {
     // orientation 2: lane = key j, registers = queries i -> dk, dv
     f32x16 st[1], dp[1];
-    dl_zero(st); dl_zero(dp);
+    tile_zero(st); tile_zero(dp);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      const uint4 kb = dl_frag(ks_, DL_HS, m, hi, ks), vb = dl_frag(vs, DL_HS, m, hi, ks);
-      mma32(st[0], dl_frag(qs, DL_HS, m, hi, ks), kb);
-      mma32(dp[0], dl_frag(dos, DL_HS, m, hi, ks), vb);
+      const uint4 kb = frag_rm(ks_, DL_HS, m, hi, ks), vb = frag_rm(vs, DL_HS, m, hi, ks);
+      mma32(st[0], frag_rm(qs, DL_HS, m, hi, ks), kb);
+      mma32(dp[0], frag_rm(dos, DL_HS, m, hi, ks), vb);
     }
     const int j = m, uj = j / p.g.L;
     float pv[16], dsv[16];
@@ -1597,14 +1564,14 @@ __global__ __launch_bounds__(256, 1) void dec_self_bwd_kernel(DlSelfBwdArgs p) {
       dsv[r] = pv[r] * (dp[0][r] - dels[i]) * p.scale;
     }
     f32x16 dv[2], dk[2];
-    dl_zero(dv); dl_zero(dk);
+    tile_zero(dv); tile_zero(dk);
 #pragma unroll
     for (int k2 = 0; k2 < 2; ++k2) {
-      const uint4 pb = dl_pack8(pv + 8 * k2), sb = dl_pack8(dsv + 8 * k2);
+      const uint4 pb = frag_pack8(pv + 8 * k2), sb = frag_pack8(dsv + 8 * k2);
 #pragma unroll
       for (int ct = 0; ct < 2; ++ct) {
-        mma32(dv[ct], dl_tfrag(dot, 32 * ct + m, hi, k2), pb);
-        mma32(dk[ct], dl_tfrag(qt, 32 * ct + m, hi, k2), sb);
+        mma32(dv[ct], frag_tr(dot, DL_VT, 32 * ct + m, 0, hi, k2), pb);
+        mma32(dk[ct], frag_tr(qt, DL_VT, 32 * ct + m, 0, hi, k2), sb);
       }
     }
 #pragma unroll
@@ -1623,16 +1590,16 @@ __global__ __launch_bounds__(256, 1) void dec_self_bwd_kernel(DlSelfBwdArgs p) {
       }
   }
   __syncthreads();
-  DL_STAMP(5, 3);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 5, (int)blockIdx.x & 255, 3, true);
   f32x16 acc[2];
-  dl_zero(acc);
+  tile_zero(acc);
 #pragma unroll
   for (int j = 0; j < 3; ++j) sg[j].run(acc, gs, GS, 4 * j, lane);
-  dl_put_tile(red, acc[0], (2 * wid) * 32, lane);
-  dl_put_tile(red, acc[1], (2 * wid + 1) * 32, lane);
+  put_tile<DL_RS>(red, acc[0], (2 * wid) * 32, lane);
+  put_tile<DL_RS>(red, acc[1], (2 * wid + 1) * 32, lane);
   __syncthreads();
   dl_store_slab<4>(p.slabs + (int64_t)h * p.ln.R * DL_D, red, row0, nrows, tid);
-  DL_STAMP(5, 4);
+  OTR_STAMP(p.trace, OTR_KID_DECLAYER + 5, (int)blockIdx.x & 255, 4, true);
 }
 
 // dx = skip + sum of slabs
@@ -1699,7 +1666,6 @@ int32_t dl_check_geom(const char* who, int32_t B, int32_t L, DlGeom& g) {
 }
 
 }  // namespace
-extern unsigned long long* g_otr_trace;   // api.hip (otr_debug_trace)
 
 extern "C" int32_t otr_dec_group_size(int32_t B, int32_t L) {
   if (B <= 0 || L <= 0 || L > DL_RB) return 0;

@@ -14,7 +14,6 @@
 #include "common.h"
 
 #define NEG_INF (-__builtin_huge_valf())
-extern int g_otr_decode_attn64;    // api.hip (otr_debug_set(24, v)): the vector-load form of the cached self-attention step
 
 __global__ void decode_embed_kernel(const int64_t* preds, int64_t ldp, const int32_t* pos, const float* E, float* y,
                                     bf16_t* y_lp, int d, int vocab, float scale) {

@@ -15,10 +15,10 @@
 //     contracted over the streamed index), then every wave walks the 32-row tiles on its own: no barrier, no global load in the loop;
 //   * 32 x 32 x 16 MFMAs: half the operand bytes per flop of the 16-row tiles; the owned side's fragments stay in registers;
 //   * P and dS go from the accumulators straight back into MFMA operands (the accumulator layout is an operand layout once the
-//     contraction slots are taken in accumulator order -- the transposed images are read in that order, dl_tfrag in declayer.hip);
+//     contraction slots are taken in accumulator order -- the transposed images are read in that order, frag_tr in tile32.h);
 //   * delta = rowsum(dO . O) is formed on the way in (no separate pass), outputs leave through LDS as whole 128-byte rows.
 // Work per (utterance, head): 7 products of T x T x 64 (S and dP are formed in both orientations) -- the same recompute as before.
-#include "common.h"
+#include "tile32.h"
 
 namespace {
 
@@ -31,9 +31,6 @@ constexpr int EA_RM = EA_T * EA_HS;       // 36864
 constexpr int EA_TR = EA_DK * EA_TS;      // 33280
 constexpr float EA_LOG2E = 1.4426950408889634f;
 
-// tuning hook (otr_debug_trace): thread 0 stamps the shader clock into trace[16384 + ((6 + orientation) * 256 + unit) * 16 + k]
-#define EA_STAMP(K) do { if (p.trace && threadIdx.x == 0 && g < 256) p.trace[16384 + ((6 + orient) * 256 + g) * 16 + (K)] = __builtin_amdgcn_s_memtime(); } while (0)
-
 struct EaArgs {
   unsigned long long* trace;
   const uint16_t *q, *k, *v, *o, *do_;
@@ -45,22 +42,6 @@ struct EaArgs {
   float scale;
 };
 
-__device__ __forceinline__ uint4 ea_frag(const unsigned char* img, int row, int hi, int ks) {
-  return *reinterpret_cast<const uint4*>(img + row * EA_HS + (2 * ks + hi) * 16);
-}
-// contraction slots of step k2 (16 streamed rows from `col0`) in accumulator order: rows col0 + 16 k2 + 4 hi + e, then + 8
-__device__ __forceinline__ uint4 ea_tfrag(const unsigned char* timg, int row, int col0, int hi, int k2) {
-  const unsigned char* vr = timg + row * EA_TS + (col0 + 16 * k2 + 4 * hi) * 2;
-  const uint2 lo = *reinterpret_cast<const uint2*>(vr), up = *reinterpret_cast<const uint2*>(vr + 16);
-  return make_uint4(lo.x, lo.y, up.x, up.y);
-}
-__device__ __forceinline__ uint4 ea_pack8(const float* v) {
-  return make_uint4(pack2h(v[0], v[1]), pack2h(v[2], v[3]), pack2h(v[4], v[5]), pack2h(v[6], v[7]));
-}
-__device__ __forceinline__ void ea_zero(f32x16& a) {
-#pragma unroll
-  for (int r = 0; r < 16; ++r) a[r] = 0.f;
-}
 
 // The streamed side is staged in CHUNKS of 64 rows (two tiles): the workgroup issues every global load of its set-up at once, chunk by
 // chunk (vmcnt retires in order), and starts on the tiles of chunk c while chunks c+1.. are still travelling -- the set-up is bound by
@@ -127,13 +108,13 @@ __device__ __forceinline__ void ea_put_rows(const f32x16 (&acc)[2], float scale,
 __device__ __forceinline__ void ea_store_rows(const f32x16 (&acc)[2], float scale, bool live, unsigned char* og, uint16_t* dst, int64_t ts, int row0,
                                               int T, int lane) {
   ea_put_rows(acc, scale, live, og, lane);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  wait_lds();
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int j = 8 * q + (lane >> 3), ch = lane & 7;
     if (row0 + j < T) st_global_b128(dst + (int64_t)(row0 + j) * ts + 8 * ch, *reinterpret_cast<const uint4*>(og + j * EA_HS + ch * 16));
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  wait_lds();
 }
 
 constexpr int EA_SMEM = 2 * EA_RM + 2 * EA_TR + 2 * EA_T * 4;
@@ -165,7 +146,7 @@ __global__ __launch_bounds__(512, 1) void encattn_bwd_kernel(EaArgs p) {
   const int own = o0 + 32 * wid + m;                             // this lane's own row (query or key)
   const int ownc = min(own, T - 1);
   const bool wave_live = o0 + 32 * wid < T;                      // this wave owns at least one real row
-  EA_STAMP(0);
+  OTR_STAMP(p.trace, OTR_KID_ENCATTN + orient, g, 0, g < 256);
 
   if (orient == 0) {
     // ------------------------------------------------------------------ lane = query: dQ = scale . dS K
@@ -185,7 +166,7 @@ __global__ __launch_bounds__(512, 1) void encattn_bwd_kernel(EaArgs p) {
       gv[c] = ea_issue(V, p.v_ts, T, tid, c);
     }
     __builtin_amdgcn_sched_barrier(0);
-    EA_STAMP(1);
+    OTR_STAMP(p.trace, OTR_KID_ENCATTN + orient, g, 1, g < 256);
     float del = 0.f;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
@@ -197,14 +178,14 @@ __global__ __launch_bounds__(512, 1) void encattn_bwd_kernel(EaArgs p) {
     // a query row with no live key at all (lse = -inf) has P = 0 everywhere; rows past T contribute nothing and are not stored
     const float nl = (own < T && l0 != -__builtin_huge_valf()) ? -l0 * EA_LOG2E : -__builtin_huge_valf();
     f32x16 dq[2];
-    ea_zero(dq[0]); ea_zero(dq[1]);
+    tile_zero(dq[0]); tile_zero(dq[1]);
     auto tile = [&](int jt) {
       const unsigned char* kr = krm + jt * 32 * EA_HS;
       const unsigned char* vr = vrm + jt * 32 * EA_HS;
       f32x16 st, dp;
-      ea_zero(st); ea_zero(dp);
+      tile_zero(st); tile_zero(dp);
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) { mma32(st, ea_frag(kr, m, hi, ks), qf[ks]); mma32(dp, ea_frag(vr, m, hi, ks), dof[ks]); }
+      for (int ks = 0; ks < 4; ++ks) { mma32(st, frag_rm(kr, EA_HS, m, hi, ks), qf[ks]); mma32(dp, frag_rm(vr, EA_HS, m, hi, ks), dof[ks]); }
       float dsv[16];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -219,9 +200,9 @@ __global__ __launch_bounds__(512, 1) void encattn_bwd_kernel(EaArgs p) {
       }
 #pragma unroll
       for (int k2 = 0; k2 < 2; ++k2) {
-        const uint4 pb = ea_pack8(dsv + 8 * k2);
+        const uint4 pb = frag_pack8(dsv + 8 * k2);
 #pragma unroll
-        for (int ct = 0; ct < 2; ++ct) mma32(dq[ct], ea_tfrag(kt, 32 * ct + m, jt * 32, hi, k2), pb);
+        for (int ct = 0; ct < 2; ++ct) mma32(dq[ct], frag_tr(kt, EA_TS, 32 * ct + m, jt * 32, hi, k2), pb);
       }
     };
     for (int s0 = 0; s0 < (MULTI ? T : 1); s0 += EA_T) {           // streamed super-chunks (one when T <= 256)
@@ -244,18 +225,18 @@ __global__ __launch_bounds__(512, 1) void encattn_bwd_kernel(EaArgs p) {
         __syncthreads();
         ea_transpose(kt, krm, c, tid & 255, 2 * (tid >> 8), 2);
         __syncthreads();
-        if (c == 0) EA_STAMP(2);
+        if (c == 0) OTR_STAMP(p.trace, OTR_KID_ENCATTN + orient, g, 2, g < 256);
         if (wave_live) {
           tile(2 * c);
           if (2 * c + 1 < nt) tile(2 * c + 1);
         }
       }
     }
-    EA_STAMP(3);
+    OTR_STAMP(p.trace, OTR_KID_ENCATTN + orient, g, 3, g < 256);
     __syncthreads();                                               // every wave is done with the images: they become staging space
-    EA_STAMP(4);
+    OTR_STAMP(p.trace, OTR_KID_ENCATTN + orient, g, 4, g < 256);
     if (wave_live) ea_store_rows(dq, p.scale, true, krm + 32 * wid * EA_HS, p.dq + (int64_t)b * p.q_bs + h * EA_DK, p.q_ts, o0 + 32 * wid, T, lane);
-    EA_STAMP(5);
+    OTR_STAMP(p.trace, OTR_KID_ENCATTN + orient, g, 5, g < 256);
   } else {
     // ------------------------------------------------------------------ lane = key: dV = P^T dO, dK = scale . dS^T Q
     unsigned char* qrm = smem;
@@ -276,19 +257,19 @@ __global__ __launch_bounds__(512, 1) void encattn_bwd_kernel(EaArgs p) {
       go[c] = ea_issue(O, p.o_ts, T, tid, c);
     }
     __builtin_amdgcn_sched_barrier(0);
-    EA_STAMP(1);
+    OTR_STAMP(p.trace, OTR_KID_ENCATTN + orient, g, 1, g < 256);
     // a masked key (or one past T) only pollutes ITS OWN dk / dv rows -- the lane is a column of every product here -- so the loop
     // carries no mask at all and the rows are zeroed on their way out
     const bool keyok = own < T && kmb;
     f32x16 dk[2], dv[2];
-    ea_zero(dk[0]); ea_zero(dk[1]); ea_zero(dv[0]); ea_zero(dv[1]);
+    tile_zero(dk[0]); tile_zero(dk[1]); tile_zero(dv[0]); tile_zero(dv[1]);
     auto tile = [&](int it) {
       const unsigned char* qr = qrm + it * 32 * EA_HS;
       const unsigned char* dr = dorm + it * 32 * EA_HS;
       f32x16 st, dp;
-      ea_zero(st); ea_zero(dp);
+      tile_zero(st); tile_zero(dp);
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) { mma32(st, ea_frag(qr, m, hi, ks), kf[ks]); mma32(dp, ea_frag(dr, m, hi, ks), vf[ks]); }
+      for (int ks = 0; ks < 4; ++ks) { mma32(st, frag_rm(qr, EA_HS, m, hi, ks), kf[ks]); mma32(dp, frag_rm(dr, EA_HS, m, hi, ks), vf[ks]); }
       float pv[16], dsv[16];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -304,11 +285,11 @@ __global__ __launch_bounds__(512, 1) void encattn_bwd_kernel(EaArgs p) {
       }
 #pragma unroll
       for (int k2 = 0; k2 < 2; ++k2) {
-        const uint4 pb = ea_pack8(pv + 8 * k2), sb = ea_pack8(dsv + 8 * k2);
+        const uint4 pb = frag_pack8(pv + 8 * k2), sb = frag_pack8(dsv + 8 * k2);
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct) {
-          mma32(dv[ct], ea_tfrag(dot, 32 * ct + m, it * 32, hi, k2), pb);
-          mma32(dk[ct], ea_tfrag(qt, 32 * ct + m, it * 32, hi, k2), sb);
+          mma32(dv[ct], frag_tr(dot, EA_TS, 32 * ct + m, it * 32, hi, k2), pb);
+          mma32(dk[ct], frag_tr(qt, EA_TS, 32 * ct + m, it * 32, hi, k2), sb);
         }
       }
     };
@@ -334,27 +315,25 @@ __global__ __launch_bounds__(512, 1) void encattn_bwd_kernel(EaArgs p) {
         if (tid < 256) ea_transpose(qt, qrm, c, tid, 0, 4);         // wave-uniform split: four waves per image
         else ea_transpose(dot, dorm, c, tid - 256, 0, 4);
         __syncthreads();
-        if (c == 0) EA_STAMP(2);
+        if (c == 0) OTR_STAMP(p.trace, OTR_KID_ENCATTN + orient, g, 2, g < 256);
         if (wave_live) {
           tile(2 * c);
           if (2 * c + 1 < nt) tile(2 * c + 1);
         }
       }
     }
-    EA_STAMP(3);
+    OTR_STAMP(p.trace, OTR_KID_ENCATTN + orient, g, 3, g < 256);
     __syncthreads();
-    EA_STAMP(4);
+    OTR_STAMP(p.trace, OTR_KID_ENCATTN + orient, g, 4, g < 256);
     if (wave_live) {
       ea_store_rows(dk, p.scale, keyok, qrm + 32 * wid * EA_HS, p.dk + (int64_t)b * p.k_bs + h * EA_DK, p.k_ts, o0 + 32 * wid, T, lane);
       ea_store_rows(dv, 1.f, keyok, dorm + 32 * wid * EA_HS, p.dv + (int64_t)b * p.v_bs + h * EA_DK, p.v_ts, o0 + 32 * wid, T, lane);
     }
-    EA_STAMP(5);
+    OTR_STAMP(p.trace, OTR_KID_ENCATTN + orient, g, 5, g < 256);
   }
 }
 
 }  // namespace
-
-extern unsigned long long* g_otr_trace;
 
 // shapes this kernel serves (attention.hip asks before it takes its own path)
 bool encattn_bwd_takes(int dtype_is_h16, int dk, int Tq, int Tk, int causal, int has_bias, int vec) {

@@ -15,7 +15,7 @@
 //     attention.hip's bias_load4); lane = key reads one column per register (the lanes of a wave are consecutive columns of one row: coalesced)
 //     and writes d bias = scale . dS the same way, EVERY in-range pair, masked ones with 0 (the caller keeps the tensor across steps);
 //   * it replaced attn_bwd_dq_kernel<96> + attn_bwd_dkdv_kernel<96> (27 + 55 us per Conformer block at the bench batch).
-#include "common.h"
+#include "tile32.h"
 
 namespace {
 
@@ -45,22 +45,6 @@ struct E9Args {
   float scale;
 };
 
-__device__ __forceinline__ uint4 e9_frag(const unsigned char* img, int row, int hi, int ks) {
-  return *reinterpret_cast<const uint4*>(img + row * E9_HS + (2 * ks + hi) * 16);
-}
-// contraction slots of step k2 (16 streamed rows from `col0`) in accumulator order: rows col0 + 16 k2 + 4 hi + e, then + 8
-__device__ __forceinline__ uint4 e9_tfrag(const unsigned char* timg, int row, int col0, int hi, int k2) {
-  const unsigned char* vr = timg + row * E9_TS + (col0 + 16 * k2 + 4 * hi) * 2;
-  const uint2 lo = *reinterpret_cast<const uint2*>(vr), up = *reinterpret_cast<const uint2*>(vr + 16);
-  return make_uint4(lo.x, lo.y, up.x, up.y);
-}
-__device__ __forceinline__ uint4 e9_pack8(const float* v) {
-  return make_uint4(pack2h(v[0], v[1]), pack2h(v[2], v[3]), pack2h(v[4], v[5]), pack2h(v[6], v[7]));
-}
-__device__ __forceinline__ void e9_zero(f32x16& a) {
-#pragma unroll
-  for (int r = 0; r < 16; ++r) a[r] = 0.f;
-}
 // staging chunk c = rows 32 c .. + 31 of the super-chunk: thread t holds piece (row 32 c + t / 16, 16 bytes t % 16) -- slots 12 .. 15 idle
 // (they load piece 11 again and drop it).  Rows past the end are clamped at the load and zeroed when they are written.
 // -> row-major image.  DOT: w is the same piece of a second matrix and sdot[row] = sum_d a[row][d] b[row][d] is left in LDS.
@@ -116,13 +100,13 @@ __device__ __forceinline__ void e9_store_rows(const f32x16 (&acc)[E9_CT], float 
       if (!live) v = make_uint2(0u, 0u);
       *reinterpret_cast<uint2*>(og + m * E9_HS + (32 * ct + 8 * q + 4 * hi) * 2) = v;
     }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  wait_lds();
 #pragma unroll
   for (int i = 0; i < 32 * E9_PPR / 64; ++i) {
     const int idx = lane + 64 * i, j = idx / E9_PPR, ch = idx - j * E9_PPR;
     if (row0 + j < T) st_global_b128(dst + (int64_t)(row0 + j) * ts + 8 * ch, *reinterpret_cast<const uint4*>(og + j * E9_HS + ch * 16));
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  wait_lds();
 }
 typedef float e9_f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
 
@@ -187,7 +171,7 @@ __global__ __launch_bounds__(512, 1) void encattn96_bwd_kernel(E9Args p) {
     const float* brow = p.bias + bb + (int64_t)ownc * p.bias_rs + (T - 1 - ownc);
     f32x16 dq[E9_CT];
 #pragma unroll
-    for (int ct = 0; ct < E9_CT; ++ct) e9_zero(dq[ct]);
+    for (int ct = 0; ct < E9_CT; ++ct) tile_zero(dq[ct]);
     for (int cc = 0; cc < nchunk; ++cc) {
       const int c = cc & 3, s0 = (cc >> 2) * E9_TI, Ts = min(E9_TI, T - s0);
       if (c == 0) {
@@ -214,9 +198,9 @@ __global__ __launch_bounds__(512, 1) void encattn96_bwd_kernel(E9Args p) {
         const unsigned char* kr = krm + c * 32 * E9_HS;
         const unsigned char* vr = vrm + c * 32 * E9_HS;
         f32x16 st, dp;
-        e9_zero(st); e9_zero(dp);
+        tile_zero(st); tile_zero(dp);
 #pragma unroll
-        for (int ks = 0; ks < E9_KS; ++ks) { mma32(st, e9_frag(kr, m, hi, ks), qf[ks]); mma32(dp, e9_frag(vr, m, hi, ks), dof[ks]); }
+        for (int ks = 0; ks < E9_KS; ++ks) { mma32(st, frag_rm(kr, E9_HS, m, hi, ks), qf[ks]); mma32(dp, frag_rm(vr, E9_HS, m, hi, ks), dof[ks]); }
         float dsv[16];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -231,9 +215,9 @@ __global__ __launch_bounds__(512, 1) void encattn96_bwd_kernel(E9Args p) {
         }
 #pragma unroll
         for (int k2 = 0; k2 < 2; ++k2) {
-          const uint4 pb = e9_pack8(dsv + 8 * k2);
+          const uint4 pb = frag_pack8(dsv + 8 * k2);
 #pragma unroll
-          for (int ct = 0; ct < E9_CT; ++ct) mma32(dq[ct], e9_tfrag(kt, 32 * ct + m, c * 32, hi, k2), pb);
+          for (int ct = 0; ct < E9_CT; ++ct) mma32(dq[ct], frag_tr(kt, E9_TS, 32 * ct + m, c * 32, hi, k2), pb);
         }
       }
     }
@@ -290,7 +274,7 @@ __global__ __launch_bounds__(512, 1) void encattn96_bwd_kernel(E9Args p) {
     const int64_t bcol = bb + (T - 1) + ownc, bstep = p.bias_rs - 1;
     f32x16 dk[E9_CT], dv[E9_CT];
 #pragma unroll
-    for (int ct = 0; ct < E9_CT; ++ct) { e9_zero(dk[ct]); e9_zero(dv[ct]); }
+    for (int ct = 0; ct < E9_CT; ++ct) { tile_zero(dk[ct]); tile_zero(dv[ct]); }
     for (int cc = 0; cc < nchunk; ++cc) {
       const int c = cc & 3, s0 = (cc >> 2) * E9_TI, Ts = min(E9_TI, T - s0);
       if (c == 0 && cc > 0) __syncthreads();                       // every wave is done with the previous super-chunk's images
@@ -312,9 +296,9 @@ __global__ __launch_bounds__(512, 1) void encattn96_bwd_kernel(E9Args p) {
         const unsigned char* qr = qrm + c * 32 * E9_HS;
         const unsigned char* dr = dorm + c * 32 * E9_HS;
         f32x16 st, dp;
-        e9_zero(st); e9_zero(dp);
+        tile_zero(st); tile_zero(dp);
 #pragma unroll
-        for (int ks = 0; ks < E9_KS; ++ks) { mma32(st, e9_frag(qr, m, hi, ks), kf[ks]); mma32(dp, e9_frag(dr, m, hi, ks), vf[ks]); }
+        for (int ks = 0; ks < E9_KS; ++ks) { mma32(st, frag_rm(qr, E9_HS, m, hi, ks), kf[ks]); mma32(dp, frag_rm(dr, E9_HS, m, hi, ks), vf[ks]); }
         float pv[16], dsv[16];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -342,11 +326,11 @@ __global__ __launch_bounds__(512, 1) void encattn96_bwd_kernel(E9Args p) {
         }
 #pragma unroll
         for (int k2 = 0; k2 < 2; ++k2) {
-          const uint4 pb = e9_pack8(pv + 8 * k2), sb = e9_pack8(dsv + 8 * k2);
+          const uint4 pb = frag_pack8(pv + 8 * k2), sb = frag_pack8(dsv + 8 * k2);
 #pragma unroll
           for (int ct = 0; ct < E9_CT; ++ct) {
-            mma32(dv[ct], e9_tfrag(dot, 32 * ct + m, c * 32, hi, k2), pb);
-            mma32(dk[ct], e9_tfrag(qt, 32 * ct + m, c * 32, hi, k2), sb);
+            mma32(dv[ct], frag_tr(dot, E9_TS, 32 * ct + m, c * 32, hi, k2), pb);
+            mma32(dk[ct], frag_tr(qt, E9_TS, 32 * ct + m, c * 32, hi, k2), sb);
           }
         }
       }
@@ -360,8 +344,6 @@ __global__ __launch_bounds__(512, 1) void encattn96_bwd_kernel(E9Args p) {
 }
 
 }  // namespace
-
-extern int g_otr_attn_enc96;       // api.hip (otr_debug_set(33, v))
 
 // shapes this kernel serves (attention.hip asks before it takes its own path): 16-bit, head dim 96, self-attention without a causal mask,
 // WITH the relative-position score term in fp32 whose rows allow the 16-byte loads (AttnArgs.bias_vec4), aligned operands

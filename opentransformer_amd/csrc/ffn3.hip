@@ -27,7 +27,7 @@
 // DMAs per wave are issued behind the first MFMA group of phase p+1 (scalar instructions only: wave-uniform source,
 // SGPR base + lane offset) and waited for with a counted vmcnt(16) at the end of phase p+3's predecessor, so a phase's data
 // has nearly three whole phases (> 3000 cycles) to land.  One barrier per phase (32 MFMAs per wave).
-#include "ffn_frag.h"
+#include "tile32.h"
 
 namespace {
 
@@ -46,31 +46,16 @@ constexpr int F3_BIAS = 8 * 1024;        // b_1 of the slice: [v1 chunk][value 3
 #else
 #define F3_ST_SAVE(P, V) st_global_b128((P), (V))
 #endif
-template <int N> __device__ __forceinline__ void f3_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void f3_wait_lds() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ void f3_barrier() {
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
   asm volatile("" ::: "memory");
 }
 
-// GEMM1's MFMA with the register classes spelled out: accumulator in VGPRs (the GLU's VALU code reads it without
-// v_accvgpr_read), weight fragment in VGPRs (fresh from ds_read), activation fragment in the ACCUMULATOR half of the register
-// file ("a": it is an MFMA operand only).  With the builtin hipcc keeps both operands in VGPRs; the 128 registers of x then
-// overflow the 256 architectural VGPRs and are shuttled through AGPRs (160 v_accvgpr moves per 32 MFMAs in the first build).
-// Hazards (hipcc pads nothing inside asm, cdna_hip_programming.md 5.7): the accumulate chain D -> C of the next MFMA needs no
-// wait states; the VALU readers of the result sit behind a barrier and an explicit s_nop (F3_MFMA_DRAIN); and every statement
-// opens with `s_nop 1`: hipcc is free to place a VALU write of an operand (a register copy of the bias-initialised
-// accumulator, seen in one build: the first chunk's row tile 0 came out wrong) directly in front of the statement, and a VALU
-// write -> MFMA read needs two wait states.  Inside a back-to-back MFMA stream the two states hide behind the busy pipe.
-#ifdef OTR_HALF_FP16
-#define F3_MFMA_OP "v_mfma_f32_32x32x16_f16"
-#else
-#define F3_MFMA_OP "v_mfma_f32_32x32x16_bf16"
-#endif
-__device__ __forceinline__ void f3_mma_xa(f32x16& acc, const otr_u32x4& w, const otr_u32x4& x_acc) {
-  asm volatile("s_nop 1\n\t" F3_MFMA_OP " %0, %1, %2, %0" : "+v"(acc) : "v"(w), "a"(x_acc));
-}
+// GEMM1 and the backward's du GEMM multiply with mma32_agpr_b (common.h): accumulator in VGPRs (the GLU's VALU code reads it
+// without v_accvgpr_read), weight fragment in VGPRs (fresh from ds_read), the activation / dy fragments -- 128 registers, resident
+// for the whole kernel -- in the ACCUMULATOR half of the register file.  The VALU readers of the result sit behind a barrier and
+// an explicit s_nop:
 #define F3_MFMA_DRAIN() asm volatile("s_nop 15\n\ts_nop 3" ::: "memory")   /* >= 12 wait states: MFMA result -> VALU reader */
 
 // ---- partial-sum exchange between the four workgroups of a row block (fused forms).  Accumulator layout throughout: tile
@@ -190,7 +175,7 @@ __device__ __forceinline__ void f3_recv_partials(otr_u32x4 (&part)[3][2][4], f3_
 // the fragments straight from global memory (lane (m, hi) fetches 16 bytes of ITS row per contraction step) touches 64
 // different 128-byte lines per instruction, and the 32 KiB of a row tile thrash the L1: the forward prologue took 11.9 k
 // cycles (5.7 us of a 45 us kernel, per-workgroup clock stamps).  Coalesced loads (a wave instruction covers two whole rows)
-// into an XOR-swizzled row-major image (chunk index ^ (row & 15): conflict-free for the fragment reads, ffn_frag.h), two
+// into an XOR-swizzled row-major image (chunk index ^ (row & 15): conflict-free for the fragment reads, tile32.h), two
 // barriers, 32 ds_read_b128 per lane.
 template <int D>
 __device__ __forceinline__ void f3_stage_rows128(uint4* xs, const uint16_t* src, int rb, int M, int tid) {
@@ -265,7 +250,7 @@ __device__ __forceinline__ void f3_store_slab(const f32x16 (&acc)[2][4], unsigne
       for (int q = 0; q < 4; ++q)
         *reinterpret_cast<uint2*>(lds + (64 * wr + 32 * rt + m) * TS + (128 * wc + 32 * ct + 8 * q + 4 * hi) * 2) =
             make_uint2(pack2h(acc[rt][ct][4 * q], acc[rt][ct][4 * q + 1]), pack2h(acc[rt][ct][4 * q + 2], acc[rt][ct][4 * q + 3]));
-  f3_wait_lds();
+  wait_lds();
   f3_barrier();
 #pragma unroll
   for (int k = 0; k < 16; ++k) {
@@ -275,6 +260,9 @@ __device__ __forceinline__ void f3_store_slab(const f32x16 (&acc)[2][4], unsigne
     if (row < M) st_global_b128(slab_rows + row * 256 + m * 8, v);
   }
 }
+
+// tuning hook of both kernels (TRACE instantiations): thread 0 stamps the shader clock into trace[workgroup * 48 + i], i < 48
+#define F3_STAMP() if constexpr (TRACE) { if (p.trace && tid == 0 && stamp_i < 48) p.trace[(int64_t)blockIdx.x * 48 + stamp_i++] = __builtin_amdgcn_s_memtime(); }
 
 template <int D, bool TRACE, bool SAVE, bool SLAB = false>
 __global__ __launch_bounds__(256, 1) void ffn3_fwd_kernel(Ffn3FwdArgs p) {
@@ -294,7 +282,6 @@ __global__ __launch_bounds__(256, 1) void ffn3_fwd_kernel(Ffn3FwdArgs p) {
   if (rb * 128 >= p.M) return;                                   // whole workgroup: the grid is padded to whole XCD groups
   const int row0 = rb * 128 + wr * 64;
   int stamp_i = 0;
-#define F3_STAMP() if constexpr (TRACE) { if (p.trace && tid == 0 && stamp_i < 48) p.trace[(int64_t)blockIdx.x * 48 + stamp_i++] = __builtin_amdgcn_s_memtime(); }
   // the constant-rate clock all XCDs share (100 MHz): when each workgroup starts / ends, at [256 * 48 + 2 workgroup + 0 / 1]
 #define F3_REALTIME(K) if constexpr (TRACE) { if (p.trace && tid == 0) p.trace[256 * 48 + 2 * (int64_t)blockIdx.x + (K)] = __builtin_amdgcn_s_memrealtime(); }
   F3_REALTIME(0)
@@ -313,7 +300,7 @@ __global__ __launch_bounds__(256, 1) void ffn3_fwd_kernel(Ffn3FwdArgs p) {
   const unsigned char* psrc = nullptr;
   uint32_t pa = 0, pb = 0, pc = 0, pdst = 0;
   int pC = 0, pk = 0;                                            // the next phase to schedule
-  const uint32_t ring0 = (uint32_t)(uintptr_t)(ffn_lds_byte*)ring;
+  const uint32_t ring0 = (uint32_t)(uintptr_t)(lds_byte*)ring;
   const uint32_t lane_off = (uint32_t)lane * 16u;
   auto schedule = [&](int slot) {
     const bool w2 = pk == 2 || pC >= NC;
@@ -331,8 +318,8 @@ __global__ __launch_bounds__(256, 1) void ffn3_fwd_kernel(Ffn3FwdArgs p) {
   };
   auto issue2 = [&](int i) {                                     // fragments 2i, 2i + 1 of the scheduled phase
     const uint32_t o = pa * (uint32_t)(i >> 1) + pb * (uint32_t)(i & 1);
-    ffn_dma(psrc + ((uint64_t)o << 10), lane_off, pdst + (uint32_t)(2 * i) * 1024u);
-    ffn_dma(psrc + ((uint64_t)(o + pc) << 10), lane_off, pdst + (uint32_t)(2 * i + 1) * 1024u);
+    lds_dma_sbase(psrc + ((uint64_t)o << 10), lane_off, pdst + (uint32_t)(2 * i) * 1024u);
+    lds_dma_sbase(psrc + ((uint64_t)(o + pc) << 10), lane_off, pdst + (uint32_t)(2 * i + 1) * 1024u);
   };
 
   schedule(0);
@@ -349,7 +336,7 @@ __global__ __launch_bounds__(256, 1) void ffn3_fwd_kernel(Ffn3FwdArgs p) {
     const int c = i >> 6, j = i & 63;
     bias_s[i] = p.b1[(j < 32 ? 0 : p.F) + (c_base + c) * 32 + (j & 31)];
   }
-  f3_wait_lds();
+  wait_lds();
   f3_barrier();
   if constexpr (!SLAB) f3_sync_publish(sy, sl, tid);
   otr_u32x4 xf[2][NKS];
@@ -366,23 +353,19 @@ __global__ __launch_bounds__(256, 1) void ffn3_fwd_kernel(Ffn3FwdArgs p) {
   for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) asm volatile("" : "+a"(xf[rt][ks]));
-  f3_wait_lds();
+  wait_lds();
   f3_barrier();                                                  // every wave has its fragments: slots 2 and 3 may be filled
   schedule(2);
 #pragma unroll
   for (int i = 0; i < 4; ++i) issue2(i);
   schedule(3);                                                   // issued between the MFMA groups of phase 0
-  f3_wait_vm<16>();                                              // phase 0 has landed (phases 1, 2 may fly)
+  wait_vm<16>();                                                 // phase 0 has landed (phases 1, 2 may fly)
   f3_barrier();
   F3_STAMP()
 
   f32x16 yacc[2][4];
 #pragma unroll
-  for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) yacc[rt][ct][r] = 0.f;
+  for (int rt = 0; rt < 2; ++rt) tile_zero(yacc[rt]);
   f32x16 hv[2], hg[2];
   uint4 uown[2][2], upart[2][2];
 #pragma unroll
@@ -435,8 +418,8 @@ __global__ __launch_bounds__(256, 1) void ffn3_fwd_kernel(Ffn3FwdArgs p) {
       __builtin_amdgcn_sched_barrier(0);                                                                       \
       _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                          \
         const int ks = (HALF) * 8 + 2 * g + (j >> 1);                                                          \
-        if (j & 1) { f3_mma_xa(hg[0], fr[g & 1][j], xf[0][ks]); f3_mma_xa(hg[1], fr[g & 1][j], xf[1][ks]); }   \
-        else       { f3_mma_xa(hv[0], fr[g & 1][j], xf[0][ks]); f3_mma_xa(hv[1], fr[g & 1][j], xf[1][ks]); }   \
+        if (j & 1) { mma32_agpr_b(hg[0], fr[g & 1][j], xf[0][ks]); mma32_agpr_b(hg[1], fr[g & 1][j], xf[1][ks]); }   \
+        else       { mma32_agpr_b(hv[0], fr[g & 1][j], xf[0][ks]); mma32_agpr_b(hv[1], fr[g & 1][j], xf[1][ks]); }   \
       }                                                                                                        \
       if constexpr (SAVE && (STP)) u_store(CHP, g);    /* the previous chunk's u */                             \
       F3_ISSUE2(g)                                                                                             \
@@ -449,8 +432,8 @@ __global__ __launch_bounds__(256, 1) void ffn3_fwd_kernel(Ffn3FwdArgs p) {
   // group may still fly -- the 16 DMAs of the two phases after it plus EXTRA = the global stores of those two phases (SAVE: 12
   // per G phase, unconditional so that the count is exact)
 #define F3_PHASE_END(EXTRA)                                                                                    \
-  f3_wait_vm<16 + (EXTRA)>();                                                                                 \
-  f3_wait_lds();                                                                                               \
+  wait_vm<16 + (EXTRA)>();                                                                                     \
+  wait_lds();                                                                                                  \
   f3_barrier();                                                                                                \
   schedule(slot);                                                                                              \
   slot = (slot + 1) & 3;                                                                                       \
@@ -557,8 +540,8 @@ __global__ __launch_bounds__(256, 1) void ffn3_fwd_kernel(Ffn3FwdArgs p) {
 #undef F3_PHASE_G
 #undef F3_READ_PARTNER
   F3_STAMP()
-  f3_wait_vm<0>();                                               // the placeholder DMAs have landed: the ring becomes scratch
-  f3_wait_lds();
+  wait_vm<0>();                                                  // the placeholder DMAs have landed: the ring becomes scratch
+  wait_lds();
   f3_barrier();
   F3_STAMP()
   if constexpr (SLAB) {
@@ -602,8 +585,8 @@ __global__ __launch_bounds__(256, 1) void ffn3_fwd_kernel(Ffn3FwdArgs p) {
       btr[t][q] = *reinterpret_cast<const float4*>(p.beta + col);
     }
   F3_STAMP()
-  f3_wait_vm<0>();                                               // this wave's write-through stores are at memory
-  f3_wait_lds();
+  wait_vm<0>();                                                  // this wave's write-through stores are at memory
+  wait_lds();
   f3_barrier();
   F3_STAMP()
   if (tid == 0) f3_arrive_wait(sy, p.spin_limit, p.fault);
@@ -644,7 +627,7 @@ __global__ __launch_bounds__(256, 1) void ffn3_fwd_kernel(Ffn3FwdArgs p) {
   F3_STAMP()
   sm += __shfl_xor(sm, 32);
   if (hi == 0) red[wid * 32 + m] = sm;
-  f3_wait_lds();
+  wait_lds();
   f3_barrier();
   const float mean = (red[m] + red[32 + m] + red[64 + m] + red[96 + m]) * (1.f / D);
   float qq = 0.f;
@@ -654,7 +637,7 @@ __global__ __launch_bounds__(256, 1) void ffn3_fwd_kernel(Ffn3FwdArgs p) {
     for (int r = 0; r < 16; ++r) { const float d_ = v[t][r] - mean; qq += d_ * d_; }
   qq += __shfl_xor(qq, 32);
   if (hi == 0) red[128 + wid * 32 + m] = qq;
-  f3_wait_lds();
+  wait_lds();
   f3_barrier();
   const float rstd = rsqrtf((red[128 + m] + red[160 + m] + red[192 + m] + red[224 + m]) * (1.f / D) + p.eps);
   if (live) {
@@ -687,7 +670,6 @@ __global__ __launch_bounds__(256, 1) void ffn3_fwd_kernel(Ffn3FwdArgs p) {
     if (wid == 0 && hi == 0) { p.mean[row] = mean; p.rstd[row] = rstd; }
   }
   F3_STAMP()
-#undef F3_STAMP
 }
 
 
@@ -731,10 +713,6 @@ __device__ __forceinline__ void f3_gload(otr_u32x4& dst, const void* uniform_src
 template <int N> __device__ __forceinline__ void f3_wait_vm_for(otr_u32x4& a, otr_u32x4& b, otr_u32x4& c, otr_u32x4& d) {
   asm volatile("s_waitcnt vmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N) : "memory");
 }
-__device__ __forceinline__ void f3_mma_acc(f32x16& acc, const otr_u32x4& w, const otr_u32x4& b_acc) {
-  asm volatile("s_nop 1\n\t" F3_MFMA_OP " %0, %1, %2, %0" : "+v"(acc) : "v"(w), "a"(b_acc));
-}
-__device__ __forceinline__ float f3_h2f_lo(uint32_t w) { return h2f_lo(w); }
 
 template <int D, bool TRACE, bool SLAB = false>
 __global__ __launch_bounds__(256, 1) void ffn3_bwd_kernel(Ffn3BwdArgs p) {
@@ -754,8 +732,7 @@ __global__ __launch_bounds__(256, 1) void ffn3_bwd_kernel(Ffn3BwdArgs p) {
   if (rb * 128 >= p.M) return;
   const int row0 = rb * 128 + wr * 64;
   int stamp_i = 0;
-#define F3B_STAMP() if constexpr (TRACE) { if (p.trace && tid == 0 && stamp_i < 48) p.trace[(int64_t)blockIdx.x * 48 + stamp_i++] = __builtin_amdgcn_s_memtime(); }
-  F3B_STAMP()
+  F3_STAMP()
   F3Sync sy{};
   if constexpr (!SLAB) f3_sync_begin(sy, p.sync + 8 * rb, p.coh_only ? 16 + sl : f3_xcc_id());
   const int nchunk = p.F / 32, per = nchunk / 4, NC = per >> 1;
@@ -769,7 +746,7 @@ __global__ __launch_bounds__(256, 1) void ffn3_bwd_kernel(Ffn3BwdArgs p) {
   const unsigned char* psrc = nullptr;
   uint32_t pa = 0, pb = 0, pc = 0, pdst = 0;
   int pC = 0, pk = 0;
-  const uint32_t ring0 = (uint32_t)(uintptr_t)(ffn_lds_byte*)ring;
+  const uint32_t ring0 = (uint32_t)(uintptr_t)(lds_byte*)ring;
   const uint32_t lane_off = (uint32_t)lane * 16u;
   auto schedule = [&](int slot) {
     int kind, ch;                                                // kind 0: w_2^T, 1: own step, 2: partner step
@@ -789,8 +766,8 @@ __global__ __launch_bounds__(256, 1) void ffn3_bwd_kernel(Ffn3BwdArgs p) {
   };
   auto issue2 = [&](int i) {
     const uint32_t o = pa * (uint32_t)(i >> 1) + pb * (uint32_t)(i & 1);
-    ffn_dma(psrc + ((uint64_t)o << 10), lane_off, pdst + (uint32_t)(2 * i) * 1024u);
-    ffn_dma(psrc + ((uint64_t)(o + pc) << 10), lane_off, pdst + (uint32_t)(2 * i + 1) * 1024u);
+    lds_dma_sbase(psrc + ((uint64_t)o << 10), lane_off, pdst + (uint32_t)(2 * i) * 1024u);
+    lds_dma_sbase(psrc + ((uint64_t)(o + pc) << 10), lane_off, pdst + (uint32_t)(2 * i + 1) * 1024u);
   };
 #define F3B_ISSUE2(I) if ((I) == 0) { issue2(0); issue2(1); issue2(2); issue2(3); }   /* see ffn3_fwd_kernel */
 
@@ -804,7 +781,7 @@ __global__ __launch_bounds__(256, 1) void ffn3_bwd_kernel(Ffn3BwdArgs p) {
   // and 3 (f3_stage_rows128)
   uint4* xs = reinterpret_cast<uint4*>(ring + 2 * F3_PHASE);
   f3_stage_rows128<D>(xs, p.dy16, rb, p.M, tid);
-  f3_wait_lds();
+  wait_lds();
   f3_barrier();
   if constexpr (!SLAB) f3_sync_publish(sy, sl, tid);
   otr_u32x4 dyf[2][NKS];
@@ -819,7 +796,7 @@ __global__ __launch_bounds__(256, 1) void ffn3_bwd_kernel(Ffn3BwdArgs p) {
   for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) asm volatile("" : "+a"(dyf[rt][ks]));
-  f3_wait_lds();
+  wait_lds();
   f3_barrier();                                                  // every wave has its fragments: slots 2 and 3 may be filled
   // the saved (value, sigmoid) tiles of chunk C for this wave: 8 pieces; hp[0..3] = row tile 0 (value 0, 1, sigmoid 0, 1),
   // hp[4..7] = row tile 1
@@ -846,11 +823,7 @@ __global__ __launch_bounds__(256, 1) void ffn3_bwd_kernel(Ffn3BwdArgs p) {
 
   f32x16 xacc[2][4];
 #pragma unroll
-  for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) xacc[rt][ct][r] = 0.f;
+  for (int rt = 0; rt < 2; ++rt) tile_zero(xacc[rt]);
   f32x16 du[2];
   uint4 dho[2][4], dhp[2][4];                                    // own / partner dh fragments of the previous chunk
 #pragma unroll
@@ -878,8 +851,7 @@ __global__ __launch_bounds__(256, 1) void ffn3_bwd_kernel(Ffn3BwdArgs p) {
   // D: du = w_2^T . dy over 16 contraction steps, 8 MFMAs per group of 4 fragments, two DMAs behind every group
 #define F3B_PHASE_D(SLOT, STP, CHP)                                                                            \
   {                                                                                                            \
-    _Pragma("unroll") for (int rt = 0; rt < 2; ++rt)                                                           \
-      _Pragma("unroll") for (int r = 0; r < 16; ++r) du[rt][r] = 0.f;                                          \
+    _Pragma("unroll") for (int rt = 0; rt < 2; ++rt) tile_zero(du[rt]);                                        \
     asm volatile("s_nop 3" ::: "memory");                                                                      \
     const otr_u32x4* wb = reinterpret_cast<const otr_u32x4*>(ring + (SLOT) * F3_PHASE) + wc * 64 + lane;       \
     otr_u32x4 fr[2][4];                                                                                        \
@@ -890,8 +862,8 @@ __global__ __launch_bounds__(256, 1) void ffn3_bwd_kernel(Ffn3BwdArgs p) {
       }                                                                                                        \
       __builtin_amdgcn_sched_barrier(0);                                                                       \
       _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                          \
-        f3_mma_acc(du[0], fr[g & 1][j], dyf[0][4 * g + j]);                                                    \
-        f3_mma_acc(du[1], fr[g & 1][j], dyf[1][4 * g + j]);                                                    \
+        mma32_agpr_b(du[0], fr[g & 1][j], dyf[0][4 * g + j]);                                                  \
+        mma32_agpr_b(du[1], fr[g & 1][j], dyf[1][4 * g + j]);                                                  \
       }                                                                                                        \
       if constexpr (STP) { dh_store(CHP, 2 * g); dh_store(CHP, 2 * g + 1); }   /* the previous chunk's dh */     \
       F3B_ISSUE2(g)                                                                                            \
@@ -899,8 +871,8 @@ __global__ __launch_bounds__(256, 1) void ffn3_bwd_kernel(Ffn3BwdArgs p) {
     }                                                                                                          \
   }
 #define F3B_PHASE_END(KEEP)                                                                                    \
-  f3_wait_vm<(KEEP)>();                                                                                       \
-  f3_wait_lds();                                                                                               \
+  wait_vm<(KEEP)>();                                                                                           \
+  wait_lds();                                                                                                  \
   f3_barrier();                                                                                                \
   schedule(slot);                                                                                              \
   slot = (slot + 1) & 3;
@@ -977,16 +949,16 @@ __global__ __launch_bounds__(256, 1) void ffn3_bwd_kernel(Ffn3BwdArgs p) {
   int slot = 0;
   uint4 dhn[2][4];                                               // the fragments the GLU' of this iteration produces
   // ---- chunk 0: D, then GLU' only
-  F3B_STAMP()
+  F3_STAMP()
   F3B_PHASE_D(slot, false, 0)
   F3B_PHASE_END(16)
-  F3B_STAMP()
+  F3_STAMP()
   F3B_PHASE_X(false, true, slot, dho, 0, 0, dhn)
   F3B_PHASE_END(16)
-  F3B_STAMP()
+  F3_STAMP()
   F3B_PHASE_X(false, true, slot, dhp, 1, 0, dhn)
   F3B_PHASE_END(16)
-  F3B_STAMP()
+  F3_STAMP()
 #pragma unroll
   for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
@@ -996,13 +968,13 @@ __global__ __launch_bounds__(256, 1) void ffn3_bwd_kernel(Ffn3BwdArgs p) {
     F3B_READ_PARTNER()                                           // dh of chunk C-1 (written before the barriers of its X phases)
     F3B_PHASE_D(slot, true, C - 1)
     F3B_PHASE_END(16)
-    F3B_STAMP()
+    F3_STAMP()
     F3B_PHASE_X(true, true, slot, dho, 0, C, dhn)
     F3B_PHASE_END(16)
-    F3B_STAMP()
+    F3_STAMP()
     F3B_PHASE_X(true, true, slot, dhp, 1, C, dhn)
     F3B_PHASE_END(16)
-    F3B_STAMP()
+    F3_STAMP()
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
@@ -1015,8 +987,8 @@ __global__ __launch_bounds__(256, 1) void ffn3_bwd_kernel(Ffn3BwdArgs p) {
 #pragma unroll
   for (int t = 0; t < 8; ++t) dh_store(NC - 1, t);               // the last chunk's dh
   F3B_PHASE_X(true, false, slot, dho, 0, 0, dhn)
-  f3_wait_vm<8>();    // of the last X phase: its 4 tile reloads + 4 of its DMAs at most
-  f3_wait_lds();
+  wait_vm<8>();    // of the last X phase: its 4 tile reloads + 4 of its DMAs at most
+  wait_lds();
   f3_barrier();
   slot = (slot + 1) & 3;
   F3B_PHASE_X(true, false, slot, dhp, 1, 0, dhn)
@@ -1029,12 +1001,12 @@ __global__ __launch_bounds__(256, 1) void ffn3_bwd_kernel(Ffn3BwdArgs p) {
 #undef F3B_READ_PARTNER
   f3_wait_vm_for<0>(hp[0], hp[1], hp[2], hp[3]);                 // the last (unused) tile reloads land in registers that stay
   f3_wait_vm_for<0>(hp[4], hp[5], hp[6], hp[7]);                 // theirs until here; everything else has drained too
-  f3_wait_lds();
+  wait_lds();
   f3_barrier();
-  F3B_STAMP()
+  F3_STAMP()
   if constexpr (SLAB) {
     f3_store_slab(xacc, ring, p.slab + (int64_t)sl * p.M * 256, rb, p.M, wid, wr, wc, lane);    // see ffn3_fwd_kernel
-    F3B_STAMP()
+    F3_STAMP()
     return;
   }
 
@@ -1052,8 +1024,8 @@ __global__ __launch_bounds__(256, 1) void ffn3_bwd_kernel(Ffn3BwdArgs p) {
     for (int q = 0; q < 4; ++q)
       sk[t][q] = p.skip ? *reinterpret_cast<const float4*>(p.skip + crow * D + 32 * (2 * wid + t) + 8 * q + 4 * hi)
                         : make_float4(0.f, 0.f, 0.f, 0.f);
-  f3_wait_vm<0>();
-  f3_wait_lds();
+  wait_vm<0>();
+  wait_lds();
   f3_barrier();
   if (tid == 0) f3_arrive_wait(sy, p.spin_limit, p.fault);
   f3_barrier();
@@ -1077,16 +1049,10 @@ __global__ __launch_bounds__(256, 1) void ffn3_bwd_kernel(Ffn3BwdArgs p) {
 }  // namespace
 
 // hidden slices x row blocks, padded to whole XCD groups (f3_block_map)
-extern int g_otr_ffn_map;   // api.hip (otr_debug_set(15, v))
 static inline unsigned f3_grid(int64_t M, int S) {
   const int64_t blocks = (M + 127) / 128;
   return g_otr_ffn_map ? (unsigned)(8 * ((blocks + 1) / 2)) : (unsigned)(8 * S * ((blocks + 7) / 8));
 }
-
-extern int g_otr_spin_limit;
-extern int32_t* g_otr_fault;
-extern int g_otr_ffn_coh_only;
-extern unsigned long long* g_otr_trace;
 
 // the stamped instantiations run only while otr_debug_trace has set a buffer
 #define F3_LAUNCH_FWD(SAVE, SLAB)                                                                                  \

@@ -23,7 +23,7 @@
 //    residual / LayerNorm epilogue (forward) or the skip-connection add (backward) runs on whole rows.
 // Bound: the 3 MB (forward) / 5 MB (backward) of packed weights stream from L2 into every CU: 64 B/clk/CU ->
 // ~20 us / ~33 us per layer at B=32, i.e. ~50 % of the MFMA rate; HBM traffic is a few MB.
-#include "ffn_frag.h"
+#include "tile32.h"
 
 // ------------------------------------------------------------------------------------------------ weight packing
 // Fragment (rt, ks) of a logical matrix A[r][c] (r = free index, c = contraction index), element (r, c) at
@@ -329,7 +329,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void ffn_ln_fwd_kernel(FfnFwdArgs 
     for (int s = 0; s < STEPS; ++s) {
       const uint4 w = ring[s % PD];
       if (s < 2 * NKS) {
-        if ((s & 1) == 0) xb = frag_b<D>(xs, m, hi, s >> 1);
+        if ((s & 1) == 0) xb = frag_xor<D>(xs, m, hi, s >> 1);
         if (s & 1) mma32(ag, w, xb); else mma32(av, w, xb);
       } else {
         const int t = s - 2 * NKS;
@@ -449,10 +449,10 @@ __global__ __launch_bounds__(256, 1) void ffn_bwd_kernel(FfnBwdArgs p) {
     for (int s = 0; s < STEPS; ++s) {
       const uint4 w = ring[s % PD];
       if (s < S1) {
-        if ((s & 1) == 0) ob = frag_b<D>(xs, m, hi, s >> 1);
+        if ((s & 1) == 0) ob = frag_xor<D>(xs, m, hi, s >> 1);
         if (s & 1) mma32(ag, w, ob); else mma32(av, w, ob);
       } else if (s < S2) {
-        ob = frag_b<D>(ds, m, hi, s - S1);
+        ob = frag_xor<D>(ds, m, hi, s - S1);
         mma32(du, w, ob);
       } else {
         const int t = s - S2;

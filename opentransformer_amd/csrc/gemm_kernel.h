@@ -1073,8 +1073,6 @@ __global__ __launch_bounds__(256, 2) void gemm_batched_kernel(GemmArgs p) {
 // ------------------------------------------------------------------------------------------------
 // Tile / split-K selection.  Goal: >= ~512 workgroups (2 per CU) whenever the problem allows it; split-K
 // only when the output grid alone cannot fill the chip and a workspace was provided.
-extern int g_otr_force_tile;    // 0 = heuristic, 64 / 128 = forced (tuning hook: otr_debug_set(0, v))
-extern int g_otr_force_ksplit;  // 0 = heuristic, n = forced                  (otr_debug_set(1, v))
 constexpr int OTR_RESIDENT_WG = 512;     // 256 CUs x 2 workgroups (launch_bounds(256, 2), 64 KB LDS each)
 constexpr int OTR_RESIDENT_WG64 = 1024;  // 64-wide tiles: 256 CUs x 4 workgroups (see gemm_launch_tiles)
 

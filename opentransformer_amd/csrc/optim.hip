@@ -6,8 +6,6 @@
 // is hipGraph-replayable:  state = {step, lr, bias_corr1, bias_corr2, sqnorm, skipped}.
 #include "common.h"
 
-extern int32_t* g_otr_fault;   // api.hip: sticky device fault word (otr_set_fault_counter) or NULL
-
 struct OptState {
   float step;            // [0] number of optimizer updates applied so far (Adam's t)
   float lr;              // [1] learning rate used by the last update

@@ -12,7 +12,7 @@
 // L2 -> VGPR through a register ring with no barrier in the loop, activations sit in LDS as MFMA B operands, and the
 // epilogue (bias / dropout / residual / LayerNorm, or the 16-bit store) runs on whole rows.  Bound: the packed weight
 // (128 KB for 256 x 256, 384 KB for 768 x 256) into every CU at ~22 B/clk: 3 / 8 us.
-#include "common.h"
+#include "tile32.h"
 #include "ln_pro.h"
 
 namespace {
@@ -35,9 +35,6 @@ template <int K, int NTHR = 256> __device__ __forceinline__ void rb_stage_rows(u
     const int i = tid + j * NTHR, r = i / CPR, ch = i % CPR;
     dst[r * CPR + (ch ^ (r & 15))] = v[j];
   }
-}
-template <int K> __device__ __forceinline__ uint4 rb_frag_b(const uint4* rows, int m, int hi, int ks) {
-  return rows[m * (K / 8) + ((2 * ks + hi) ^ (m & 15))];
 }
 
 // acc[i] (i < TPW) += W[tile (t0 + i)] . x^T: the wave walks the contraction outermost (one LDS operand per k-step, used by
@@ -66,7 +63,7 @@ template <int K, int TPW> struct RbStream {
     uint4 xb;
 #pragma clang loop unroll(full)
     for (int s = 0; s < STEPS; ++s) {
-      if (s % TPW == 0) xb = rb_frag_b<K>(xs, m, hi, ks_of(s));
+      if (s % TPW == 0) xb = frag_xor<K>(xs, m, hi, ks_of(s));
       const uint4 w = ring[s % RB_PD];
       mma32(acc[s % TPW], w, xb);
       if (s + RB_PD < STEPS) ring[s % RB_PD] = ld_global_b128(fptr(s + RB_PD));
@@ -74,14 +71,6 @@ template <int K, int TPW> struct RbStream {
     }
   }
 };
-
-// accumulator tile (out columns 8q + 4hi + (r&3), q = r>>2, of row m = lane&31) -> red[m][col0 + ...] (row stride RS floats)
-template <int RS> __device__ __forceinline__ void rb_put_tile(float* red, const f32x16& a, int col0, int lane) {
-  const int m = lane & 31, hi = lane >> 5;
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-    *reinterpret_cast<float4*>(red + m * RS + col0 + 8 * q + 4 * hi) = make_float4(a[4 * q], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3]);
-}
 
 // ------------------------------------------------------------------------------------------------ a touch for the launch that follows
 // Inside the step every launch finds its operands in HBM only.  Where that hurts the NEXT launch (scattered or latency-critical first
@@ -143,7 +132,7 @@ __global__ __launch_bounds__(256, NSPLIT) void rb_linear_kernel(RbLinArgs p) {
     for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
   ws.run(acc, xs, lane);
 #pragma unroll
-  for (int i = 0; i < TPW; ++i) rb_put_tile<RS>(red, acc[i], (wid * TPW + i) * 32, lane);
+  for (int i = 0; i < TPW; ++i) put_tile<RS>(red, acc[i], (wid * TPW + i) * 32, lane);
   __syncthreads();
   // whole rows: wave w owns rows 8w .. 8w+7, a lane 4 consecutive columns per pass of 256
 #pragma unroll
@@ -206,7 +195,7 @@ __global__ __launch_bounds__(NW * 64, NSPLIT) void rb_linear_ln_kernel(RbLinLnAr
     for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
   ws.run(acc, xs, lane);
 #pragma unroll
-  for (int i = 0; i < TPW; ++i) rb_put_tile<RS>(red, acc[i], (wid * TPW + i) * 32, lane);
+  for (int i = 0; i < TPW; ++i) put_tile<RS>(red, acc[i], (wid * TPW + i) * 32, lane);
   __syncthreads();
 #pragma unroll
   for (int rr = 0; rr < RPW; ++rr) {
@@ -283,7 +272,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void proj_ln_fwd_kernel(ProjLnArgs
   uint32_t sink[RB_TOUCH_PER] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
   rb_touch_issue(p.touch, sink, tid, 64 * NW);
 #pragma unroll
-  for (int i = 0; i < TPW; ++i) rb_put_tile<RS>(red, acc[i], (wid * TPW + i) * 32, lane);
+  for (int i = 0; i < TPW; ++i) put_tile<RS>(red, acc[i], (wid * TPW + i) * 32, lane);
   __syncthreads();
   // the 8 rows of a wave are normalised TOGETHER: their 2 x 6 butterfly steps are independent, so the cross-lane latency
   // is paid 12 times per wave instead of 96 (one row after the other it was ~5 us of this kernel)
@@ -476,7 +465,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ln_bwd_proj_kernel(LnBwdProjA
   uint32_t sink[RB_TOUCH_PER] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
   rb_touch_issue(p.touch, sink, tid, 64 * NW);                       // nothing below loads anything
 #pragma unroll
-  for (int i = 0; i < TPW; ++i) rb_put_tile<RS>(red, acc[i], (wid * TPW + i) * 32, lane);
+  for (int i = 0; i < TPW; ++i) put_tile<RS>(red, acc[i], (wid * TPW + i) * 32, lane);
   __syncthreads();
 #pragma unroll
   for (int i = 0; i < RPW; ++i) {
@@ -550,7 +539,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void rb_linear_ln_bwd_kernel(RbLin
   uint32_t sink[RB_TOUCH_PER] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
   rb_touch_issue(p.touch, sink, tid, 64 * NW);                       // nothing below loads anything
 #pragma unroll
-  for (int i = 0; i < TPW; ++i) rb_put_tile<RS>(red, acc[i], (wid * TPW + i) * 32, lane);
+  for (int i = 0; i < TPW; ++i) put_tile<RS>(red, acc[i], (wid * TPW + i) * 32, lane);
   __syncthreads();
   // ---- LayerNorm backward on this wave's 8 rows (ln_bwd_proj_kernel), dy = the product + skip
   float dg[4] = {0.f, 0.f, 0.f, 0.f}, db[4] = {0.f, 0.f, 0.f, 0.f}, dab[4] = {0.f, 0.f, 0.f, 0.f};

@@ -1,6 +1,9 @@
-// Device helpers shared by the fused FFN kernels (ffn_fused.hip: 32-row workgroups, weights L2 -> VGPR; ffn3.hip: 128-row
-// workgroups, weights through an LDS-DMA ring): the fragment conventions of otr_pack_frags, the GLU on accumulator tiles, the
-// accumulator-tile -> operand-fragment / row-major / column-sum conversions, and the direct-to-LDS fragment copy.
+// Device helpers for 32 x 32 MFMA tiles (v_mfma_f32_32x32x16 on the 16-bit type, mma32 in common.h) shared by the row-block,
+// fused-FFN, decoder-layer and encoder-attention kernels: the accumulator and operand-fragment conventions, the fragment reads of
+// the LDS images they stage, the accumulator-tile -> operand-fragment / row-major / column-sum conversions, and the GLU's sigmoid.
+//
+// Accumulator tile: lane (m = lane & 31, hi = lane >> 5) holds columns 8q + 4hi + (r & 3), q = r >> 2, of row m in its 16 registers.
+// Operand fragment (uint4): lane (m, hi) holds contraction elements 16 ks + 8 hi .. + 7 of row m for contraction step ks.
 #pragma once
 #include "common.h"
 
@@ -20,14 +23,50 @@ __device__ __forceinline__ void stage_rows(uint4* dst, const uint16_t* src, int 
     dst[r * CPR + (ch ^ (r & 15))] = ld_global_b128(src + (int64_t)gr * D + ch * 8);
   }
 }
-template <int D> __device__ __forceinline__ uint4 frag_b(const uint4* rows, int m, int hi, int ks) {
+// fragment (m, hi, ks) of such rows (D 16-bit elements each)
+template <int D> __device__ __forceinline__ uint4 frag_xor(const uint4* rows, int m, int hi, int ks) {
   return rows[m * (D / 8) + ((2 * ks + hi) ^ (m & 15))];
+}
+// fragment (m, hi, ks) of a padded row-major LDS image, `stride` bytes per row
+__device__ __forceinline__ uint4 frag_rm(const unsigned char* img, int stride, int m, int hi, int ks) {
+  return *reinterpret_cast<const uint4*>(img + m * stride + (2 * ks + hi) * 16);
+}
+// fragment of a transposed LDS image (`stride` bytes per row) with the contraction slots of step k2 in ACCUMULATOR order: elements
+// col0 + 16 k2 + 4 hi + e, then + 8 (e < 4) of row `row` -- so that an accumulator tile converted by frag_pack8 is the other operand
+__device__ __forceinline__ uint4 frag_tr(const unsigned char* timg, int stride, int row, int col0, int hi, int k2) {
+  const unsigned char* vr = timg + row * stride + (col0 + 16 * k2 + 4 * hi) * 2;
+  const uint2 lo = *reinterpret_cast<const uint2*>(vr), up = *reinterpret_cast<const uint2*>(vr + 16);
+  return make_uint4(lo.x, lo.y, up.x, up.y);
+}
+
+__device__ __forceinline__ void tile_zero(f32x16& a) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) a[r] = 0.f;
+}
+template <int N> __device__ __forceinline__ void tile_zero(f32x16 (&acc)[N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+}
+
+// eight floats -> one operand fragment of the 16-bit type
+__device__ __forceinline__ uint4 frag_pack8(const float* v) {
+  return make_uint4(pack2h(v[0], v[1]), pack2h(v[2], v[3]), pack2h(v[4], v[5]), pack2h(v[6], v[7]));
 }
 
 // accumulator tile (16 floats: hidden units 8q + 4hi + (r&3), q = r>>2, of row m = lane&31) -> two B-operand fragments
 __device__ __forceinline__ void tile_to_frags(const float* v, uint4& f0, uint4& f1) {
-  f0 = make_uint4(pack2h(v[0], v[1]), pack2h(v[2], v[3]), pack2h(v[4], v[5]), pack2h(v[6], v[7]));
-  f1 = make_uint4(pack2h(v[8], v[9]), pack2h(v[10], v[11]), pack2h(v[12], v[13]), pack2h(v[14], v[15]));
+  f0 = frag_pack8(v);
+  f1 = frag_pack8(v + 8);
+}
+
+// accumulator tile -> red[m][col0 + 8q + 4hi + (r&3)] (row stride RS floats)
+template <int RS> __device__ __forceinline__ void put_tile(float* red, const f32x16& a, int col0, int lane) {
+  const int m = lane & 31, hi = lane >> 5;
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    *reinterpret_cast<float4*>(red + m * RS + col0 + 8 * q + 4 * hi) = make_float4(a[4 * q], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3]);
 }
 
 // store an accumulator tile as 32 consecutive 16-bit elements of row m (row-major consumer: the weight-gradient GEMM).
@@ -68,30 +107,4 @@ __device__ __forceinline__ void tile_colsum_store(const float* v, float* dst, in
   d += __shfl_xor(d, 1);
   const int r = ((m >> 4) & 1) * 8 + ((m >> 3) & 1) * 4 + ((m >> 2) & 1) * 2 + ((m >> 1) & 1);
   if ((m & 1) == 0) dst[8 * (r >> 2) + 4 * hi + (r & 3)] = d;
-}
-
-// ------------------------------------------------------------------------------------------------ direct-to-LDS fragment copy
-typedef __attribute__((address_space(3))) unsigned char lds_byte;
-typedef __attribute__((address_space(1))) const unsigned char gbl_byte;
-
-// one 1 KiB fragment: 64 lanes x 16 B, global (fragment-major pack) -> LDS, asynchronous (vmcnt)
-// Inline asm, not __builtin_amdgcn_global_load_lds: with the builtin hipcc tracks the pending LDS write and puts
-// `s_waitcnt vmcnt(0)` in front of the next ds_read of ANY address -- i.e. it waited for the chunk it had just started to
-// fetch before multiplying the current one (seen in the ISA: the whole DMA latency exposed per chunk).  The asm form is
-// invisible to that bookkeeping; the kernels below wait themselves (vmcnt(0) + barrier right before a buffer is read).
-// M0 carries the wave-uniform LDS byte address and is restored afterwards (cdna_hip_programming.md 5.7).
-__device__ __forceinline__ void dma_frag(const uint4* src_frag, unsigned char* lds_frag, int lane) {
-  const uint32_t dst = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_byte*)lds_frag);
-  const uint4* src = src_frag + lane;
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-}
-
-// the same with a wave-uniform source (SGPR base + per-lane byte offset): scalar address arithmetic only
-typedef __attribute__((address_space(3))) unsigned char ffn_lds_byte;
-__device__ __forceinline__ void ffn_dma(const void* uniform_src, uint32_t lane_off, uint32_t lds_dst) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(lane_off), "s"(uniform_src), "s"(lds_dst) : "memory");
 }

@@ -25,12 +25,8 @@
 
 #include <algorithm>
 
-extern int g_otr_spin_limit;       // api.hip: bound of the turnstile spin (otr_debug_set(11, v))
-extern int32_t* g_otr_fault;       // api.hip: sticky device fault word (otr_set_fault_counter) or NULL
-
 namespace {
 
-typedef __attribute__((address_space(3))) unsigned char lds_byte;
 typedef short v4s __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) v4s lds_v4s;
 
@@ -38,20 +34,6 @@ constexpr int SLAB_ROWS = 16;
 constexpr int SLAB_BYTES = 16384;                 // 16 rows x 256 columns x 2 B, dy part then x part
 constexpr int RING = 8, AHEAD = 6;
 constexpr int LDS_BYTES = RING * SLAB_BYTES;      // 128 KB; after a piece's last slab the ring doubles as the epilogue's scratch (16 KB per wave)
-
-// one wave instruction: 64 lanes x 16 B, per-lane global source -> LDS [dst, dst + 1024) lane-linear.  Inline asm so
-// that hipcc does not see a pending LDS write (it would wait vmcnt(0) before the next ds_read, ffn_fused.hip).
-__device__ __forceinline__ void dma16(const void* src, uint32_t lds_dst) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void dma16_nt(const void* src, uint32_t lds_dst) {     // non-temporal: a stream no other tile reads
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src), "s"(lds_dst) : "memory");
-}
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 __device__ __forceinline__ uint2 tr_read(uint32_t lds_addr) {
   v4s r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(uintptr_t)lds_addr);
@@ -132,9 +114,8 @@ struct Stager {                 // this lane's share of the two DMA instructions
     } else {
       pb = ok && col_b ? base_b + slab * step_b : zeros;
     }
-    if constexpr (NTA) dma16_nt(pa, (uint32_t)(slot * SLAB_BYTES) + dst); else dma16(pa, (uint32_t)(slot * SLAB_BYTES) + dst);
-    if constexpr (NTB) dma16_nt(pb, (uint32_t)(slot * SLAB_BYTES) + 8192u + dst);
-    else dma16(pb, (uint32_t)(slot * SLAB_BYTES) + 8192u + dst);
+    lds_dma<NTA>(pa, (uint32_t)(slot * SLAB_BYTES) + dst);
+    lds_dma<NTB>(pb, (uint32_t)(slot * SLAB_BYTES) + 8192u + dst);
   }
 };
 
