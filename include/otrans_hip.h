@@ -667,6 +667,32 @@ int32_t otr_beam_prune(const float* k_score, const int64_t* k_idx, const float* 
                        const int64_t* preds_in, int64_t ldp, int32_t batch, int32_t beam, int32_t t, int32_t eos,
                        float* scores_out, uint8_t* flag_out, int64_t* preds_out, int32_t* n_finished, void* stream);
 
+/* ---- CTC prefix beam search (CTCRecognizer mode='beam'; recognize/ctc.py:60-67 hands it to ctcdecode), csrc/ctcbeam.hip.  f32.
+ * log_probs f32 [B, T, V]: frame (b, t) at log_probs + (b*T + t)*ld; lengths int32 [B] on the device, clamped to [0, T]; frames
+ * t >= lengths[b] are not read.  Standard prefix beam search in log space: every prefix carries pb (paths ending in blank) and pnb
+ * (ending in a non-blank); the empty prefix starts with pb = 0, pnb = -inf.  At frame t the candidates are the K tokens of highest
+ * log-prob (ties -> lower token); blank takes part only if it is among them.  For prefix s with last token l and candidate c, log-prob p:
+ *   c == blank:  pb'(s) += (pb(s) + pnb(s)) * p          (in log space: + is log-add-exp, * is +)
+ *   c == l:      pnb'(s) += pnb(s) * p,  pnb'(s+c) += pb(s) * p
+ *   other c:     pnb'(s+c) += (pb(s) + pnb(s)) * p
+ * Equal strings reached from different parents merge.  The new beam is the W entries of highest pb' + pnb' (log-add-exp) that are
+ * above -inf; ties go to the lower (parent slot, token), a prefix carried over from slot i counting as (i, -1).  After the last
+ * frame the beam is in descending score order.  The score-threshold pruning of ctcdecode ("min_cutoff") is NOT applied.
+ * Prefix identity inside the beam is (length, 64-bit hash): a false merge needs a hash collision between two of the <= W*(W+1)
+ * pairs compared per frame, probability <= T*W*(W+1) / 2^64 per utterance.
+ * otr_ctc_topk:        top_lp f32 / top_tok int32 [B*T, K] (rows of frames past lengths[b] are left untouched); V <= 8192,
+ *   K <= min(128, V) (ctcdecode's cutoff_top_n is 40; 128 lets K = V for the vocabularies up to 128).
+ * otr_ctc_beam_search: one launch, one workgroup per utterance; W <= 32.  workspace: otr_ctc_beam_workspace_bytes(B, T, W) bytes,
+ *   8-byte aligned (the back-pointer trie, int32 {parent node, token} per (b, t, slot)); tokens int64 [B, W, T] padded with -1,
+ *   out_len int32 [B, W], scores f32 [B, W] = log-probability of the prefix; slots past the live beam get score -inf, length 0.
+ * otr_ctc_beam_workspace_bytes: pure host function, -1 for a bad shape. */
+int64_t otr_ctc_beam_workspace_bytes(int32_t B, int32_t T, int32_t W);
+int32_t otr_ctc_topk(const float* log_probs, int64_t ld, const int32_t* lengths, int32_t B, int32_t T, int32_t V, int32_t K,
+                     float* top_lp, int32_t* top_tok, void* stream);
+int32_t otr_ctc_beam_search(const float* top_lp, const int32_t* top_tok, const int32_t* lengths, int32_t B, int32_t T, int32_t V,
+                            int32_t K, int32_t blank, int32_t W, void* workspace, int64_t ws_bytes, int64_t* tokens,
+                            int32_t* out_len, float* scores, void* stream);
+
 /* ---- transposed copies of many matrices in ONE launch (the W^T bf16 shadows that turn dx = dy.W into a
  *      forward-type GEMM; refreshed after every optimizer step).  table: DEVICE int64 [n_mats,4] rows of
  *      {element offset, rows, cols, first tile}; matrix i is src+offset [rows,cols] row-major and is written to

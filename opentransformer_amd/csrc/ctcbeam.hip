@@ -1,0 +1,289 @@
+// CTC prefix beam search on the device: the decoder behind CTCRecognizer(mode='beam') (recognize/ctc.py:60-67, which hands it to
+// the un-vendored ctcdecode_edited).  Two launches per batch, f32 in both builds; include/otrans_hip.h states the semantics.
+//  * ctc_topk:        one wave per frame (b, t < lengths[b]): the K best (log-prob, token) of the row, descending, ties -> lower
+//                     token.  The row sits in registers as order-preserving u32 keys; the K-th largest key is found by a 32-step
+//                     bitwise search over wave-wide counts, then the <= K winners are compacted and ranked in LDS.
+//  * ctc_beam_search: one workgroup per utterance runs every frame.  Beam state (pb, pnb, last token, length, prefix hash, parent
+//                     hash, trie node) lives in LDS; the back-pointer trie {parent node, token} lives in the caller's workspace and
+//                     is walked once after the last frame to write the hypotheses.
+#include "common.h"
+
+#define NEG_INF (-__builtin_huge_valf())
+
+constexpr int CB_MAXW = 32;                            // beam width
+constexpr int CB_MAXK = 128;                           // cutoff_top_n: ctcdecode's 40, or every token of a vocabulary <= 128
+constexpr int CB_MAXV = 8192;                          // vocabulary of the top-K pass (128 keys per lane)
+constexpr int CB_NT = 256;                             // threads of the search workgroup
+constexpr int CB_MAXC = CB_MAXW + CB_MAXW * CB_MAXW;   // candidates of a frame after the per-slot cut: W stays + W extensions per slot
+constexpr uint64_t CB_H0 = 0x6a09e667f3bcc908ull;      // hash of the empty prefix
+
+// ---------------------------------------------------------------- top-K of a frame
+// Order-preserving key of a float: a > b <=> key(a) > key(b).  -0 is folded onto +0 first.  The value 0 is never a key of a
+// real float, so it pads the lanes past V.
+__device__ __forceinline__ uint32_t cb_key(float x) {
+  const uint32_t u = __float_as_uint(x + 0.f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float cb_unkey(uint32_t k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+__device__ __forceinline__ int wave_isum(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+template <int NV>
+__global__ __launch_bounds__(64) void ctc_topk_kernel(const float* lp, int64_t ld, const int32_t* lengths, int T, int V, int K,
+                                                      float* out_lp, int32_t* out_tok) {
+  __shared__ uint32_t s_key[CB_MAXK];
+  __shared__ int s_tok[CB_MAXK];
+  const int64_t row = blockIdx.x;
+  const int b = (int)(row / T), t = (int)(row - (int64_t)b * T);
+  if (t >= lengths[b]) return;                         // frames past the utterance are not read (the search never reads them)
+  const int lane = threadIdx.x;
+  const float* x = lp + row * ld;
+  uint32_t key[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int v = lane + 64 * j;
+    key[j] = v < V ? cb_key(x[v]) : 0u;
+  }
+  // tau = the largest key with at least K keys >= it, i.e. the K-th largest key
+  uint32_t tau = 0;
+  for (int bit = 31; bit >= 0; --bit) {
+    const uint32_t cand = tau | (1u << bit);
+    int c = 0;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) c += key[j] >= cand;
+    if (wave_isum(c) >= K) tau = cand;
+  }
+  int gt = 0;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) gt += key[j] > tau;
+  const int need_eq = K - wave_isum(gt);               // >= 1: how many keys equal to tau are taken, lowest tokens first
+  const uint64_t lt_mask = (1ull << lane) - 1ull;
+  int base = 0, eq_seen = 0;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {                       // token v = lane + 64 j: ascending over (j, lane)
+    const bool eq = key[j] == tau;
+    const uint64_t eqm = __ballot(eq);
+    const bool sel = key[j] > tau || (eq && eq_seen + __popcll(eqm & lt_mask) < need_eq);
+    const uint64_t selm = __ballot(sel);
+    if (sel) {
+      const int p = base + __popcll(selm & lt_mask);
+      s_key[p] = key[j];
+      s_tok[p] = lane + 64 * j;
+    }
+    base += __popcll(selm);
+    eq_seen += __popcll(eqm);
+  }
+  __syncthreads();                                     // one wave per workgroup: orders the LDS writes before the reads
+  for (int e = lane; e < K; e += 64) {
+    const uint32_t k = s_key[e];
+    const int tok = s_tok[e];
+    int r = 0;
+    for (int q = 0; q < K; ++q) {
+      const uint32_t k2 = s_key[q];
+      r += k2 > k || (k2 == k && s_tok[q] < tok);
+    }
+    out_lp[row * K + r] = cb_unkey(k);
+    out_tok[row * K + r] = tok;
+  }
+}
+
+// ---------------------------------------------------------------- the search
+__device__ __forceinline__ float cb_lae(float a, float b) {   // log(exp a + exp b)
+  const float m = fmaxf(a, b);
+  if (m == NEG_INF) return NEG_INF;
+  return m + log1pf(expf(fminf(a, b) - m));
+}
+__device__ __forceinline__ uint64_t cb_hash(uint64_t h, int c) {   // prefix hash of (prefix with hash h) + token c: splitmix64 finaliser
+  uint64_t z = h ^ ((uint64_t)(c + 1) * 0x9e3779b97f4a7c15ull);
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+  return z ^ (z >> 31);
+}
+// candidate order: higher score first, then the lower key = (parent slot << 16) | (token + 1), a stay having token -1
+__device__ __forceinline__ bool cb_better(float s, int key, float s2, int key2) { return s > s2 || (s == s2 && key < key2); }
+struct CbPair { float s; int k; };   // (score, token) of an extension / (score, key) of a candidate: one 8-byte LDS read per compare
+
+__global__ __launch_bounds__(CB_NT) void ctc_beam_search_kernel(const float* top_lp, const int32_t* top_tok, const int32_t* lengths,
+                                                               int T, int K, int blank, int W, int2* trie, int64_t* tokens,
+                                                               int32_t* out_len, float* scores) {
+  __shared__ float f_lp[CB_MAXK];
+  __shared__ int f_tok[CB_MAXK];
+  __shared__ float s_pb[2][CB_MAXW], s_pnb[2][CB_MAXW];
+  __shared__ int s_last[2][CB_MAXW], s_len[2][CB_MAXW], s_node[2][CB_MAXW];
+  __shared__ uint64_t s_h[2][CB_MAXW], s_ph[2][CB_MAXW];
+  __shared__ float st_pb[CB_MAXW], st_pnb[CB_MAXW];    // the stays' new pb / pnb
+  __shared__ CbPair x_s[CB_MAXW * CB_MAXK];            // extension (slot i, candidate k): score (-inf = none or merged into a stay), token
+  __shared__ CbPair c_s[CB_MAXC];                      // the frame's candidates: score, key
+  __shared__ int s_n[2];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int len = min(max(lengths[b], 0), T);
+  int2* tr = trie + (int64_t)b * T * W;
+  if (tid == 0) {
+    s_pb[0][0] = 0.f; s_pnb[0][0] = NEG_INF; s_last[0][0] = -1; s_len[0][0] = 0; s_node[0][0] = -1;
+    s_h[0][0] = CB_H0; s_ph[0][0] = 0;
+  }
+  int cur = 0, n = 1;
+  const bool loader = tid < K;                         // K <= 128 < CB_NT
+  const int64_t fr0 = (int64_t)b * T * K;
+  float nlp = 0.f;
+  int ntok = 0;
+  if (loader && len > 0) { nlp = top_lp[fr0 + tid]; ntok = top_tok[fr0 + tid]; }
+  __syncthreads();
+  for (int t = 0; t < len && n > 0; ++t) {
+    const int nxt = cur ^ 1;
+    if (loader) {
+      f_lp[tid] = nlp; f_tok[tid] = ntok;
+      if (t + 1 < len) { nlp = top_lp[fr0 + (int64_t)(t + 1) * K + tid]; ntok = top_tok[fr0 + (int64_t)(t + 1) * K + tid]; }   // next frame, in flight during this one
+    }
+    if (tid == 0) s_n[nxt] = 0;
+    __syncthreads();
+    // (1) extension scores; an extension naming a string already in the beam is merged into that stay (step 1b)
+    for (int e = tid; e < n * K; e += CB_NT) {
+      const int i = e / K, c = f_tok[e - i * K];
+      float s = NEG_INF;
+      if (c != blank) {
+        s = (c == s_last[cur][i] ? s_pb[cur][i] : cb_lae(s_pb[cur][i], s_pnb[cur][i])) + f_lp[e - i * K];
+        const uint64_t h = s_h[cur][i];
+        const int l1 = s_len[cur][i] + 1;
+#pragma unroll 8
+        for (int j = 0; j < n; ++j)
+          if (s_len[cur][j] == l1 && s_last[cur][j] == c && s_ph[cur][j] == h) s = NEG_INF;
+      }
+      x_s[e] = CbPair{s, c};
+    }
+    // (1b) stays: blank, repeat of the last token, and the one extension (parent slot, last token) that names the same string
+    if (tid < n) {
+      const int j = tid, lj = s_last[cur][j];
+      float pbl = NEG_INF, pl = NEG_INF;
+#pragma unroll 8
+      for (int k = 0; k < K; ++k) {
+        if (f_tok[k] == blank) pbl = f_lp[k];
+        if (f_tok[k] == lj) pl = f_lp[k];
+      }
+      const float pb = cb_lae(s_pb[cur][j], s_pnb[cur][j]) + pbl;
+      float pnb = s_pnb[cur][j] + pl;
+      if (lj >= 0 && pl != NEG_INF) {
+        const uint64_t ph = s_ph[cur][j];
+        const int l0 = s_len[cur][j] - 1;
+#pragma unroll 8
+        for (int i = 0; i < n; ++i)
+          if (s_len[cur][i] == l0 && s_h[cur][i] == ph)
+            pnb = cb_lae(pnb, (s_last[cur][i] == lj ? s_pb[cur][i] : cb_lae(s_pb[cur][i], s_pnb[cur][i])) + pl);
+      }
+      st_pb[j] = pb;
+      st_pnb[j] = pnb;
+      c_s[j] = CbPair{cb_lae(pb, pnb), j << 16};
+    }
+    for (int e = n + tid; e < n + n * W; e += CB_NT) c_s[e] = CbPair{NEG_INF, 0};
+    __syncthreads();
+    // (2) per slot, only its W best extensions can enter the beam: rank them within the slot
+    for (int e = tid; e < n * K; e += CB_NT) {
+      const float s = x_s[e].s;
+      if (s == NEG_INF) continue;
+      const int i = e / K, tok = x_s[e].k;
+      const CbPair* xi = x_s + i * K;
+      int r = 0;
+#pragma unroll 8
+      for (int k = 0; k < K; ++k) {
+        const CbPair o = xi[k];
+        r += o.s > s || (o.s == s && o.k < tok);
+      }
+      if (r < W) c_s[n + i * W + r] = CbPair{s, (i << 16) | (tok + 1)};
+    }
+    __syncthreads();
+    // (3) rank every live candidate among all of them; rank r < W becomes slot r of the next beam
+    const int M = n + n * W;
+    for (int e = tid; e < M; e += CB_NT) {
+      const float s = c_s[e].s;
+      if (s == NEG_INF) continue;
+      const int key = c_s[e].k;
+      int r = 0;
+#pragma unroll 8
+      for (int q = 0; q < M; ++q) {
+        const CbPair o = c_s[q];
+        r += cb_better(o.s, o.k, s, key);
+      }
+      if (r >= W) continue;
+      atomicAdd(&s_n[nxt], 1);
+      const int i = key >> 16, tp = key & 0xffff;
+      if (tp == 0) {
+        s_pb[nxt][r] = st_pb[i]; s_pnb[nxt][r] = st_pnb[i];
+        s_last[nxt][r] = s_last[cur][i]; s_len[nxt][r] = s_len[cur][i]; s_node[nxt][r] = s_node[cur][i];
+        s_h[nxt][r] = s_h[cur][i]; s_ph[nxt][r] = s_ph[cur][i];
+      } else {
+        const int c = tp - 1;
+        s_pb[nxt][r] = NEG_INF; s_pnb[nxt][r] = s;
+        s_last[nxt][r] = c; s_len[nxt][r] = s_len[cur][i] + 1; s_node[nxt][r] = t * W + r;
+        s_h[nxt][r] = cb_hash(s_h[cur][i], c); s_ph[nxt][r] = s_h[cur][i];
+        tr[t * W + r] = make_int2(s_node[cur][i], c);
+      }
+    }
+    __syncthreads();
+    n = s_n[nxt];
+    cur = nxt;
+  }
+  // hypotheses, sorted by score (the last selection ranked them); slots past the live beam: score -inf, length 0, all -1
+  int64_t* tk = tokens + (int64_t)b * W * T;
+  for (int e = tid; e < W * T; e += CB_NT) {
+    const int r = e / T, pos = e - r * T;
+    if (r >= n || pos >= s_len[cur][r]) tk[e] = -1;
+  }
+  if (tid < W) {
+    const int r = tid;
+    const bool live = r < n;
+    const int l = live ? s_len[cur][r] : 0;
+    scores[b * W + r] = live ? cb_lae(s_pb[cur][r], s_pnb[cur][r]) : NEG_INF;
+    out_len[b * W + r] = l;
+    int node = live ? s_node[cur][r] : -1;
+    for (int pos = l - 1; pos >= 0; --pos) {
+      const int2 nd = tr[node];
+      tk[(int64_t)r * T + pos] = nd.y;
+      node = nd.x;
+    }
+  }
+}
+
+extern "C" int64_t otr_ctc_beam_workspace_bytes(int32_t B, int32_t T, int32_t W) {
+  if (B < 1 || T < 1 || W < 1 || W > CB_MAXW) return -1;
+  return (int64_t)B * T * W * (int64_t)sizeof(int2);
+}
+
+extern "C" int32_t otr_ctc_topk(const float* log_probs, int64_t ld, const int32_t* lengths, int32_t B, int32_t T, int32_t V,
+                                int32_t K, float* top_lp, int32_t* top_tok, void* stream) {
+  OTR_REQUIRE(log_probs && lengths && top_lp && top_tok, "ctc_topk: null pointer");
+  OTR_REQUIRE(B >= 1 && T >= 1, "ctc_topk: bad shape B=%d T=%d", B, T);
+  OTR_REQUIRE(V >= 1 && V <= CB_MAXV && ld >= V, "ctc_topk: V=%d must be in [1, %d] and ld=%lld >= V", V, CB_MAXV, (long long)ld);
+  OTR_REQUIRE(K >= 1 && K <= CB_MAXK && K <= V, "ctc_topk: K=%d must be in [1, min(%d, V=%d)]", K, CB_MAXK, V);
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)((int64_t)B * T));
+  if (V <= 64 * 16)
+    hipLaunchKernelGGL(ctc_topk_kernel<16>, grid, dim3(64), 0, s, log_probs, ld, lengths, T, V, K, top_lp, top_tok);
+  else if (V <= 64 * 72)
+    hipLaunchKernelGGL(ctc_topk_kernel<72>, grid, dim3(64), 0, s, log_probs, ld, lengths, T, V, K, top_lp, top_tok);
+  else
+    hipLaunchKernelGGL(ctc_topk_kernel<128>, grid, dim3(64), 0, s, log_probs, ld, lengths, T, V, K, top_lp, top_tok);
+  return otr_check_launch("ctc_topk");
+}
+
+extern "C" int32_t otr_ctc_beam_search(const float* top_lp, const int32_t* top_tok, const int32_t* lengths, int32_t B, int32_t T,
+                                       int32_t V, int32_t K, int32_t blank, int32_t W, void* workspace, int64_t ws_bytes,
+                                       int64_t* tokens, int32_t* out_len, float* scores, void* stream) {
+  OTR_REQUIRE(top_lp && top_tok && lengths && workspace && tokens && out_len && scores, "ctc_beam_search: null pointer");
+  OTR_REQUIRE(B >= 1 && T >= 1, "ctc_beam_search: bad shape B=%d T=%d", B, T);
+  OTR_REQUIRE(W >= 1 && W <= CB_MAXW, "ctc_beam_search: beam width W=%d must be in [1, %d]", W, CB_MAXW);
+  OTR_REQUIRE(V >= 1 && V <= CB_MAXV, "ctc_beam_search: V=%d must be in [1, %d]", V, CB_MAXV);
+  OTR_REQUIRE(K >= 1 && K <= CB_MAXK && K <= V, "ctc_beam_search: K=%d must be in [1, min(%d, V=%d)]", K, CB_MAXK, V);
+  OTR_REQUIRE(blank >= 0 && blank < V, "ctc_beam_search: blank=%d must be in [0, V=%d)", blank, V);
+  OTR_REQUIRE(((uintptr_t)workspace & 7) == 0, "ctc_beam_search: workspace must be 8-byte aligned");
+  const int64_t need = otr_ctc_beam_workspace_bytes(B, T, W);
+  OTR_REQUIRE(ws_bytes >= need, "ctc_beam_search: workspace of %lld bytes, %lld needed (otr_ctc_beam_workspace_bytes)",
+              (long long)ws_bytes, (long long)need);
+  hipLaunchKernelGGL(ctc_beam_search_kernel, dim3(B), dim3(CB_NT), 0, (hipStream_t)stream, top_lp, top_tok, lengths, T, K, blank, W,
+                     (int2*)workspace, tokens, out_len, scores);
+  return otr_check_launch("ctc_beam_search");
+}

@@ -3459,3 +3459,37 @@ def log_softmax(x):
     y = torch.empty_like(x2)
     L.check(L.load().otr_log_softmax(_p(x2), _p(y), x2.shape[0], V, _stream()), 'otr_log_softmax')
     return y.view(x.shape)
+
+
+def ctc_prefix_beam_search(log_probs, lengths, beam_width=5, cutoff_top_n=40, blank=0, workspace=None):
+    """CTC prefix beam search on the device (include/otrans_hip.h otr_ctc_topk + otr_ctc_beam_search; the decoder that
+    recognize/ctc.py:60-67 takes from ctcdecode.CTCBeamDecoder without a scorer).  log_probs f32 [B, T, V] (log-softmax output),
+    lengths [B] frames per utterance.  Returns (tokens int64 [B, W, T] padded with -1, out_len int32 [B, W], scores f32 [B, W]),
+    each utterance's beam in descending score order; slots past the live beam have score -inf and length 0.  cutoff_top_n is
+    clamped to V.  ctcdecode's score-threshold pruning (cutoff_prob / "min_cutoff") is not applied.  Two launches on the current
+    stream, no host synchronisation: capturable into a graph (pass `workspace`, otr_ctc_beam_workspace_bytes bytes, to reuse one)."""
+    _cuda(log_probs, lengths)
+    if log_probs.dim() != 3 or log_probs.dtype != torch.float32:
+        raise L.OtransHipError('ctc_prefix_beam_search: log_probs must be f32 [B, T, V], got %s %s'
+                               % (log_probs.dtype, tuple(log_probs.shape)))
+    B, T, V = log_probs.shape
+    W, K = int(beam_width), min(int(cutoff_top_n), V)
+    lib = L.load()
+    lp = log_probs if log_probs.stride(2) == 1 and log_probs.stride(0) == T * log_probs.stride(1) else log_probs.contiguous()
+    ln = lengths.to(torch.int32).contiguous()
+    dev = log_probs.device
+    need = lib.otr_ctc_beam_workspace_bytes(B, T, W)
+    if need < 0 or not 0 <= blank < V:            # refused before the first launch (the library checks everything again)
+        raise L.OtransHipError('ctc_prefix_beam_search: bad arguments B=%d T=%d beam_width=%d blank=%d V=%d' % (B, T, W, blank, V))
+    top_lp = torch.empty((B * T, K), dtype=torch.float32, device=dev)
+    top_tok = torch.empty((B * T, K), dtype=torch.int32, device=dev)
+    if workspace is None:
+        workspace = torch.empty(need // 8, dtype=torch.int64, device=dev)
+    tokens = torch.empty((B, W, T), dtype=torch.int64, device=dev)
+    out_len = torch.empty((B, W), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, W), dtype=torch.float32, device=dev)
+    L.check(lib.otr_ctc_topk(_p(lp), lp.stride(1), _p(ln), B, T, V, K, _p(top_lp), _p(top_tok), _stream()), 'otr_ctc_topk')
+    L.check(lib.otr_ctc_beam_search(_p(top_lp), _p(top_tok), _p(ln), B, T, V, K, blank, W, _p(workspace),
+                                    workspace.numel() * workspace.element_size(), _p(tokens), _p(out_len), _p(scores), _stream()),
+            'otr_ctc_beam_search')
+    return tokens, out_len, scores

@@ -793,15 +793,22 @@ class CachedBeamState:
 
 
 class CTCRecognizer(Recognizer):
-    """recognize/ctc.py:7-58, greedy mode (the 'beam' mode needs the un-vendored ctcdecode_edited:
-    SURVEY.md 8c, out of scope).  `model` must expose frontend / encoder / assistor."""
+    """recognize/ctc.py:7-67.  `model` must expose frontend / encoder / assistor.
+    mode 'greedy': per-frame arg-max, repeats and blanks collapsed.  mode 'beam': CTC prefix beam search on the device
+    (ops.ctc_prefix_beam_search; cutoff_top_n defaults to 40 as in ctcdecode.CTCBeamDecoder) in place of the reference's ctcdecode_edited; the
+    1-best of the beam.  The two differ in general, also at beam_width 1: the beam sums the probability of every path of a prefix,
+    greedy follows the single best path.  There is no KenLM here, so ngram_lm must be None; alpha / beta are then unused, as in
+    ctcdecode without a scorer, and lm / lm_weight are unused in beam mode as in the reference."""
 
     def __init__(self, model, lm=None, lm_weight=0.1, ngram_lm=None, beam_width=5, idx2unit=None, ngpu=1,
-                 mode='greedy', alpha=0.1, beta=0.0):
+                 mode='greedy', alpha=0.1, beta=0.0, cutoff_top_n=40):
         super().__init__(model, idx2unit, lm, lm_weight, ngpu)
-        if mode != 'greedy':
-            raise NotImplementedError("CTCRecognizer mode '%s': only 'greedy' is built" % mode)
+        if mode not in ('greedy', 'beam'):
+            raise NotImplementedError("CTCRecognizer mode '%s': 'greedy' and 'beam' are built" % mode)
+        if mode == 'beam' and ngram_lm is not None:
+            raise NotImplementedError('CTCRecognizer: n-gram LM scoring (KenLM) is not built; use ngram_lm=None')
         self.beam_width, self.mode = beam_width, mode
+        self.alpha, self.beta, self.cutoff_top_n = alpha, beta, cutoff_top_n
 
     @torch.no_grad()
     def recognize_greedy(self, inputs, inputs_mask):
@@ -826,7 +833,19 @@ class CTCRecognizer(Recognizer):
             results.append(pred)
         return results
 
+    @torch.no_grad()
+    def recognize_beam(self, inputs, inputs_mask):
+        x, mask, _ = self.model.frontend.inference(inputs, inputs_mask, None)
+        memory, memory_mask, _ = self.model.encoder(x, mask)
+        log_probs, length = self.model.assistor.inference(memory, memory_mask)      # look-ahead conv + log_softmax, f32
+        tokens, out_len, _ = ops.ctc_prefix_beam_search(log_probs, length, beam_width=self.beam_width, cutoff_top_n=self.cutoff_top_n,
+                                                        blank=self.model.assistor.blank)
+        best, n = tokens[:, 0].cpu(), out_len[:, 0].cpu()
+        return [best[b, :int(n[b])].tolist() for b in range(best.size(0))]
+
     def recognize(self, inputs, inputs_mask):
+        if self.mode == 'beam':
+            return self.translate(self.recognize_beam(inputs, inputs_mask))
         return self.translate(self.recognize_greedy(inputs, inputs_mask))
 
 
