@@ -729,6 +729,41 @@ int32_t otr_decode_lookup(const int64_t* preds, int64_t ldp, const int32_t* pos,
                           int32_t d, int32_t vocab, void* stream);
 int32_t otr_lstm_cell(const float* gates_a, const float* gates_b, const float* bias_b, const float* c_prev, float* h, void* h_bf16,
                       float* c, int64_t rows, int32_t hidden, void* stream);
+/* ---- training the recurrent LM: nn.LSTM forward with saved activations, and backpropagation through time (csrc/lstm.hip).
+ * Per layer the caller computes gx = X W_ih^T + b_ih for all T steps at once (otr_linear_fwd), stored TIME-MAJOR [T, B, 4H], then
+ * runs one step launch per t; the weight gradients are GEMMs over the saved dG [T, B, 4H] afterwards (dW_hh = sum_t dG_t^T h_{t-1},
+ * dW_ih = dG^T X, db_ih = db_hh = column sums of dG, dX = dG W_ih).  Gate order i | f | g | o; act holds the activations
+ * (sigmoid(i), sigmoid(f), tanh(g), sigmoid(o)) [B, 4H] f32; h, c [B, H] f32.
+ *  dtype: OTR_F32 (f32 operands, exact-f32 MFMA) or this build's 16-bit code (16-bit operands, f32 accumulate).  "CT" below is that
+ *  type: h_prev, dg_next and dg are CT; in f32 mode h_prev is the previous step's f32 h and h_bf16 is NULL.
+ * Limits of the fused step kernels (otr_lstm_step_supported says whether a shape is inside): 1 <= rows (the batch) <=
+ * OTR_LSTM_MAX_ROWS, hidden a multiple of OTR_LSTM_HIDDEN_MULT and <= OTR_LSTM_MAX_HIDDEN; h_prev, dg_next and the packs 16-byte
+ * aligned.  Other shapes take the unfused route: the recurrent products as otr_linear_fwd / otr_linear_dgrad calls per step and the
+ * elementwise otr_lstm_cell_fwd / otr_lstm_cell_bwd, which have no shape limit.
+ * otr_lstm_pack_whh: W_hh [4H, H] f32 -> fwd_pack and/or bwd_pack (either may be NULL), 4H*H elements of CT each, in the MFMA
+ *   fragment order the step kernels read (per block of 16 hidden units: its four gate rows / its 16 columns).  A pack is a copy:
+ *   make it again after every change of W_hh.
+ * otr_lstm_fwd_step:  z = gx_t [B,4H] + bias [4H] (NULL: none; pass b_hh) + h_prev W_hh^T (h_prev NULL = zero state, no product);
+ *   act = activations of z; c = act_f c_prev + act_i act_g (c_prev NULL = zeros); h = act_o tanh(c), h_bf16 its 16-bit twin (NULL: none).
+ * otr_lstm_bwd_step:  dh = dy [B,H] + dg_next W_hh (dg_next NULL: the last step, no product); dc = dh act_o (1 - tanh^2 c) + dc_in
+ *   (dc_in NULL = zeros); dg = (dc act_g act_i(1-act_i), dc c_prev act_f(1-act_f), dc act_i (1-act_g^2), dh tanh(c) act_o(1-act_o));
+ *   dc_out = dc act_f.  dc_in and dc_out may be the same buffer.
+ * otr_lstm_cell_fwd / otr_lstm_cell_bwd: the same cell maths on `rows` rows, with the recurrent product given as gh [rows,4H] /
+ *   dh_rec [rows,H] (NULL: none). */
+#define OTR_LSTM_MAX_ROWS 64
+#define OTR_LSTM_HIDDEN_MULT 64
+#define OTR_LSTM_MAX_HIDDEN 2048
+int32_t otr_lstm_step_supported(int64_t rows, int32_t hidden);
+int32_t otr_lstm_pack_whh(const float* w_hh, void* fwd_pack, void* bwd_pack, int32_t dtype, int32_t hidden, void* stream);
+int32_t otr_lstm_fwd_step(const float* gx, const float* bias, const void* h_prev, const float* c_prev, const void* fwd_pack, float* h,
+                          void* h_bf16, float* c, float* act, int32_t dtype, int64_t rows, int32_t hidden, void* stream);
+int32_t otr_lstm_bwd_step(const float* dy, const void* dg_next, const void* bwd_pack, const float* act, const float* c,
+                          const float* c_prev, const float* dc_in, float* dc_out, void* dg, int32_t dtype, int64_t rows, int32_t hidden,
+                          void* stream);
+int32_t otr_lstm_cell_fwd(const float* gx, const float* gh, const float* bias, const float* c_prev, float* h, void* h_bf16, float* c,
+                          float* act, int64_t rows, int32_t hidden, void* stream);
+int32_t otr_lstm_cell_bwd(const float* dy, const float* dh_rec, const float* act, const float* c, const float* c_prev,
+                          const float* dc_in, float* dc_out, void* dg, int32_t dtype, int64_t rows, int32_t hidden, void* stream);
 int32_t otr_decode_self_attention(const void* qkv, void* kcache, void* vcache, const int32_t* anc, const int32_t* pos,
                                   void* out, int32_t dtype, int64_t rows, int32_t H, int32_t dk, int32_t maxlen,
                                   float scale, void* stream);

@@ -206,6 +206,12 @@ SIGNATURES = {
     'otr_decode_embed': [_P, _I64, _P, _P, _P, _P, _I64, _I32, _I32, _F32, _P],
     'otr_decode_lookup': [_P, _I64, _P, _P, _P, _P, _I64, _I32, _I32, _P],
     'otr_lstm_cell': [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P],
+    'otr_lstm_step_supported': [_I64, _I32],
+    'otr_lstm_pack_whh': [_P, _P, _P, _I32, _I32, _P],
+    'otr_lstm_fwd_step': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I64, _I32, _P],
+    'otr_lstm_bwd_step': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I64, _I32, _P],
+    'otr_lstm_cell_fwd': [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P],
+    'otr_lstm_cell_bwd': [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I64, _I32, _P],
     'otr_decode_self_attention': [_P, _P, _P, _P, _P, _P, _I32, _I64, _I32, _I32, _I32, _F32, _P],
     'otr_residual_add_fwd': [_P, _P, _I32, _P, _I64, _F32, _F32, _P, C.c_uint64, _P],
     'otr_residual_add_bwd': [_P, _P, _I32, _I64, _F32, _F32, _P, C.c_uint64, _P],

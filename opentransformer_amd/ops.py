@@ -2666,6 +2666,179 @@ def lstm_cell(gates_a, gates_b, bias_b, c_prev):
     return attach_lp(h, hlp), c
 
 
+# ---------------------------------------------------------------------------------------- recurrent LM training
+# nn.Embedding -> nn.LSTM -> Linear with a backward pass (model/lm.py:63-70).  Sequences run TIME-MAJOR ([T, B, ...]) so that each
+# step's rows are contiguous; see include/otrans_hip.h (otr_lstm_*) for the kernels and their limits.
+_LSTM_FUSED = True      # tests flip it: the unfused route (per-step GEMMs + otr_lstm_cell_fwd / _bwd) also on shapes the step kernels take
+
+
+def lstm_fused_applies(rows, hidden):
+    """True when one layer's steps run on the fused step kernels (otr_lstm_fwd_step / otr_lstm_bwd_step) for this batch / width"""
+    return _LSTM_FUSED and bool(L.load().otr_lstm_step_supported(rows, hidden))
+
+
+def _lstm_code():
+    return _code(half_dtype()) if is_half() else L.OTR_F32
+
+
+def lstm_pack_whh(w_hh, fwd=True, bwd=True):
+    """(fwd_pack, bwd_pack) of W_hh [4H, H] f32 in the compute type (otr_lstm_pack_whh); made from the weight as it is NOW"""
+    H = w_hh.shape[1]
+    cdt = half_dtype() if is_half() else torch.float32
+    f = torch.empty((4 * H * H,), dtype=cdt, device=w_hh.device) if fwd else None
+    b = torch.empty((4 * H * H,), dtype=cdt, device=w_hh.device) if bwd else None
+    L.check(L.load().otr_lstm_pack_whh(_p(w_hh.detach().contiguous()), _p(f), _p(b), _lstm_code(), H, _stream()), 'otr_lstm_pack_whh')
+    return f, b
+
+
+class EmbeddingFn(torch.autograd.Function):
+    """nn.Embedding: y[r] = E[tok[r]] (otr_decode_lookup, with the 16-bit twin).  Backward: dE[tok[r]] += dy[r] (otr_embed_bwd, scale 1),
+    into the in-place gradient buffer when there is one.  The adds are atomic f32, so where a token occurs more than once the order
+    of its sum -- and the last bits of the embedding gradient (the tied output weight's too) -- is not deterministic."""
+
+    @staticmethod
+    def forward(ctx, tokens, E):
+        _cuda(tokens, E)
+        tok = tokens.reshape(-1, 1).contiguous()
+        R = tok.shape[0]
+        V, d = E.shape
+        y = torch.empty((R, d), dtype=torch.float32, device=E.device)
+        ylp = torch.empty((R, d), dtype=half_dtype(), device=E.device) if is_half() else None
+        L.check(L.load().otr_decode_lookup(_p(tok), 1, None, _p(E), _p(y), _p(ylp), R, d, V, _stream()), 'otr_decode_lookup')
+        ctx.save_for_backward(tok)
+        ctx.e_ref = E
+        if ylp is not None:
+            ctx.mark_non_differentiable(ylp)
+        shape = tuple(tokens.shape) + (d,)
+        return y.view(shape), (ylp.view(shape) if ylp is not None else None)
+
+    @staticmethod
+    def backward(ctx, dy, _dylp=None):
+        (tok,) = ctx.saved_tensors
+        E = ctx.e_ref
+        V, d = E.shape
+        gt = grad_target(E)
+        dE = gt if gt is not None else torch.zeros((V, d), dtype=torch.float32, device=E.device)
+        L.check(L.load().otr_embed_bwd(_p(tok), _p(dy.contiguous().float()), _p(dE), tok.shape[0], d, V, 1.0, _stream()), 'otr_embed_bwd')
+        return None, (None if gt is not None else dE)
+
+
+def embedding(tokens, E):
+    y, ylp = EmbeddingFn.apply(tokens, E)
+    return attach_lp(y, ylp)
+
+
+class LstmLayerFn(torch.autograd.Function):
+    """One nn.LSTM layer (gate order i | f | g | o) over a time-major sequence from the zero state, with backpropagation through time.
+    x [T, B, Hin] f32 (16-bit twin used when attached) -> (h [T, B, H] f32, its 16-bit twin or None).
+
+    Forward: gx = X W_ih^T + b_ih for all steps in one GEMM, then T step launches (b_hh is added there).  Saved for backward: the GEMM
+    operand of X, h (operand form), c and the gate activations of every step -- gx is not kept.  Backward: T step launches from t = T-1
+    down to 0 write dG [T, B, 4H] (compute type), then dW_hh = sum_t dG_t^T h_{t-1}, dW_ih = dG^T X, db_ih = db_hh = column sums of
+    dG and dX = dG W_ih are GEMMs of the existing launches (deferred into the grouped weight-gradient launch where that is on).
+    W_hh's packs are made from the weight inside each call (forward pack in forward, backward pack in backward): never stale."""
+
+    @staticmethod
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh):
+        _cuda(x, w_ih, w_hh)
+        T, B, Hin = x.shape
+        H = w_hh.shape[1]
+        half = is_half()
+        cdt = half_dtype() if half else torch.float32
+        code = _lstm_code()
+        x2 = lp_of(x) if half else None
+        if x2 is None:
+            x2 = cast_bf16(x) if half else x
+        x2 = x2.contiguous().view(T * B, Hin)
+        wi = weight_lp(w_ih) if half else w_ih
+        gx = linear_fwd_raw(x2, wi, b_ih, torch.float32)                     # [T*B, 4H], time-major
+        dev = x.device
+        hs = torch.empty((T, B, H), dtype=torch.float32, device=dev)
+        hs16 = torch.empty((T, B, H), dtype=cdt, device=dev) if half else None
+        cs = torch.empty((T, B, H), dtype=torch.float32, device=dev)
+        acts = torch.empty((T, B, 4 * H), dtype=torch.float32, device=dev)
+        hop = hs16 if half else hs                                           # h in its GEMM-operand form
+        fused = lstm_fused_applies(B, H)
+        lib, st = L.load(), _stream()
+        bhh = b_hh.detach().contiguous()
+        if fused:
+            wf, _ = lstm_pack_whh(w_hh, bwd=False)
+        else:
+            wh = weight_lp(w_hh) if half else w_hh
+        for t in range(T):
+            hp, cp = (hop[t - 1], cs[t - 1]) if t else (None, None)
+            if fused:
+                L.check(lib.otr_lstm_fwd_step(_p(gx, t * B * 4 * H), _p(bhh), _p(hp), _p(cp), _p(wf), _p(hs[t]), _p(hs16[t] if half else None),
+                                              _p(cs[t]), _p(acts[t]), code, B, H, st), 'otr_lstm_fwd_step')
+            else:
+                gh = linear_fwd_raw(hp, wh, None, torch.float32) if t else None
+                L.check(lib.otr_lstm_cell_fwd(_p(gx, t * B * 4 * H), _p(gh), _p(bhh), _p(cp), _p(hs[t]), _p(hs16[t] if half else None),
+                                              _p(cs[t]), _p(acts[t]), B, H, st), 'otr_lstm_cell_fwd')
+        ctx.save_for_backward(x2, w_ih, w_hh, hop, cs, acts)
+        ctx.fused, ctx.cdt, ctx.code, ctx.dims = fused, cdt, code, (T, B, Hin, H)
+        ctx.w_refs = (w_ih, w_hh, b_ih, b_hh)
+        if half:
+            ctx.mark_non_differentiable(hs16)
+        return hs, hs16
+
+    @staticmethod
+    def backward(ctx, dy, _dy16=None):
+        x2, w_ih, w_hh, hop, cs, acts = ctx.saved_tensors
+        T, B, Hin, H = ctx.dims
+        half, code, cdt = is_half(), ctx.code, ctx.cdt
+        dev = dy.device
+        dy = dy.contiguous().float()
+        dG = torch.empty((T, B, 4 * H), dtype=cdt, device=dev)
+        dc = torch.empty((B, H), dtype=torch.float32, device=dev)
+        lib, st = L.load(), _stream()
+        if ctx.fused:
+            _, wb = lstm_pack_whh(w_hh, fwd=False)
+        else:
+            wh = weight_lp(w_hh) if half else w_hh
+        for t in range(T - 1, -1, -1):
+            dgn = dG[t + 1] if t < T - 1 else None
+            dcin = dc if t < T - 1 else None
+            cp = cs[t - 1] if t else None
+            if ctx.fused:
+                L.check(lib.otr_lstm_bwd_step(_p(dy[t]), _p(dgn), _p(wb), _p(acts[t]), _p(cs[t]), _p(cp), _p(dcin), _p(dc), _p(dG[t]),
+                                              code, B, H, st), 'otr_lstm_bwd_step')
+            else:
+                dhr = linear_dgrad_raw(dgn, wh, torch.float32) if dgn is not None else None
+                L.check(lib.otr_lstm_cell_bwd(_p(dy[t]), _p(dhr), _p(acts[t]), _p(cs[t]), _p(cp), _p(dcin), _p(dc), _p(dG[t]), code, B, H,
+                                              st), 'otr_lstm_cell_bwd')
+        dG2 = dG.view(T * B, 4 * H)
+        w_ih_ref, w_hh_ref, b_ih_ref, b_hh_ref = ctx.w_refs
+        wi = weight_lp(w_ih) if half else w_ih
+        dx = linear_dgrad_raw(dG2, wi, torch.float32).view(T, B, Hin) if ctx.needs_input_grad[0] else None
+        dw_ih = dw_hh = db_ih = db_hh = None
+        if ctx.needs_input_grad[1]:
+            gt = grad_target(w_ih_ref)
+            dw_ih = linear_wgrad_raw(dG2, x2, wi, out=gt)
+            dw_ih = None if gt is not None else dw_ih
+        if ctx.needs_input_grad[2]:
+            gt = grad_target(w_hh_ref)
+            if T > 1:
+                dw_hh = linear_wgrad_raw(dG[1:].reshape((T - 1) * B, 4 * H), hop[:T - 1].reshape((T - 1) * B, H), w_hh, out=gt)
+            elif gt is None:
+                dw_hh = torch.zeros_like(w_hh)
+            dw_hh = None if gt is not None else dw_hh
+        for i, ref in ((3, b_ih_ref), (4, b_hh_ref)):
+            if ctx.needs_input_grad[i]:
+                gt = grad_target(ref)
+                db = colsum_raw(dG2, out=gt) if gt is not None else colsum_raw(dG2)
+                if i == 3:
+                    db_ih = None if gt is not None else db
+                else:
+                    db_hh = None if gt is not None else db
+        return dx, dw_ih, dw_hh, db_ih, db_hh
+
+
+def lstm_layer(x, w_ih, w_hh, b_ih, b_hh):
+    """one nn.LSTM layer with autograd over x [T, B, Hin] (time-major) from the zero state -> h [T, B, H] with its 16-bit twin"""
+    h, hlp = LstmLayerFn.apply(x, w_ih, w_hh, b_ih, b_hh)
+    return attach_lp(h, hlp)
+
+
 def decode_self_attention(qkv, kcache, vcache, anc, pos, n_heads):
     """New-position query against the ancestors' cached keys/values (include/otrans_hip.h)."""
     _cuda(qkv, kcache, vcache, anc, pos)

@@ -77,8 +77,8 @@ class RecurrentLanguageModel(nn.Module):
     the reference hands it the LAST token of every hypothesis with no carried state (recognize/speech2text.py:102-105 passes
     cache['lm'], which is never set) -- `logits_last`.  `predict` is the reference's general form (any prefix length, optional
     state).  The cell runs as two otr_linear_fwd GEMMs + otr_lstm_cell per layer and step; `self.rnn` only holds the parameters.
-    Training this LM (model/lm.py:63-70 through nn.LSTM's backward) is not part of the speech path: forward()
-    evaluates the loss without building a graph."""
+    forward() with a gradient wanted trains it (_train_forward: the otr_lstm_* step kernels and backpropagation through time);
+    without one it evaluates the loss on the inference path above."""
 
     def __init__(self, params):
         super().__init__()
@@ -146,11 +146,29 @@ class RecurrentLanguageModel(nn.Module):
 
     def forward(self, inputs, targets):
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise NotImplementedError('opentransformer_amd: training the recurrent LM (nn.LSTM backward) is outside the speech hot path '
-                                      '(SURVEY.md section 8); evaluate it under torch.no_grad()')
+            return self._train_forward(inputs['inputs'], targets['targets'])
         y, _ = self._run(inputs['inputs'], None)
         logits = ops.linear(y, self.output_project.weight, self.output_project.bias)
         return self.crit(logits, targets['targets']), None
+
+    def _train_forward(self, tokens, target):
+        """model/lm.py:63-70 with a backward pass: the sequence runs time-major (one contiguous [B, H] slice per step) through
+        ops.embedding -> ops.lstm_layer per layer (nn.LSTM's dropout on the output of every layer but the last, off in eval()) ->
+        output_project -> the label-smoothing loss.  Like the reference, nothing is packed: the LSTM runs over the PAD tail and only
+        the loss masks it.  The fp16 loss scale registered by FusedAdam rides in the loss launch's gradient."""
+        T = tokens.shape[1]
+        x = ops.embedding(tokens.t(), self.embedding.weight)                 # [T, B, H]
+        p = float(self.params['dropout'])
+        for k in range(self.num_layers):
+            if k:
+                x = ops.dropout(x, p, self.training)
+            x = ops.lstm_layer(x, *self._layer_params(k))
+        logits = ops.linear(x, self.output_project.weight, self.output_project.bias)
+        self.crit._otr_grad_scale = ops.loss_scale_of(self)
+        try:
+            return self.crit(logits, target.t()), None
+        finally:
+            self.crit._otr_grad_scale = None
 
     def save_checkpoint(self, params, name):
         torch.save({'params': params, 'model': self.state_dict()}, name)

@@ -118,11 +118,20 @@ def lm_config(vocab_size, d_model=256, n_heads=4, d_ff=2048, num_blocks=4):
                 smoothing=0.1)
 
 
-def rnn_lm_config(vocab_size, hidden_size=256, num_layers=2):
-    """a `rnn_lm` model section (model/lm.py:33-60: vocab_size, hidden_size, num_layers, dropout, share_embedding, smoothing); the
-    reference ships no yaml for it -- sizes follow transformer_lm.yaml's width"""
-    return dict(type='recurrent_lm', vocab_size=vocab_size, hidden_size=hidden_size, num_layers=num_layers, dropout=0.0,
+def rnn_lm_config(vocab_size, hidden_size=256, num_layers=2, dropout=0.0):
+    """a `rnn_lm` model section (model/lm.py:33-60: vocab_size, hidden_size, num_layers, dropout, share_embedding, smoothing) at
+    test sizes; the reference's own sizes are in egs/aishell/conf/rnnlm.yaml -- rnn_lm_yaml_config()"""
+    return dict(type='recurrent_lm', vocab_size=vocab_size, hidden_size=hidden_size, num_layers=num_layers, dropout=dropout,
                 share_embedding=True, smoothing=0.1)
+
+
+def rnn_lm_yaml_config():
+    """the model section of egs/aishell/conf/rnnlm.yaml"""
+    return rnn_lm_config(4233, hidden_size=1024, num_layers=2, dropout=0.1)
+
+
+# the training section of egs/aishell/conf/rnnlm.yaml (Adam, gradient clipping by norm)
+RNN_LM_YAML_OPTIM = dict(lr=1e-3, betas=(0.9, 0.98), eps=1e-9, weight_decay=1e-6, clip_grad=5.0, batch_size=16)
 
 
 def fill_state_dict_(sd, seed=1234):
