@@ -6,7 +6,7 @@ frontend.input_size 80, residual_dropout 0.1, synthetic 80-d fbank x 1000 frames
 B = 32 utterances per GPU, 16-bit MFMA operands / fp32 accumulate.  One step = zero grads, forward, backward,
 ONE gradient all-reduce (N>1), clip + Adam + Noam update: nothing is skipped in the timed region.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 --dump-outputs DIR writes what the last of the K timed steps computed as DIR/<name>.npy (train: loss.npy, params.npy and
 grads.npy -- a fixed seeded sample of 2^20 of the updated parameters and of their gradients --, optimizer.npy; decode: hyps.npy,
@@ -17,7 +17,12 @@ N > 1 without a torchrun environment re-launches itself as `python -m torch.dist
 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same flags>` (one rank per GPU over RCCL); under
 torchrun it reads RANK / LOCAL_RANK / WORLD_SIZE as usual.
 
-Prints ONE JSON line (rank 0) following the driver's contract, plus
+A plain run sets up, warms up, times the K steps, writes its outputs (--dump-outputs) and prints ONE JSON line (rank 0):
+metric, value, unit, higher_is_better, dtype, ms_per_step and the configuration.  --full also measures, after the timed steps
+(--task decode: the CPU baseline alone),
+  windows       five further windows of K steps, timed like the timed region;
+  step_breakdown  forward + backward against all-reduce + optimizer, from events; at N > 1 also the collective on its own and
+                the step without collectives and with a bf16 gradient payload;
   roofline      the kernel with the largest share of the training step (launches x duration; today the fused FFN backward),
                 its launch re-timed back to back inside a hipGraph with events on the launch stream, FLOPs / duration against
                 the 16-bit MFMA peak, HBM traffic and MFMA-busy share from the committed --pmc passes; `roofline_kernels`
@@ -65,9 +70,12 @@ def parse():
     ap.add_argument('--task', default='train', choices=['train', 'decode'],
                     help='train = the metric (BASELINE configs[1]); decode = configs[4] (C5): batch beam search + LM fusion, one GPU')
     ap.add_argument('--no-graph', action='store_true', help='launch eagerly instead of replaying a hipGraph')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='timed region only (profiler runs): no breakdown, no roofline, no bf16 line')
-    ap.add_argument('--no-bf16-line', action='store_true', help='skip the secondary bf16 measurement of the same workload')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure the windows, step breakdown, roofline, bf16 line and CPU baseline '
+                         '(decode: the CPU baseline); a plain run times the contract region alone')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: no windows, step breakdown, roofline or bf16 line')
+    ap.add_argument('--no-bf16-line', action='store_true', help='with --full: skip the secondary bf16 measurement of the same workload')
     ap.add_argument('--overlap', default='auto', choices=['auto', 'on', 'off'],
                     help='off = ONE gradient all-reduce per step behind the backward pass (what north_star states; the form at N = 1).  '
                          'on = staged step: the backward pass is cut at the encoder / decoder boundary into two hipGraphs, and between '
@@ -337,7 +345,7 @@ def decode_task(args):
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     argv = ['--mode', args.mode, '--iters', str(args.steps), '--warmup', str(args.warmup)]
-    if args.no_cpu_baseline:
+    if args.no_cpu_baseline or not args.full:
         argv.append('--no-cpu-baseline')
     outputs = {} if args.dump_outputs else None
     mod.main(argv, outputs=outputs)
@@ -519,19 +527,20 @@ def main():
     used_graph = graph is not None
     elapsed = timed(step, args.warmup, args.steps)
 
-    # ---- untimed extras: where the step time goes (every rank: the collectives must match)
+    # ---- --full, untimed: where the step time goes (every rank: the collectives must match)
     final_loss, final_stats = float(loss_buf.item()), opt.stats()      # state at the end of the timed region
     if args.dump_outputs and rank == 0:       # before the extras below run more steps on the same replica
         dump_outputs(args.dump_outputs, train_step_outputs(run, final_loss))
+    extras = args.full and not args.no_extras
     parts = {}
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
     windows = None
-    if not args.no_extras:
+    if extras:
         # box-to-box and run-to-run spread is ~1.5 %: besides the contract's K steps (`value`), five more windows of K steps each,
         # timed the same way (barrier + synchronize on both sides, max over ranks); their median is the robust figure
         windows = [timed(step, 0, args.steps) / args.steps * 1e3 for _ in range(5)]
         final_loss, final_stats = float(loss_buf.item()), opt.stats()
-    if not args.no_extras:
+    if extras:
         acc = [0.0, 0.0]
         for _ in range(5):
             ev[0].record()
@@ -548,7 +557,7 @@ def main():
         if run['whole'] and graph is not None:
             parts = {'whole_step_graph_ms': acc[0] / 5,
                      'note': 'N = 1: forward, backward and the optimizer launches are ONE hipGraph (--opt-in-graph off separates them)'}
-    if world > 1 and not args.no_extras:     # the collective on its own: 5 all-reduces of the flat gradient buffer, events on the stream
+    if world > 1 and extras:     # the collective on its own: 5 all-reduces of the flat gradient buffer, events on the stream
         ev[0].record()
         for _ in range(5):
             dp.all_reduce_gradients()
@@ -581,7 +590,7 @@ def main():
         ops.set_stage_split(run['overlap'])
         ops.set_compute_dtype(args.mode)
     kern = None
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and extras:
         dp.skip_collectives = True            # rank 0 alone runs this pass: it must not start a collective (staged step: the early group's)
         try:
             kern = instrumented_step(ops, fwd_bwd, args.mode)
@@ -616,7 +625,8 @@ def main():
                               'skipped' % (int(st['faults']), int(st['skipped'])))
         elif st['skipped'] != 0 or not (st['grad_sqnorm'] == st['grad_sqnorm'] and st['grad_sqnorm'] < float('inf')):
             out['INVALID'] = 'non-finite gradient norm: %d optimizer updates were skipped' % int(st['skipped'])
-        out['step_breakdown'] = parts
+        if parts:
+            out['step_breakdown'] = parts
         if windows:
             ws_ = sorted(windows)
             out['windows'] = {'ms_per_step': windows, 'median_ms_per_step': ws_[len(ws_) // 2],
@@ -744,7 +754,7 @@ def main():
     #      4e-3 from the fp32 reference, outside the north star's 1e-3 -- why the headline value is the fp16 line).  Every rank
     #      takes part (the step holds the collective); after the replays above, which need the primary mode's operands
     bf16_line = None
-    if args.mode != 'bf16' and args.model == 'transformer' and not (args.no_extras or args.no_bf16_line):
+    if args.mode != 'bf16' and args.model == 'transformer' and extras and not args.no_bf16_line:
         overlap_primary = run['overlap']
         del run, dp, opt, fwd_bwd, run_fwd_bwd, step, graph, kern    # free the primary replica (graph pool, 2.2 GB of saved activations)
         torch.cuda.empty_cache()
@@ -775,7 +785,7 @@ def main():
             out['bf16'] = bf16_line
         if args.model != 'transformer':
             out['config']['workload'] = out['config']['workload'].replace('transformer_baseline.yaml (+input_size 80), 12 enc / 6 dec layers', 'conformer_baseline.yaml, 12 conformer blocks / 6 dec layers')
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(args)
         print(json.dumps(out))
     if world > 1:

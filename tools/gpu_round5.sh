@@ -25,7 +25,7 @@ tests|smoke|bench|benchq|trace|conformer|newtests)
 two)
   # the N > 1 control flow of bench.py end to end on ONE GPU: two ranks on cuda:0, collectives over gloo (numbers mean nothing)
   OTR_BENCH_ONE_GPU=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 \
-      bench.py --gpus 2 --steps 4 --warmup 2 --calib-steps 3 --no-cpu-baseline > $OUT/bench_2rank_onegpu_gloo.log 2>&1; echo "two-rank exit $?"
+      bench.py --gpus 2 --steps 4 --warmup 2 --calib-steps 3 --full --no-cpu-baseline > $OUT/bench_2rank_onegpu_gloo.log 2>&1; echo "two-rank exit $?"
   grep '^{' $OUT/bench_2rank_onegpu_gloo.log | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print(json.dumps({k:d.get(k) for k in ('value','n_gpus','ms_per_step','step_breakdown','INVALID')})[:1500])" ;;

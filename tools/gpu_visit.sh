@@ -19,10 +19,10 @@ newtests)
 smoke)
   timeout 200 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke exit $?"; grep -v amdgpu.ids $OUT/smoke.log | tail -3 ;;
 bench)
-  timeout 600 python bench.py --steps 20 --warmup 5 > $OUT/bench.log 2> $OUT/bench.err; echo "bench exit $?"
+  timeout 600 python bench.py --steps 20 --warmup 5 --full > $OUT/bench.log 2> $OUT/bench.err; echo "bench exit $?"
   grep '^{' $OUT/bench.log | tail -1 > $OUT/bench.json; cut -c1-400 $OUT/bench.json; tail -3 $OUT/bench.err | cut -c1-300 ;;
 benchq)
-  timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-bf16-line > $OUT/benchq.log 2> $OUT/benchq.err; echo "benchq exit $?"
+  timeout 300 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-bf16-line > $OUT/benchq.log 2> $OUT/benchq.err; echo "benchq exit $?"
   grep '^{' $OUT/benchq.log | tail -1 > $OUT/benchq.json; cut -c1-300 $OUT/benchq.json; tail -3 $OUT/benchq.err | cut -c1-300 ;;
 pmc)
   bash tools/gpu_pmc_step.sh $TAG ;;
@@ -36,7 +36,7 @@ ffn)
   tail -15 $OUT/ffn_test.log | cut -c1-300
   timeout 300 python tools/ffn_bench.py --mode fp16 > $OUT/ffn_bench.log 2>&1; echo "ffn bench exit $?"; grep -v amdgpu.ids $OUT/ffn_bench.log | tail -3 | cut -c1-1500 ;;
 conformer)
-  timeout 300 python bench.py --model conformer --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_conformer.log 2>&1; echo "conformer exit $?"
+  timeout 300 python bench.py --model conformer --steps 10 --warmup 3 --full --no-cpu-baseline > $OUT/bench_conformer.log 2>&1; echo "conformer exit $?"
   grep '^{' $OUT/bench_conformer.log | tail -1 | cut -c1-300 ;;
 *) echo "unknown step $what" ;;
 esac
