@@ -693,6 +693,50 @@ int32_t otr_ctc_beam_search(const float* top_lp, const int32_t* top_tok, const i
                             int32_t K, int32_t blank, int32_t W, void* workspace, int64_t ws_bytes, int64_t* tokens,
                             int32_t* out_len, float* scores, void* stream);
 
+/* ---- joint CTC/attention beam search (SpeechToTextRecognizer joint_ctc=True; Watanabe et al. 2017, Algorithm 2; ESPnet's
+ *      CTCPrefixScore), csrc/ctcscore.hip.  f32 in every build.  lambda = ctc_weight in [0, 1]; x_t(c) = log_probs of token c at frame
+ *      t of the utterance, T_b = lengths[b] clamped to [1, T']; "+" of probabilities is log-add-exp, "*" is +.  BOS = EOS.
+ * Prefix state: every hypothesis g carries r^n_t(g), r^b_t(g) for t < T_b and its prefix score psi(g).  The start prefix (BOS only):
+ *   r^n = -inf, r^b_t = sum_{tau <= t} x_tau(blank), psi = 0; it has no last token.
+ * Pre-beam (otr_joint_prebeam): per hypothesis the K' tokens of highest att_weight * log_softmax(att) + lm_weight * log_softmax(lm)
+ *   (att_weight = 1 - lambda; lm_logits NULL: no LM term), descending, ties -> lower token.  The log-softmaxes are formed exactly as
+ *   otr_beam_topk forms them.  cand_score f32 / cand_idx int32 [rows, K'].  V <= 8192, K' <= min(32, V).
+ * Prefix score of h = g.c (otr_ctc_prefix_score), per candidate of an unfinished hypothesis:
+ *   c == blank: psi(h) = -inf.   c == eos: psi(h) = r^n_{T_b-1}(g) + r^b_{T_b-1}(g).
+ *   otherwise: phi_t = r^b_t(g) + (c == last(g) ? -inf : r^n_t(g));  r^n_0(h) = x_0(c) if g is the start prefix else -inf,
+ *   r^b_0(h) = -inf;  for t = 1 .. T_b-1: r^n_t(h) = (r^n_{t-1}(h) + phi_{t-1}) * x_t(c), r^b_t(h) = (r^b_{t-1}(h) + r^n_{t-1}(h)) * x_t(blank);
+ *   psi(h) = r^n_0(h) + sum_{t=1}^{T_b-1} phi_{t-1} * x_t(c).  Frames t >= T_b are never read.
+ * Joint score (cand_score given): j = cand_score + lambda * (psi(h) - psi(g)); at lambda = 0 exactly cand_score (no CTC term, even where
+ *   psi is -inf); for lambda > 0, -inf where psi(h) or psi(g) is -inf (never NaN).  Each hypothesis keeps the `beam` best of its K'
+ *   candidates, descending, ties -> lower token, written in the layout otr_beam_prune reads: k_score f32 / k_idx int64 [rows, beam], plus
+ *   k_src int32 [rows, beam] = row * K' + candidate (the candidate's state slot).  A finished hypothesis (flags[row] != 0) does not
+ *   consult the CTC head: its k_score = -inf, k_idx = eos, k_src = -1 (the prune masks them).
+ * Prefix of row r: preds int64 [rows, ldp], BOS at column 0; the prefix has t columns (t = *pos + 1 where pos is given, the cached
+ *   search's device scalar; else the host t), last(g) = preds[r, t-1] when t > 1.  Hypothesis row r belongs to utterance
+ *   r / rows_per_utt.  log_probs f32 [B, T', V], frame (b, t) at log_probs + (b*T' + t)*ld; lengths int32 [B] on the device.
+ * State: slot s of a state buffer holds r^n / r^b f32 [slots, T'] (row s at s*T') and psi f32 [slots].  For t > 1 row r's parent state
+ *   is slot jsrc[r] of (rn_in, rb_in, psi_in); the launch writes every candidate's state to slot r*K' + k of (rn_out, rb_out, psi_out)
+ *   (rn_out / rb_out may both be NULL: psi only; frames t >= T_b are not written).  In and out buffers must differ (double-buffer them
+ *   per ping-pong phase like preds).  Limits: T' <= 2048, K' <= min(32, V), beam <= min(16, K').
+ * otr_beam_prune_joint / otr_beam_prune_cached_joint: otr_beam_prune / otr_beam_prune_cached plus jsrc_out[r'] = ksrc_in[the entry
+ *   r' came from] (-1 where its parent was finished): the state slot each survivor inherits, for the next step's jsrc. */
+int32_t otr_joint_prebeam(const float* logits, int64_t ld, const float* lm_logits, int64_t ld_lm, float att_weight, float lm_weight,
+                          int64_t rows, int32_t V, int32_t K, float* cand_score, int32_t* cand_idx, void* stream);
+int32_t otr_ctc_prefix_score(const float* log_probs, int64_t ld, const int32_t* lengths, int32_t B, int32_t T, int32_t V, int32_t blank,
+                             int32_t eos, int64_t rows, int32_t rows_per_utt, int32_t K, const int32_t* cand_idx, const float* cand_score,
+                             const uint8_t* flags, const int64_t* preds, int64_t ldp, int32_t t, const int32_t* pos, const int32_t* jsrc,
+                             const float* rn_in, const float* rb_in, const float* psi_in, float ctc_weight, float* rn_out, float* rb_out,
+                             float* psi_out, int32_t beam, float* k_score, int64_t* k_idx, int32_t* k_src, void* stream);
+int32_t otr_beam_prune_joint(const float* k_score, const int64_t* k_idx, const float* scores_in, const uint8_t* flag_in,
+                             const int64_t* preds_in, int64_t ldp, int32_t batch, int32_t beam, int32_t t, int32_t eos, float* scores_out,
+                             uint8_t* flag_out, int64_t* preds_out, int32_t* n_finished, const int32_t* ksrc_in, int32_t* jsrc_out,
+                             void* stream);
+int32_t otr_beam_prune_cached_joint(const float* k_score, const int64_t* k_idx, const float* scores_in, const uint8_t* flag_in,
+                                    const int64_t* preds_in, int64_t ldp, int32_t batch, int32_t beam, int32_t eos, const int32_t* pos_in,
+                                    int32_t* pos_out, const int32_t* anc_in, int32_t* anc_out, int32_t ld_anc, float* scores_out,
+                                    uint8_t* flag_out, int64_t* preds_out, int32_t* n_finished, const int32_t* ksrc_in, int32_t* jsrc_out,
+                                    void* stream);
+
 /* ---- transposed copies of many matrices in ONE launch (the W^T bf16 shadows that turn dx = dy.W into a
  *      forward-type GEMM; refreshed after every optimizer step).  table: DEVICE int64 [n_mats,4] rows of
  *      {element offset, rows, cols, first tile}; matrix i is src+offset [rows,cols] row-major and is written to

@@ -203,6 +203,11 @@ SIGNATURES = {
     'otr_ctc_beam_workspace_bytes': [_I32, _I32, _I32],
     'otr_ctc_topk': [_P, _I64, _P, _I32, _I32, _I32, _I32, _P, _P, _P],
     'otr_ctc_beam_search': [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P, _P, _P, _P],
+    'otr_joint_prebeam': [_P, _I64, _P, _I64, _F32, _F32, _I64, _I32, _I32, _P, _P, _P],
+    'otr_ctc_prefix_score': [_P, _I64, _P, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _P, _P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P,
+                             _F32, _P, _P, _P, _I32, _P, _P, _P, _P],
+    'otr_beam_prune_joint': [_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],
+    'otr_beam_prune_cached_joint': [_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P],
     'otr_decode_embed': [_P, _I64, _P, _P, _P, _P, _I64, _I32, _I32, _F32, _P],
     'otr_decode_lookup': [_P, _I64, _P, _P, _P, _P, _I64, _I32, _I32, _P],
     'otr_lstm_cell': [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P],

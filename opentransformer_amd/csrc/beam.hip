@@ -252,7 +252,7 @@ __global__ __launch_bounds__(256) void beam_prune_kernel(const float* k_score, c
                                                         int beam, int t, int eos, float* scores_out, uint8_t* flag_out,
                                                         int64_t* preds_out, int32_t* n_finished, const int32_t* pos_in,
                                                         int32_t* pos_out, const int32_t* anc_in, int32_t* anc_out,
-                                                        int ld_anc, int32_t* arrive) {
+                                                        int ld_anc, int32_t* arrive, const int32_t* ksrc_in, int32_t* jsrc_out) {
   __shared__ float c0[256];
   __shared__ int win[MAXK];
   const int b = blockIdx.x, tid = threadIdx.x, nc = beam * beam;
@@ -299,6 +299,7 @@ __global__ __launch_bounds__(256) void beam_prune_kernel(const float* k_score, c
       const int64_t src = ob + w / beam;
       const bool fin = flag_in[src] != 0;
       const int64_t tok = fin ? (int64_t)eos : k_idx[src * beam + (w % beam)];   // mask_finished_preds
+      if (jsrc_out) jsrc_out[ob + tid] = fin ? -1 : ksrc_in[src * beam + (w % beam)];   // joint CTC: the candidate's prefix state
       preds_out[(ob + tid) * ldp + t] = tok;
       if (anc_in) anc_out[(ob + tid) * ld_anc + t - 1] = (int32_t)src;
       f = tok == eos;
@@ -334,7 +335,7 @@ extern "C" int32_t otr_beam_prune(const float* k_score, const int64_t* k_idx, co
   otr_zero_f32(reinterpret_cast<float*>(n_finished), 1, s);   // int32 0 == float 0 bit pattern
   hipLaunchKernelGGL(beam_prune_kernel, dim3(batch), dim3(256), 0, s, k_score, k_idx, scores_in, flag_in, preds_in, ldp,
                      beam, t, eos, scores_out, flag_out, preds_out, n_finished, (const int32_t*)nullptr, (int32_t*)nullptr,
-                     (const int32_t*)nullptr, (int32_t*)nullptr, 0, (int32_t*)nullptr);
+                     (const int32_t*)nullptr, (int32_t*)nullptr, 0, (int32_t*)nullptr, (const int32_t*)nullptr, (int32_t*)nullptr);
   return otr_check_launch("beam_prune");
 }
 
@@ -356,6 +357,47 @@ extern "C" int32_t otr_beam_prune_cached(const float* k_score, const int64_t* k_
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(beam_prune_kernel, dim3(batch), dim3(256), 0, s, k_score, k_idx, scores_in, flag_in, preds_in, ldp,
                      beam, 0, eos, scores_out, flag_out, preds_out, n_finished, pos_in, pos_out, anc_in, anc_out, ld_anc,
-                     n_finished + 1);
+                     n_finished + 1, (const int32_t*)nullptr, (int32_t*)nullptr);
   return otr_check_launch("beam_prune_cached");
+}
+
+// The joint CTC/attention search (csrc/ctcscore.hip): the same prunes, plus jsrc_out[r'] = ksrc_in[the entry r' came from] (-1 for a
+// finished parent) -- which candidate's CTC prefix state each survivor inherits.
+extern "C" int32_t otr_beam_prune_joint(const float* k_score, const int64_t* k_idx, const float* scores_in, const uint8_t* flag_in,
+                                        const int64_t* preds_in, int64_t ldp, int32_t batch, int32_t beam, int32_t t, int32_t eos,
+                                        float* scores_out, uint8_t* flag_out, int64_t* preds_out, int32_t* n_finished,
+                                        const int32_t* ksrc_in, int32_t* jsrc_out, void* stream) {
+  OTR_REQUIRE(k_score && k_idx && scores_in && flag_in && preds_in && scores_out && flag_out && preds_out && n_finished && ksrc_in &&
+              jsrc_out, "beam_prune_joint: null pointer");
+  OTR_REQUIRE(beam >= 1 && beam <= MAXK && beam * beam <= 256, "beam_prune_joint: beam=%d must be in [1, 16]", beam);
+  OTR_REQUIRE(batch > 0 && t >= 1 && t < ldp, "beam_prune_joint: bad shape batch=%d t=%d ldp=%lld", batch, t, (long long)ldp);
+  hipStream_t s = (hipStream_t)stream;
+  otr_zero_f32(reinterpret_cast<float*>(n_finished), 1, s);
+  hipLaunchKernelGGL(beam_prune_kernel, dim3(batch), dim3(256), 0, s, k_score, k_idx, scores_in, flag_in, preds_in, ldp,
+                     beam, t, eos, scores_out, flag_out, preds_out, n_finished, (const int32_t*)nullptr, (int32_t*)nullptr,
+                     (const int32_t*)nullptr, (int32_t*)nullptr, 0, (int32_t*)nullptr, ksrc_in, jsrc_out);
+  return otr_check_launch("beam_prune_joint");
+}
+
+extern "C" int32_t otr_beam_prune_cached_joint(const float* k_score, const int64_t* k_idx, const float* scores_in,
+                                               const uint8_t* flag_in, const int64_t* preds_in, int64_t ldp, int32_t batch,
+                                               int32_t beam, int32_t eos, const int32_t* pos_in, int32_t* pos_out,
+                                               const int32_t* anc_in, int32_t* anc_out, int32_t ld_anc, float* scores_out,
+                                               uint8_t* flag_out, int64_t* preds_out, int32_t* n_finished, const int32_t* ksrc_in,
+                                               int32_t* jsrc_out, void* stream) {
+  OTR_REQUIRE(k_score && k_idx && scores_in && flag_in && preds_in && scores_out && flag_out && preds_out && n_finished && ksrc_in &&
+              jsrc_out, "beam_prune_cached_joint: null pointer");
+  OTR_REQUIRE(pos_in && pos_out && anc_in && anc_out, "beam_prune_cached_joint: null position / ancestor pointer");
+  OTR_REQUIRE(pos_in != pos_out && anc_in != anc_out && preds_in != preds_out,
+              "beam_prune_cached_joint: in/out buffers must be distinct (ping-pong)");
+  OTR_REQUIRE(beam >= 1 && beam <= MAXK && beam * beam <= 256, "beam_prune_cached_joint: beam=%d must be in [1, 16]", beam);
+  OTR_REQUIRE(batch > 0 && ld_anc > 0 && ld_anc < ldp, "beam_prune_cached_joint: bad shape batch=%d ld_anc=%d ldp=%lld", batch,
+              ld_anc, (long long)ldp);
+  OTR_REQUIRE(batch < 32768 && (int64_t)batch * beam < 65536, "beam_prune_cached_joint: batch=%d x beam=%d too large for the packed arrival word",
+              batch, beam);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(beam_prune_kernel, dim3(batch), dim3(256), 0, s, k_score, k_idx, scores_in, flag_in, preds_in, ldp,
+                     beam, 0, eos, scores_out, flag_out, preds_out, n_finished, pos_in, pos_out, anc_in, anc_out, ld_anc,
+                     n_finished + 1, ksrc_in, jsrc_out);
+  return otr_check_launch("beam_prune_cached_joint");
 }

@@ -3666,3 +3666,46 @@ def ctc_prefix_beam_search(log_probs, lengths, beam_width=5, cutoff_top_n=40, bl
                                     workspace.numel() * workspace.element_size(), _p(tokens), _p(out_len), _p(scores), _stream()),
             'otr_ctc_beam_search')
     return tokens, out_len, scores
+
+
+# ------------------------------------------------------------------ joint CTC/attention beam search (csrc/ctcscore.hip)
+JOINT_MAX_K, JOINT_MAX_T, JOINT_MAX_V, JOINT_MAX_BEAM = 32, 2048, 8192, 16
+
+
+def joint_prebeam(logits, lm_logits, att_weight, lm_weight, k, V, cand_score=None, cand_idx=None):
+    """The pre-beam of the joint search (include/otrans_hip.h otr_joint_prebeam): per row of logits f32 [R, >= V] (and lm_logits,
+    or None) the k tokens of highest att_weight * log_softmax(logits) + lm_weight * log_softmax(lm_logits), descending, ties -> lower
+    token.  Returns (cand_score f32 [R, k], cand_idx int32 [R, k]); one launch on the current stream, capturable."""
+    _cuda(logits)
+    R = logits.shape[0]
+    dev = logits.device
+    if cand_score is None:
+        cand_score = torch.empty((R, k), dtype=torch.float32, device=dev)
+        cand_idx = torch.empty((R, k), dtype=torch.int32, device=dev)
+    L.check(L.load().otr_joint_prebeam(_p(logits), logits.stride(0), _p(lm_logits) if lm_logits is not None else None,
+                                       lm_logits.stride(0) if lm_logits is not None else V, float(att_weight), float(lm_weight), R, V, k,
+                                       _p(cand_score), _p(cand_idx), _stream()), 'otr_joint_prebeam')
+    return cand_score, cand_idx
+
+
+def ctc_prefix_score(log_probs, lengths, cand_idx, preds, t, rows_per_utt, blank, eos, jsrc, state_in, state_out, pos=None,
+                     cand_score=None, ctc_weight=0.0, beam=0, flags=None, k_score=None, k_idx=None, k_src=None):
+    """CTC prefix scores of every candidate extension (include/otrans_hip.h otr_ctc_prefix_score).  log_probs f32 [B, T', V] (the CTC
+    head's log-softmax), lengths int32 [B] frames; cand_idx int32 [R, K'] candidate tokens of the R hypotheses whose prefixes are
+    preds[:, :t] (t = pos + 1 with pos a device int32 scalar, when given); jsrc int32 [R]: each hypothesis's slot in state_in.
+    state_in / state_out: (rn f32 [slots, T'], rb f32 [slots, T'], psi f32 [slots]) -- state_out gets slot r*K'+k for every candidate
+    (rn / rb may be None: psi only).  With cand_score f32 [R, K'] also the joint score and the top-`beam` of the K' per hypothesis into
+    (k_score, k_idx, k_src).  One launch on the current stream, no host synchronisation: capturable."""
+    _cuda(log_probs, lengths, cand_idx, preds)
+    B, T, V = log_probs.shape
+    R, K = cand_idx.shape
+    rn_o, rb_o, psi_o = state_out
+    L.check(L.load().otr_ctc_prefix_score(_p(log_probs), log_probs.stride(1), _p(lengths), B, T, V, blank, eos, R, rows_per_utt, K,
+                                          _p(cand_idx), _p(cand_score) if cand_score is not None else None,
+                                          _p(flags) if flags is not None else None, _p(preds), preds.stride(0), int(t),
+                                          _p(pos) if pos is not None else None, _p(jsrc), _p(state_in[0]), _p(state_in[1]), _p(state_in[2]),
+                                          float(ctc_weight), _p(rn_o) if rn_o is not None else None, _p(rb_o) if rb_o is not None else None,
+                                          _p(psi_o), int(beam), _p(k_score) if k_score is not None else None,
+                                          _p(k_idx) if k_idx is not None else None, _p(k_src) if k_src is not None else None, _stream()),
+            'otr_ctc_prefix_score')
+    return psi_o

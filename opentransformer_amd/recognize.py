@@ -261,14 +261,66 @@ def _padded_output(weight, bias):
     return None
 
 
+class _JointCTC:
+    """Device state of the joint CTC/attention search (include/otrans_hip.h, csrc/ctcscore.hip) for R = B * beam hypotheses over T'
+    frames: the CTC head's log-probs and lengths, the pre-beam candidates, the prefix states double-buffered per ping-pong phase like
+    preds / scores (a step reading phase cur writes phase cur ^ 1 only), the survivors' state slots and the top-beam's slots."""
+
+    def __init__(self, B, T, V, K, beam, dev):
+        R = B * beam
+        self.B, self.T, self.V, self.K, self.beam = B, T, V, K, beam
+        new = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)    # noqa: E731
+        self.lp = new((B, T, V), torch.float32)
+        self.lengths = new((B,), torch.int32)
+        self.cand_s, self.cand_i = new((R, K), torch.float32), new((R, K), torch.int32)
+        self.state = [(new((R * K, T), torch.float32), new((R * K, T), torch.float32), new((R * K,), torch.float32)) for _ in range(2)]
+        self.jsrc = [new((R,), torch.int32) for _ in range(2)]
+        self.k_src = new((R, beam), torch.int32)
+
+    def load(self, log_probs, lengths):
+        self.lp.copy_(log_probs)
+        self.lengths.copy_(lengths.reshape(-1))
+
+    def score(self, rec, logits, lm_logits, preds, cur, flags, k_score, k_idx, t=0, pos=None):
+        """pre-beam top-K' + CTC prefix scores + the joint top-beam of one step, reading phase cur, writing phase cur ^ 1's states"""
+        lam = float(rec.ctc_weight)
+        ops.joint_prebeam(logits, lm_logits, 1.0 - lam, float(rec.lm_weight or 0.0), self.K, self.V, self.cand_s, self.cand_i)
+        ops.ctc_prefix_score(self.lp, self.lengths, self.cand_i, preds, t, self.beam, rec.model.assistor.blank, EOS, self.jsrc[cur],
+                             self.state[cur], self.state[cur ^ 1], pos=pos, cand_score=self.cand_s, ctc_weight=lam, beam=self.beam,
+                             flags=flags, k_score=k_score, k_idx=k_idx, k_src=self.k_src)
+
+
 class SpeechToTextRecognizer(Recognizer):
-    """recognize/speech2text.py:6-153.  ctc_weight is accepted and unused, as in the reference."""
+    """recognize/speech2text.py:6-153.
+    joint_ctc=False (the default, as in the reference): attention decoder (+ LM shallow fusion) only; ctc_weight is accepted and unused.
+    joint_ctc=True: hybrid CTC/attention decoding (Watanabe et al. 2017, Algorithm 2; ESPnet's CTCPrefixScore) with the model's CTC
+    head (model.assistor, built when the model was trained with ctc_weight > 0): per hypothesis the ctc_beam tokens of highest
+    (1 - ctc_weight) * att + lm_weight * lm are scored (1 - ctc_weight) * att + lm_weight * lm + ctc_weight * (psi(h) - psi(g)), psi the
+    CTC prefix score, and the beam best of them go to the usual prune.  The score of a hypothesis that ended in EOS is then
+    (1 - ctc_weight) log P_att + ctc_weight log P_ctc + lm_weight log P_lm.  ctc_beam defaults to min(V, int(1.5 * beam_width)) as in
+    ESPnet.  Both decode loops; under apply_cache the joint step is part of the captured graph.  include/otrans_hip.h states the
+    semantics and the limits (beam_width <= 16, beam_width <= ctc_beam <= min(V, 32), T' <= 2048)."""
 
     def __init__(self, model, lm=None, lm_weight=0.1, ctc_weight=0.0, beam_width=5, nbest=1, max_len=50,
-                 idx2unit=None, penalty=0, lamda=5, ngpu=1, apply_cache=False):
+                 idx2unit=None, penalty=0, lamda=5, ngpu=1, apply_cache=False, joint_ctc=False, ctc_beam=None):
         super().__init__(model, idx2unit, lm, lm_weight, ngpu)
         self.beam_width, self.max_len, self.nbest = beam_width, max_len, nbest
         self.penalty, self.lamda, self.ctc_weight, self.lm_weight = penalty, lamda, ctc_weight, lm_weight
+        self.joint_ctc, self.ctc_beam = bool(joint_ctc), None
+        if self.joint_ctc:
+            if getattr(model, 'assistor', None) is None:
+                raise ValueError('joint_ctc=True needs the model\'s CTC head (model.assistor): build the model with ctc_weight > 0')
+            if not 0.0 <= float(ctc_weight) <= 1.0:
+                raise ValueError('joint_ctc=True: ctc_weight=%r must be in [0, 1]' % (ctc_weight,))
+            V = model.decoder.output_layer.weight.shape[0]
+            if not 1 <= beam_width <= ops.JOINT_MAX_BEAM:
+                raise ValueError('joint_ctc=True: beam_width=%d must be in [1, %d]' % (beam_width, ops.JOINT_MAX_BEAM))
+            if V > ops.JOINT_MAX_V:
+                raise ValueError('joint_ctc=True: vocabulary %d > %d' % (V, ops.JOINT_MAX_V))
+            self.ctc_beam = int(ctc_beam) if ctc_beam is not None else min(V, int(1.5 * beam_width))
+            if not beam_width <= self.ctc_beam <= min(V, ops.JOINT_MAX_K):
+                raise ValueError('joint_ctc=True: ctc_beam=%d must be in [beam_width=%d, min(V=%d, %d)]'
+                                 % (self.ctc_beam, beam_width, V, ops.JOINT_MAX_K))
         self.attn_weights = {}
         self.apply_cache = bool(apply_cache)
         self.use_hipgraph = True
@@ -279,6 +331,13 @@ class SpeechToTextRecognizer(Recognizer):
         x, mask, fe_cache = self.model.frontend.inference(inputs, inputs_mask, None)
         memory, memory_mask, attn = self.model.encoder(x, mask)
         return memory, memory_mask, {'frontend': fe_cache}, attn
+
+    def _ctc_head(self, memory, memory_mask):
+        """the CTC head's f32 log-probs [B, T', V] and int32 lengths [B] for the joint search; T' is refused before the first launch"""
+        if memory.size(1) > ops.JOINT_MAX_T:
+            raise ValueError('joint_ctc=True: T\'=%d encoder frames > %d' % (memory.size(1), ops.JOINT_MAX_T))
+        log_probs, length = self.model.assistor.inference(memory, memory_mask)
+        return log_probs.float().contiguous(), length.to(torch.int32).contiguous()
 
     def _nbest(self, scores, preds, steps, b):
         """n-best selection on the host: B*beam scalars (speech2text.py:70-93)"""
@@ -298,22 +357,27 @@ class SpeechToTextRecognizer(Recognizer):
     def recognize_cached(self, inputs, inputs_mask):
         memory, memory_mask, _, _ = self.encode(inputs, inputs_mask)
         b, t, _ = memory.size()
+        if self.joint_ctc and t > ops.JOINT_MAX_T:
+            raise ValueError('joint_ctc=True: T\'=%d encoder frames > %d' % (t, ops.JOINT_MAX_T))
         # the captured graphs bake in the device pointers of the stand-alone 16-bit weight shadows (ops.weight_lp caches a
         # cast per parameter version): a checkpoint loaded into the same modules, averaging, ... re-allocates them, so the
         # weights' (version, pointer) fingerprint is part of the key -- stale graphs are dropped, never replayed
         fp = 0
-        for mod in (self.model.decoder, self.lm):
+        for mod in (self.model.decoder, self.lm, self.model.assistor if self.joint_ctc else None):
             if mod is not None:
                 for p_ in mod.parameters():
                     fp = (fp * 1000003 + p_._version * 31 + p_.data_ptr()) & 0xFFFFFFFFFFFF
         key = (b, t, self.beam_width, self.max_len, ops.get_compute_dtype(), str(memory.device),
-               self.lm is not None, bool(self.use_hipgraph), fp)
+               self.lm is not None, bool(self.use_hipgraph), fp, self.joint_ctc, float(self.ctc_weight) if self.joint_ctc else None,
+               self.ctc_beam)
         st = self._cached_states.get(key)
         if st is None:
             if len(self._cached_states) >= 4:                # a few shapes; each holds caches + two graphs
                 self._cached_states.pop(next(iter(self._cached_states)))
             st = self._cached_states[key] = CachedBeamState(self, b, t, memory.device)
         st.load_memory(memory, memory_mask)
+        if st.joint is not None:
+            st.joint.load(*self._ctc_head(memory, memory_mask))
         cur, steps = st.run()
         return self._nbest(st.scores[cur], st.preds[cur], steps, b)
 
@@ -339,6 +403,11 @@ class SpeechToTextRecognizer(Recognizer):
         k_score = torch.empty((R, beam), dtype=torch.float32, device=dev)
         k_idx = torch.empty((R, beam), dtype=torch.long, device=dev)
         n_fin = torch.zeros(1, dtype=torch.int32, device=dev)
+        joint = None
+        if self.joint_ctc:
+            log_probs, length = self._ctc_head(memory, memory_mask)
+            joint = _JointCTC(b, t, self.model.decoder.output_layer.weight.shape[0], self.ctc_beam, beam, dev)
+            joint.load(log_probs, length)
         cur, steps = 0, 0
         stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)    # noqa: E731
         for step in range(1, self.max_len + 1):
@@ -350,13 +419,20 @@ class SpeechToTextRecognizer(Recognizer):
                 lm_logits, lm_off, lm_ld = self.lm.logits_last(prefix), 0, V        # the last token, no state (recognize/base.py:35-36)
             elif self.lm is not None:
                 lm_logits, lm_off = self.lm.logits(prefix), (step - 1) * V
-            L.check(lib.otr_beam_topk(_ptr(logits, (step - 1) * V), step * V,
-                                      _ptr(lm_logits, lm_off) if lm_logits is not None else None, lm_ld,
-                                      float(self.lm_weight or 0.0), R, V, beam, _ptr(k_score), _ptr(k_idx), stream()),
-                    'otr_beam_topk')
-            L.check(lib.otr_beam_prune(_ptr(k_score), _ptr(k_idx), _ptr(scores[cur]), _ptr(flags[cur]), _ptr(preds[cur]),
-                                       ldp, b, beam, step, EOS, _ptr(scores[cur ^ 1]), _ptr(flags[cur ^ 1]),
-                                       _ptr(preds[cur ^ 1]), _ptr(n_fin), stream()), 'otr_beam_prune')
+            if joint is not None:
+                joint.score(self, logits[:, step - 1], None if lm_logits is None else lm_logits.reshape(R, -1, V)[:, -1], preds[cur], cur,
+                            flags[cur], k_score, k_idx, t=step)
+                L.check(lib.otr_beam_prune_joint(_ptr(k_score), _ptr(k_idx), _ptr(scores[cur]), _ptr(flags[cur]), _ptr(preds[cur]), ldp, b,
+                                                 beam, step, EOS, _ptr(scores[cur ^ 1]), _ptr(flags[cur ^ 1]), _ptr(preds[cur ^ 1]),
+                                                 _ptr(n_fin), _ptr(joint.k_src), _ptr(joint.jsrc[cur ^ 1]), stream()), 'otr_beam_prune_joint')
+            else:
+                L.check(lib.otr_beam_topk(_ptr(logits, (step - 1) * V), step * V,
+                                          _ptr(lm_logits, lm_off) if lm_logits is not None else None, lm_ld,
+                                          float(self.lm_weight or 0.0), R, V, beam, _ptr(k_score), _ptr(k_idx), stream()),
+                        'otr_beam_topk')
+                L.check(lib.otr_beam_prune(_ptr(k_score), _ptr(k_idx), _ptr(scores[cur]), _ptr(flags[cur]), _ptr(preds[cur]),
+                                           ldp, b, beam, step, EOS, _ptr(scores[cur ^ 1]), _ptr(flags[cur ^ 1]),
+                                           _ptr(preds[cur ^ 1]), _ptr(n_fin), stream()), 'otr_beam_prune')
             cur ^= 1
             steps = step
             if self.trace is not None:
@@ -419,6 +495,7 @@ class CachedBeamState:
         self.paired = bool(_DECODE_PAIR and self.fused_dec and self.fused_lm and not self.lm_recurrent)
         self.side = torch.cuda.Stream(device=dev) if (lm is not None and dev.type == 'cuda' and not self.paired) else None
         self.side_ws = ops.new_workspace(dev) if self.side is not None else None
+        self.joint = _JointCTC(b, Tm, dec.output_layer.weight.shape[0], rec.ctc_beam, beam, dev) if rec.joint_ctc else None
 
     def load_memory(self, memory, memory_mask):
         """Project the encoder memory to cross-attention K|V once per utterance and layer
@@ -753,9 +830,18 @@ class CachedBeamState:
         if self.side is not None:
             main.wait_stream(self.side)                   # join: the LM's logits are ready
         ld_lm = lm_logits.size(-1) if lm_logits is not None else V
+        nxt = cur ^ 1
+        if self.joint is not None:
+            j = self.joint
+            j.score(rec, logits, lm_logits, self.preds[cur], cur, self.flags[cur], self.k_score, self.k_idx, pos=self.pos[cur])
+            L.check(lib.otr_beam_prune_cached_joint(_ptr(self.k_score), _ptr(self.k_idx), _ptr(self.scores[cur]), _ptr(self.flags[cur]),
+                                                    _ptr(self.preds[cur]), self.ldp, self.b, beam, EOS, _ptr(self.pos[cur]), _ptr(self.pos[nxt]),
+                                                    _ptr(self.anc[cur]), _ptr(self.anc[nxt]), self.maxlen, _ptr(self.scores[nxt]),
+                                                    _ptr(self.flags[nxt]), _ptr(self.preds[nxt]), _ptr(self.n_fin[nxt]), _ptr(j.k_src),
+                                                    _ptr(j.jsrc[nxt]), stream), 'otr_beam_prune_cached_joint')
+            return
         L.check(lib.otr_beam_topk(_ptr(logits), ld, _ptr(lm_logits), ld_lm, float(rec.lm_weight or 0.0), self.R, V, beam,
                                   _ptr(self.k_score), _ptr(self.k_idx), stream), 'otr_beam_topk')
-        nxt = cur ^ 1
         L.check(lib.otr_beam_prune_cached(_ptr(self.k_score), _ptr(self.k_idx), _ptr(self.scores[cur]),
                                           _ptr(self.flags[cur]), _ptr(self.preds[cur]), self.ldp, self.b, beam, EOS,
                                           _ptr(self.pos[cur]), _ptr(self.pos[nxt]), _ptr(self.anc[cur]),
@@ -872,7 +958,8 @@ def build_recognizer(model_type, model, lm, args, idx2unit):
     if model_type == 'speech2text':
         return SpeechToTextRecognizer(model=model, lm=lm, lm_weight=args.lm_weight, ctc_weight=args.ctc_weight,
                                       beam_width=args.beam_width, nbest=args.nbest, max_len=args.max_len,
-                                      idx2unit=idx2unit, penalty=args.penalty, lamda=args.lamda, ngpu=args.ngpu)
+                                      idx2unit=idx2unit, penalty=args.penalty, lamda=args.lamda, ngpu=args.ngpu,
+                                      joint_ctc=getattr(args, 'joint_ctc', False), ctc_beam=getattr(args, 'ctc_beam', None))
     if model_type == 'ctc':
         return CTCRecognizer(model=model, lm=lm, lm_weight=args.lm_weight, ngram_lm=args.ngram_lm,
                              beam_width=args.beam_width, idx2unit=idx2unit, ngpu=args.ngpu, mode=args.mode,
