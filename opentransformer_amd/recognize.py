@@ -140,9 +140,7 @@ class RecurrentLanguageModel(nn.Module):
             preds, pos = preds[:, -1:], None
         x = ops.decode_lookup(preds, pos, self.embedding.weight)
         y = self._step(x, [None] * self.num_layers, [None] * self.num_layers)
-        if out is not None:                   # recognize._PaddedOutput of output_project: [R, rows8] logits
-            return out(y)
-        return ops.linear(y, self.output_project.weight, self.output_project.bias)
+        return _output(out, self.output_project, y)      # out: the _PaddedOutput of output_project ([R, rows8] logits) or None
 
     def forward(self, inputs, targets):
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
@@ -259,6 +257,89 @@ def _padded_output(weight, bias):
     if ops.is_half() and weight.is_cuda and weight.dim() == 2 and weight.shape[0] % 8 != 0 and weight.shape[1] % 8 == 0:
         return _PaddedOutput(weight, bias)
     return None
+
+
+def _output(padded, layer, x):
+    """the vocabulary projection of a decode step: the _PaddedOutput of `layer` where there is one, else ops.linear"""
+    return padded(x) if padded is not None else ops.linear(x, layer.weight, layer.bias)
+
+
+class _FusedChain:
+    """One post-norm stack's position in a chain of fused decode launches (csrc/declayer.hip): its residual rows, the descriptor of
+    the add + LayerNorm the NEXT launch finishes in its prologue (ops._dec_ln), and `keep`, the tensors that descriptor points at --
+    it holds raw pointers, so they stay alive until that launch is queued.  The stages of a layer: [LayerNorm of the layer below +
+    q|k|v + cached self-attention + output projection] (self_item), for a decoder layer (kvs given) [LayerNorm + q + cross-attention
+    over the utterance memory + output projection] (cross: the beam hypotheses of an utterance are the query rows of ONE attention
+    problem, exactly the training launch with L = beam), [LayerNorm + w_1 + GLU + w_2] cut into slices(F) hidden slices (ffn_item).
+    Each stage leaves its output in slabs that `close` turns into the next descriptor.  CachedBeamState._walk issues the launches."""
+
+    def __init__(self, st, cur, x, blocks, caches, kvs, slices):
+        self.st, self.cur, self.blocks, self.caches, self.kvs, self.slices, self.li = st, cur, blocks, caches, kvs, slices, 0
+        x16 = ops.lp_of(x)
+        self.yres, self.keep = x.reshape(st.R, 256), [x, x16]
+        self.ln = ops._dec_ln(None, x16.reshape(st.R, 256), None, 0)       # the rows are normalised already: nothing to finish
+
+    def _h16(self, *shape):
+        return torch.empty(shape, dtype=ops.half_dtype(), device=self.yres.device)
+
+    def close(self, slabs, bias, norm):
+        """the residual add + LayerNorm that closes a sub-layer whose output is the partial sums `slabs`: left to the next launch"""
+        y, y16 = torch.empty_like(self.yres), self._h16(*self.yres.shape)
+        self.ln = ops._dec_ln(self.yres, None, slabs, slabs.shape[0], bias, norm.weight, norm.bias, None, 0.0, norm.eps, 0, y, y16)
+        self.keep = [self.yres, slabs, y, y16]
+        self.yres, self.y16 = y, y16
+
+    def self_item(self):
+        blk, st = self.blocks[self.li], self.st
+        a, slabs = blk.slf_attn, self._h16(4, st.R, 256)
+        it = L.DecSelfStep()
+        it.ln, it.R = self.ln, st.R
+        it.wqkv_pack, it.bqkv = ops.lin_packs(a.qvk_proj.weight)[0].data_ptr(), a.qvk_proj.bias.data_ptr()
+        it.wo_pack = ops.lin_packs(a.output_proj.weight)[0].data_ptr()
+        it.kcache, it.vcache = self.caches[self.li][0].data_ptr(), self.caches[self.li][1].data_ptr()
+        it.anc, it.pos, it.maxlen, it.slabs = st.anc[self.cur].data_ptr(), st.pos[self.cur].data_ptr(), st.maxlen, slabs.data_ptr()
+        self.closing = (slabs, a.output_proj.bias, blk.norm1)
+        return it
+
+    def cross(self, lib, stream):
+        if self.kvs is None:
+            return
+        blk, kv, st = self.blocks[self.li], self.kvs[self.li], self.st
+        ca, R, beam = blk.src_attn, st.R, st.rec.beam_width
+        slB, q16, ctx2 = self._h16(4, R, 256), self._h16(R, 256), self._h16(R, 256)
+        lse2 = torch.empty((st.b, 4, beam), dtype=torch.float32, device=self.yres.device)
+        W = kv.shape[2]
+        L.check(lib.otr_dec_cross_fwd(C.byref(self.ln), st.b, beam, ops._p(ops.lin_packs(ca.q_proj.weight)[0]), ops._p(ca.q_proj.bias),
+                                      ops._p(ops.lin_packs(ca.output_proj.weight)[0]), ops._p(kv), st.Tm * W, W, 0, W // 2,
+                                      ops._p(st.mem_mask), st.Tm, ops._p(q16), ops._p(ctx2), ops._p(lse2), ops._p(slB), stream),
+                'otr_dec_cross_fwd')
+        self.close(slB, ca.output_proj.bias, blk.norm2)
+
+    def ffn_item(self):
+        blk, R = self.blocks[self.li], self.st.R
+        ff = blk.feed_forward
+        F = ff.w_2.weight.shape[1]
+        S = self.slices(F)
+        packs, slabs = ops.ffn_packs(ff.w_1.weight, ff.w_2.weight), self._h16(S, R, 256)
+        it = L.DecFfnFwd()
+        it.ln, it.R = self.ln, R
+        it.w1_pack, it.b1, it.w2_pack = packs[0].data_ptr(), ff.w_1.bias.data_ptr(), packs[1].data_ptr()
+        it.F, it.S, it.slabs, it.hsave = F, S, slabs.data_ptr(), None
+        self.closing = (slabs, ff.w_2.bias, blk.norm3 if self.kvs is not None else blk.norm2)
+        return it
+
+    def out(self):
+        return ops.attach_lp(self.yres, self.y16)
+
+
+def _issue(lib, name, items, stream):
+    """one launch of a stage: `name`_pair on the items of two chains, else the single entry on the one item (its fields after `ln`
+    are the single entry's arguments, in order)"""
+    if len(items) == 2:
+        L.check(getattr(lib, name + '_pair')(C.byref(items[0]), C.byref(items[1]), stream), name + '_pair')
+    else:
+        it = items[0]
+        L.check(getattr(lib, name)(C.byref(it.ln), *[getattr(it, f) for f, _ in it._fields_[1:]], stream), name)
 
 
 class _JointCTC:
@@ -481,19 +562,24 @@ class CachedBeamState:
         self.nf_host = torch.zeros(2, dtype=torch.int32).pin_memory()     # pinned landing pad + events of the lagged all-finished test (run)
         self.nf_ev = [torch.cuda.Event(), torch.cuda.Event()]
         self.warm = [False, False]
-        self.fused_dec = (not dec.normalize_before and adt == ops.half_dtype() and all(kv.shape[2] == 512 for kv in self.mem_kv)
-                          and self._fused_stack_ok(dec.blocks, True))
+        # per layer: may the per-operator step finish it on the fused tail?  Weights, compute dtype, beam and ops._DEC_FUSED decide,
+        # all fixed for the state's lifetime (the weights' fingerprint and the compute dtype are part of its cache key)
+        self.tail_dec = [self._fused_tail_ok(blk, True) and kv.shape[2] == 512 for blk, kv in zip(dec.blocks, self.mem_kv)]
+        self.tail_lm = [self._fused_tail_ok(blk, False) for blk in lm.blocks] if self.lm_cache is not None else []
+        # the fused stacks start from the embedded rows' 16-bit twin: decode_embed attaches it whenever is_half(), which
+        # act_dtype() == half_dtype() implies, and the compute dtype is part of the cache key -- so step() never checks for it
+        self.fused_dec = not dec.normalize_before and adt == ops.half_dtype() and self._fused_stack_ok(dec.blocks, self.tail_dec)
         self.fused_lm = (self.lm_cache is not None and not getattr(lm, 'normalize_before', False) and adt == ops.half_dtype()
-                         and self._fused_stack_ok(lm.blocks, False))
+                         and self._fused_stack_ok(lm.blocks, self.tail_lm))
         # The LM's layers and the decoder's are two independent chains of small launches (24-80 workgroups on 256 CUs) that only
         # meet at the top-k: the LM chain runs on a side stream, forked at the start of the step and joined before the top-k
         # (in the captured graph: two parallel branches).  Its GEMMs get their own split-K workspace.
         # r06: ONE fork anywhere in a hipGraph takes the whole graph off the runtime's fast per-node path (1.6 -> ~3 us per node,
         # profiles/r06_boundary_probe.txt), which cost this 34-node step about as much as the overlap returned.  Where both stacks run on
         # the fused launches, the LM's layers are the SECOND problem of the decoder's own launches instead (otr_dec_self_step_pair,
-        # otr_dec_ffn_fwd_pair, otr_dec_ln_pair: _fused_stacks_paired): the same concurrency, one chain, 23 nodes.
+        # otr_dec_ffn_fwd_pair, otr_dec_ln_pair: _walk on two chains): the same concurrency, one chain, 23 nodes.
         self.paired = bool(_DECODE_PAIR and self.fused_dec and self.fused_lm and not self.lm_recurrent)
-        self.side = torch.cuda.Stream(device=dev) if (lm is not None and dev.type == 'cuda' and not self.paired) else None
+        self.side = torch.cuda.Stream(device=dev) if (lm is not None and not self.paired) else None
         self.side_ws = ops.new_workspace(dev) if self.side is not None else None
         self.joint = _JointCTC(b, Tm, dec.output_layer.weight.shape[0], rec.ctc_beam, beam, dev) if rec.joint_ctc else None
 
@@ -565,204 +651,71 @@ class CachedBeamState:
                 return False
         return True
 
-    def _fused_tail(self, blk, x1, kv, norm_cross, norm_ffn):
-        """x1 = the layer's state after the self-attention sub-layer.  kv given (decoder): [q projection + cross-attention over the
-        utterance memory + output projection] as ONE launch per layer cut along (group of 32 // beam utterances, head) -- the beam
-        hypotheses of an utterance are the query rows of one attention problem, exactly the training launch with L = beam -- then
-        [LayerNorm + w_1 + GLU + w_2] cut along (32-row block, hidden slice), then the closing LayerNorm (otr_dec_ln): 3 launches
-        for what took 8-9 (decoder/transformer.py:70-86).  kv None (LM layer, model/lm.py:94-140): the FFN sub-layer alone, 2 launches."""
-        lib, R, d = L.load(), self.R, 256
-        dev, hdt, st = x1.device, ops.half_dtype(), ops._stream()
-        ff = blk.feed_forward
-        F = ff.w_2.weight.shape[1]
-        S = ops.dec_ffn_slices(F)
-        h16 = lambda *sh: torch.empty(sh, dtype=hdt, device=dev)          # noqa: E731
-        f32 = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)  # noqa: E731
-        xr, x16 = x1.reshape(R, d), ops.lp_of(x1).reshape(R, d)
+    def _layer(self, x, blk, cache, cur, tail, concat_self, norm_ffn, kv=None, concat_cross=None):
+        """One layer for the new position on the per-operator launches: a decoder layer where kv (its cross-attention K|V) is given,
+        an LM layer else.  concat_self / concat_cross: the layer's concat_after Linears, norm_ffn: the norm that closes its FFN.  After
+        the self-attention, where `tail` holds, the fused tail: a chain of this one layer that starts at the cross-attention (decoder:
+        3 launches for what took 8-9, decoder/transformer.py:70-86) or at the FFN (LM, model/lm.py:94-140: 2 launches)."""
+        x = self._stack_step(x, blk, cache, cur, concat_self)
+        if tail and ops.lp_of(x) is not None and x.dtype == torch.float32:
+            return self._walk([_FusedChain(self, cur, x, [blk], None, None if kv is None else [kv], ops.dec_ffn_slices)], from_self=False)[0]
         if kv is not None:
-            ca = blk.src_attn
-            beam = self.rec.beam_width
-            slB, q16, ctx2, lse2 = h16(4, R, d), h16(R, d), h16(R, d), f32(self.b, 4, beam)
-            lnB = ops._dec_ln(None, x16, None, 0)                          # the rows are normalised already: nothing to finish
-            W = kv.shape[2]
-            L.check(lib.otr_dec_cross_fwd(C.byref(lnB), self.b, beam, ops._p(ops.lin_packs(ca.q_proj.weight)[0]), ops._p(ca.q_proj.bias),
-                                          ops._p(ops.lin_packs(ca.output_proj.weight)[0]), ops._p(kv), self.Tm * W, W, 0, W // 2,
-                                          ops._p(self.mem_mask), self.Tm, ops._p(q16), ops._p(ctx2), ops._p(lse2), ops._p(slB), st),
-                    'otr_dec_cross_fwd')
-            y2, y216 = f32(R, d), h16(R, d)
-            lnC = ops._dec_ln(xr, None, slB, 4, ca.output_proj.bias, norm_cross.weight, norm_cross.bias, None, 0.0, norm_cross.eps, 0,
-                              y2, y216)
-        else:
-            y2 = xr
-            lnC = ops._dec_ln(None, x16, None, 0)
-        packs = ops.ffn_packs(ff.w_1.weight, ff.w_2.weight)
-        slC = h16(S, R, d)
-        L.check(lib.otr_dec_ffn_fwd(C.byref(lnC), R, ops._p(packs[0]), ops._p(ff.w_1.bias), ops._p(packs[1]), F, S, ops._p(slC), None, st),
-                'otr_dec_ffn_fwd')
-        y3, y316 = f32(R, d), h16(R, d)
-        lnF = ops._dec_ln(y2, None, slC, S, ff.w_2.bias, norm_ffn.weight, norm_ffn.bias, None, 0.0, norm_ffn.eps, 0, y3, y316)
-        L.check(lib.otr_dec_ln(C.byref(lnF), R, st), 'otr_dec_ln')
-        return ops.attach_lp(y3, y316)
+            a = blk.src_attn
+            q = ops.linear(x, a.q_proj.weight, a.q_proj.bias, out_dtype=ops.act_dtype())
+            # the beam hypotheses of an utterance are the query rows of ONE attention problem over its memory
+            ctx = ops.CrossAttentionFn.apply(q.view(self.b, self.rec.beam_width, -1), kv, self.mem_mask, a.nheads)
+            x = self._close(blk, concat_cross, blk.norm3 if blk.normalize_before else blk.norm2, x, a, ctx.view(self.R, -1))
+        return self._ffn(blk, norm_ffn, x)
 
-    def _fused_stack_ok(self, blocks, with_cross):
+    def _fused_stack_ok(self, blocks, tails):
         """can every layer of this stack run the step on the fused launches (otr_dec_self_step + the fused tail)?"""
-        if not _DECODE_STEP_FUSED:
+        if not _DECODE_STEP_FUSED or not all(tails):
             return False
         for blk in blocks:
             a = blk.slf_attn
-            if (not self._fused_tail_ok(blk, with_cross) or a.nheads != 4 or a.share_qvk_proj or tuple(a.qvk_proj.weight.shape) != (768, 256)
+            if (a.nheads != 4 or a.share_qvk_proj or tuple(a.qvk_proj.weight.shape) != (768, 256)
                     or tuple(a.output_proj.weight.shape) != (256, 256) or a.qvk_proj.bias is None or a.output_proj.bias is None
                     or ops.lin_packs(a.qvk_proj.weight) is None or ops.lin_packs(a.output_proj.weight) is None):
                 return False
         return True
 
-    def _fused_stack(self, x, blocks, caches, kvs, cur):
-        """Every layer of a post-norm stack for the new position on the fused launches of csrc/declayer.hip: per layer
-        [LayerNorm of the layer below + q|k|v + cached self-attention + output projection] (otr_dec_self_step), for a decoder layer
-        [LayerNorm + q + cross-attention + output projection] (otr_dec_cross_fwd, kvs given), [LayerNorm + w_1 + GLU + w_2]
-        (otr_dec_ffn_fwd); the LayerNorm that closes the stack is otr_dec_ln.  3 launches per decoder layer, 2 per LM layer (it was 6
-        and 5: decoder/transformer.py:56-86, encoder/transformer.py:41-63)."""
-        lib, R, d = L.load(), self.R, 256
-        dev, hdt, st = x.device, ops.half_dtype(), ops._stream()
-        h16 = lambda *sh: torch.empty(sh, dtype=hdt, device=dev)          # noqa: E731
-        f32 = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)  # noqa: E731
-        beam = self.rec.beam_width
-        yres = x.reshape(R, d)
-        ln = ops._dec_ln(None, ops.lp_of(x).reshape(R, d), None, 0)       # the embedded rows: nothing to finish
-        out = None
+    def _stack_slices(self, F):
+        # a few row blocks only: cut the hidden units 16 ways (a workgroup streams its slice of w_1 / w_2 at what ONE CU ingests,
+        # 24 workgroups of 393 KB at S = 8); otr_dec_self_step and otr_dec_ln take up to 16 slabs
+        return 16 if (F % 2048 == 0 and self.R <= 128) else ops.dec_ffn_slices(F)
 
-        def closes(slabs, nslab, bias, norm):
-            """descriptor of the add + LayerNorm the NEXT launch finishes in its prologue, and its outputs"""
-            y, y16 = f32(R, d), h16(R, d)
-            return ops._dec_ln(yres, None, slabs, nslab, bias, norm.weight, norm.bias, None, 0.0, norm.eps, 0, y, y16), y, y16
+    def _dec_chain(self, x, cur):
+        return _FusedChain(self, cur, x, self.rec.model.decoder.blocks, self.dec_cache, self.mem_kv, self._stack_slices)
 
-        for li, blk in enumerate(blocks):
-            a, ff = blk.slf_attn, blk.feed_forward
-            slA = h16(4, R, d)
-            L.check(lib.otr_dec_self_step(C.byref(ln), R, ops._p(ops.lin_packs(a.qvk_proj.weight)[0]), ops._p(a.qvk_proj.bias),
-                                          ops._p(ops.lin_packs(a.output_proj.weight)[0]), ops._p(caches[li][0]), ops._p(caches[li][1]),
-                                          ops._p(self.anc[cur]), ops._p(self.pos[cur]), self.maxlen, ops._p(slA), st), 'otr_dec_self_step')
-            ln, yres, _ = closes(slA, 4, a.output_proj.bias, blk.norm1)
-            if kvs is not None:
-                ca, kv = blk.src_attn, kvs[li]
-                slB, q16, ctx2, lse2 = h16(4, R, d), h16(R, d), h16(R, d), f32(self.b, 4, beam)
-                W = kv.shape[2]
-                L.check(lib.otr_dec_cross_fwd(C.byref(ln), self.b, beam, ops._p(ops.lin_packs(ca.q_proj.weight)[0]), ops._p(ca.q_proj.bias),
-                                              ops._p(ops.lin_packs(ca.output_proj.weight)[0]), ops._p(kv), self.Tm * W, W, 0, W // 2,
-                                              ops._p(self.mem_mask), self.Tm, ops._p(q16), ops._p(ctx2), ops._p(lse2), ops._p(slB), st),
-                        'otr_dec_cross_fwd')
-                ln, yres, _ = closes(slB, 4, ca.output_proj.bias, blk.norm2)
-            F = ff.w_2.weight.shape[1]
-            # a few row blocks only: cut the hidden units 16 ways (a workgroup streams its slice of w_1 / w_2 at what ONE CU ingests,
-            # 24 workgroups of 393 KB at S = 8); otr_dec_self_step and otr_dec_ln take up to 16 slabs
-            S = 16 if (F % 2048 == 0 and R <= 128) else ops.dec_ffn_slices(F)
-            packs = ops.ffn_packs(ff.w_1.weight, ff.w_2.weight)
-            slC = h16(S, R, d)
-            L.check(lib.otr_dec_ffn_fwd(C.byref(ln), R, ops._p(packs[0]), ops._p(ff.w_1.bias), ops._p(packs[1]), F, S, ops._p(slC), None, st),
-                    'otr_dec_ffn_fwd')
-            ln, yres, y16 = closes(slC, S, ff.w_2.bias, blk.norm3 if kvs is not None else blk.norm2)
-            out = (yres, y16)
-        L.check(lib.otr_dec_ln(C.byref(ln), R, st), 'otr_dec_ln')
-        return ops.attach_lp(*out)
+    def _lm_chain(self, x, cur):
+        return _FusedChain(self, cur, x, self.rec.lm.blocks, self.lm_cache, None, self._stack_slices)
 
-    def _fused_stacks_paired(self, xd, xl, cur):
-        """The decoder stack and the LM stack of one step in LOCKSTEP on pair launches: layer i of both in one otr_dec_self_step_pair and
-        one otr_dec_ffn_fwd_pair (the decoder's cross-attention launch between them is its own), the two closing LayerNorms in one
-        otr_dec_ln_pair.  The same launches on the same operands as two _fused_stack calls: bit-identical results."""
-        lib, R, d = L.load(), self.R, 256
-        dev, hdt, st = xd.device, ops.half_dtype(), ops._stream()
-        h16 = lambda *sh: torch.empty(sh, dtype=hdt, device=dev)          # noqa: E731
-        f32 = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)  # noqa: E731
-        beam = self.rec.beam_width
-        dec, lm = self.rec.model.decoder, self.rec.lm
-        state = self
-
-        class Walk:
-            """one stack's position in the chain: the descriptor of the add + LayerNorm the NEXT launch finishes, the residual rows"""
-
-            def __init__(self, x, blocks, caches, kvs):
-                self.blocks, self.caches, self.kvs, self.li = blocks, caches, kvs, 0
-                self.yres = x.reshape(R, d)
-                self.keep = [x, ops.lp_of(x)]                                     # tensors the pending descriptor points at
-                self.ln = ops._dec_ln(None, ops.lp_of(x).reshape(R, d), None, 0)
-
-            def done(self):
-                return self.li >= len(self.blocks)
-
-            def closes(self, slabs, nslab, bias, norm):
-                y, y16 = f32(R, d), h16(R, d)
-                self.ln = ops._dec_ln(self.yres, None, slabs, nslab, bias, norm.weight, norm.bias, None, 0.0, norm.eps, 0, y, y16)
-                self.keep = [self.yres, slabs, y, y16]
-                self.yres, self.y16 = y, y16
-
-            def self_item(self):
-                a = self.blocks[self.li].slf_attn
-                self.slA = h16(4, R, d)
-                it = L.DecSelfStep()
-                it.ln, it.R = self.ln, R
-                it.wqkv_pack, it.bqkv = ops.lin_packs(a.qvk_proj.weight)[0].data_ptr(), a.qvk_proj.bias.data_ptr()
-                it.wo_pack = ops.lin_packs(a.output_proj.weight)[0].data_ptr()
-                it.kcache, it.vcache = self.caches[self.li][0].data_ptr(), self.caches[self.li][1].data_ptr()
-                it.anc, it.pos, it.maxlen, it.slabs = state.anc[cur].data_ptr(), state.pos[cur].data_ptr(), state.maxlen, self.slA.data_ptr()
-                return it
-
-            def after_self(self):
-                blk = self.blocks[self.li]
-                self.closes(self.slA, 4, blk.slf_attn.output_proj.bias, blk.norm1)
-
-            def cross(self):
-                if self.kvs is None:
-                    return
-                blk = self.blocks[self.li]
-                ca, kv = blk.src_attn, self.kvs[self.li]
-                slB, q16, ctx2, lse2 = h16(4, R, d), h16(R, d), h16(R, d), f32(state.b, 4, beam)
-                W = kv.shape[2]
-                L.check(lib.otr_dec_cross_fwd(C.byref(self.ln), state.b, beam, ops._p(ops.lin_packs(ca.q_proj.weight)[0]), ops._p(ca.q_proj.bias),
-                                              ops._p(ops.lin_packs(ca.output_proj.weight)[0]), ops._p(kv), state.Tm * W, W, 0, W // 2,
-                                              ops._p(state.mem_mask), state.Tm, ops._p(q16), ops._p(ctx2), ops._p(lse2), ops._p(slB), st),
-                        'otr_dec_cross_fwd')
-                self.closes(slB, 4, ca.output_proj.bias, blk.norm2)
-
-            def ffn_item(self):
-                ff = self.blocks[self.li].feed_forward
-                F = ff.w_2.weight.shape[1]
-                self.S = 16 if (F % 2048 == 0 and R <= 128) else ops.dec_ffn_slices(F)
-                packs = ops.ffn_packs(ff.w_1.weight, ff.w_2.weight)
-                self.slC = h16(self.S, R, d)
-                it = L.DecFfnFwd()
-                it.ln, it.R = self.ln, R
-                it.w1_pack, it.b1, it.w2_pack = packs[0].data_ptr(), ff.w_1.bias.data_ptr(), packs[1].data_ptr()
-                it.F, it.S, it.slabs, it.hsave = F, self.S, self.slC.data_ptr(), None
-                return it
-
-            def after_ffn(self):
-                blk = self.blocks[self.li]
-                self.closes(self.slC, self.S, blk.feed_forward.w_2.bias, blk.norm3 if self.kvs is not None else blk.norm2)
-                self.li += 1
-
-        wd, wl = Walk(xd, dec.blocks, self.dec_cache, self.mem_kv), Walk(xl, lm.blocks, self.lm_cache, None)
-        while not (wd.done() and wl.done()):
-            live = [w for w in (wd, wl) if not w.done()]
-            items = [w.self_item() for w in live]
-            if len(items) == 2:
-                L.check(lib.otr_dec_self_step_pair(C.byref(items[0]), C.byref(items[1]), st), 'otr_dec_self_step_pair')
-            else:
-                i = items[0]
-                L.check(lib.otr_dec_self_step(C.byref(i.ln), R, i.wqkv_pack, i.bqkv, i.wo_pack, i.kcache, i.vcache, i.anc, i.pos, i.maxlen, i.slabs, st),
-                        'otr_dec_self_step')
-            for w in live:
-                w.after_self()
-                w.cross()
-            items = [w.ffn_item() for w in live]
-            if len(items) == 2:
-                L.check(lib.otr_dec_ffn_fwd_pair(C.byref(items[0]), C.byref(items[1]), st), 'otr_dec_ffn_fwd_pair')
-            else:
-                i = items[0]
-                L.check(lib.otr_dec_ffn_fwd(C.byref(i.ln), R, i.w1_pack, i.b1, i.w2_pack, i.F, i.S, i.slabs, None, st), 'otr_dec_ffn_fwd')
-            for w in live:
-                w.after_ffn()
-        L.check(lib.otr_dec_ln_pair(C.byref(wd.ln), R, C.byref(wl.ln), R, st), 'otr_dec_ln_pair')
-        return ops.attach_lp(wd.yres, wd.y16), ops.attach_lp(wl.yres, wl.y16)
+    def _walk(self, chains, from_self=True):
+        """Walk one or two post-norm stacks (_FusedChain) to their ends on the fused launches of csrc/declayer.hip: 3 launches per
+        decoder layer, 2 per LM layer (it was 6 and 5: decoder/transformer.py:56-86, encoder/transformer.py:41-63), then the closing
+        LayerNorm.  Two chains run in LOCKSTEP: layer i of both in one otr_dec_self_step_pair and one otr_dec_ffn_fwd_pair (the
+        decoder's cross-attention launch between them is its own), the closing LayerNorms in one otr_dec_ln_pair; where one stack is
+        deeper its tail runs on the single launches.  The same launches on the same operands as one chain at a time: bit-identical
+        results.  from_self=False: the first layer starts after its self-attention (the fused tail).  Returns each chain's output."""
+        lib, st = L.load(), ops._stream()
+        for _ in range(max(len(c.blocks) for c in chains)):
+            live = [c for c in chains if c.li < len(c.blocks)]
+            if from_self:
+                _issue(lib, 'otr_dec_self_step', [c.self_item() for c in live], st)
+            for c in live:
+                if from_self:
+                    c.close(*c.closing)
+                c.cross(lib, st)
+            _issue(lib, 'otr_dec_ffn_fwd', [c.ffn_item() for c in live], st)
+            for c in live:
+                c.close(*c.closing)
+                c.li += 1
+            from_self = True
+        if len(chains) == 2:
+            L.check(lib.otr_dec_ln_pair(C.byref(chains[0].ln), self.R, C.byref(chains[1].ln), self.R, st), 'otr_dec_ln_pair')
+        else:
+            L.check(lib.otr_dec_ln(C.byref(chains[0].ln), self.R, st), 'otr_dec_ln')
+        return [c.out() for c in chains]
 
     def _lm_logits(self, cur):
         """the LM's scores of the next token for every hypothesis, [R, V or V padded to 8] (speech2text.py:108-113)"""
@@ -770,62 +723,41 @@ class CachedBeamState:
         if self.lm_recurrent:
             return lm.logits_last(self.preds[cur], self.pos[cur], out=self.out_lm)     # one LSTM step from zeros on the last token (base.py:35-36)
         y = ops.decode_embed(self.preds[cur], self.pos[cur], lm.embedding.weight)
-        if self.fused_lm and ops.lp_of(y) is not None:
-            y = self._fused_stack(y, lm.blocks, self.lm_cache, None, cur)
-            return self.out_lm(y) if self.out_lm is not None else ops.linear(y, lm.output_project.weight, lm.output_project.bias)
-        for blk, cache in zip(lm.blocks, self.lm_cache):
-            y = self._stack_step(y, blk, cache, cur, getattr(blk, 'concat_linear', None))
-            if ops.lp_of(y) is not None and y.dtype == torch.float32 and self._fused_tail_ok(blk, False):
-                y = self._fused_tail(blk, y, None, None, blk.norm2)
-                continue
-            y = self._ffn(blk, blk.norm2, y)
-        return self.out_lm(y) if self.out_lm is not None else ops.linear(y, lm.output_project.weight, lm.output_project.bias)
+        if self.fused_lm:
+            y = self._walk([self._lm_chain(y, cur)])[0]
+        else:
+            for blk, cache, tail in zip(lm.blocks, self.lm_cache, self.tail_lm):
+                y = self._layer(y, blk, cache, cur, tail, getattr(blk, 'concat_linear', None), blk.norm2)
+        return _output(self.out_lm, lm.output_project, y)
 
     def step(self, cur):
-        """One beam-search step (recognize/speech2text.py:95-146) reading phase `cur`, writing phase cur^1."""
+        """One beam-search step (recognize/speech2text.py:95-146) reading phase `cur`, writing phase cur^1.  Three routes: paired (the
+        LM's layers ride in the decoder's fused launches), forked (the LM on the side stream), no LM."""
         rec, lib = self.rec, L.load()
         dec, lm, beam = rec.model.decoder, rec.lm, rec.beam_width
-        adt = ops.act_dtype()
         main = torch.cuda.current_stream()
         stream = C.c_void_p(main.cuda_stream)
+        embed = lambda m: ops.decode_embed(self.preds[cur], self.pos[cur], m.embedding.weight)    # noqa: E731
         lm_logits = None
-        paired = False
         if self.paired:
-            x = ops.decode_embed(self.preds[cur], self.pos[cur], dec.embedding.weight)
-            xl = ops.decode_embed(self.preds[cur], self.pos[cur], lm.embedding.weight)
-            if ops.lp_of(x) is not None and ops.lp_of(xl) is not None:
-                x, yl = self._fused_stacks_paired(x, xl, cur)
-                lm_logits = self.out_lm(yl) if self.out_lm is not None else ops.linear(yl, lm.output_project.weight, lm.output_project.bias)
-                paired = True
-        if paired:
-            pass
-        elif self.side is not None:
-            self.side.wait_stream(main)                   # fork
-            with torch.cuda.stream(self.side), ops.workspace_lane(self.side_ws):
-                lm_logits = self._lm_logits(cur)
-        elif lm is not None:
-            lm_logits = self._lm_logits(cur)
-        if not paired:
-            x = ops.decode_embed(self.preds[cur], self.pos[cur], dec.embedding.weight)
-        fused_dec = (self.fused_dec and ops.lp_of(x) is not None) or paired
-        if fused_dec and not paired:
-            x = self._fused_stack(x, dec.blocks, self.dec_cache, self.mem_kv, cur)
-        for blk, cache, kv in (() if fused_dec else zip(dec.blocks, self.dec_cache, self.mem_kv)):
-            x = self._stack_step(x, blk, cache, cur, getattr(blk, 'concat_linear1', None))
-            a = blk.src_attn
-            if ops.lp_of(x) is not None and x.dtype == torch.float32 and self._fused_tail_ok(blk, True) and kv.shape[2] == 512:
-                x = self._fused_tail(blk, x, kv, blk.norm2, blk.norm3)
-                continue
-            q = ops.linear(x, a.q_proj.weight, a.q_proj.bias, out_dtype=adt)
-            # the beam hypotheses of an utterance are the query rows of ONE attention problem over its memory
-            ctx = ops.CrossAttentionFn.apply(q.view(self.b, beam, -1), kv, self.mem_mask, a.nheads)
-            x = self._close(blk, getattr(blk, 'concat_linear2', None), blk.norm3 if blk.normalize_before else blk.norm2,
-                            x, a, ctx.view(self.R, -1))
-            x = self._ffn(blk, blk.norm3, x)
+            x, yl = self._walk([self._dec_chain(embed(dec), cur), self._lm_chain(embed(lm), cur)])
+            lm_logits = _output(self.out_lm, lm.output_project, yl)
+        else:
+            if self.side is not None:
+                self.side.wait_stream(main)                   # fork
+                with torch.cuda.stream(self.side), ops.workspace_lane(self.side_ws):
+                    lm_logits = self._lm_logits(cur)
+            x = embed(dec)                                    # after the fork: queued before it, the LM branch would wait for it
+            if self.fused_dec:
+                x = self._walk([self._dec_chain(x, cur)])[0]
+            else:
+                for blk, cache, kv, tail in zip(dec.blocks, self.dec_cache, self.mem_kv, self.tail_dec):
+                    x = self._layer(x, blk, cache, cur, tail, getattr(blk, 'concat_linear1', None), blk.norm3, kv,
+                                    getattr(blk, 'concat_linear2', None))
         if dec.normalize_before:
             x = ops.add_layernorm(x, None, dec.after_norm.weight, dec.after_norm.bias, 0.0, dec.after_norm.eps)
         V = dec.output_layer.weight.shape[0]
-        logits = self.out_dec(x) if self.out_dec is not None else ops.linear(x, dec.output_layer.weight, dec.output_layer.bias)
+        logits = _output(self.out_dec, dec.output_layer, x)
         ld = logits.size(-1)                             # V, or V padded to a multiple of 8 (_PaddedOutput)
         if self.side is not None:
             main.wait_stream(self.side)                   # join: the LM's logits are ready
