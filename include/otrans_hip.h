@@ -37,9 +37,9 @@ extern "C" {
 
 /* ABI version of THIS header: bumped whenever a signature, a descriptor struct or the meaning of an argument changes (600: round 6;
  * 300 was rounds 3-5, during which otr_optimizer_step, otr_ln_desc_t, otr_wgrad_item_t and otr_beam_prune_cached changed without a
- * bump).  A binding compares otr_version() with the OTR_ABI_VERSION it was written against BEFORE its first call and refuses a
+ * bump; 602: the rescoring entries, additions only).  A binding compares otr_version() with the OTR_ABI_VERSION it was written against BEFORE its first call and refuses a
  * library that answers anything else: descriptors are passed by pointer and read at the library's idea of their size. */
-#define OTR_ABI_VERSION 601
+#define OTR_ABI_VERSION 602
 int32_t otr_version(void);
 /* OTR_BF16 or OTR_F16: the 16-bit type this library was built for */
 int32_t otr_half_type(void);
@@ -737,6 +737,40 @@ int32_t otr_beam_prune_cached_joint(const float* k_score, const int64_t* k_idx, 
                                     uint8_t* flag_out, int64_t* preds_out, int32_t* n_finished, const int32_t* ksrc_in, int32_t* jsrc_out,
                                     void* stream);
 
+/* ---- attention rescoring of the CTC n-best (SpeechToTextRecognizer rescore=True: two-pass decoding), csrc/rescore.hip.  f32 in every
+ *      build.  The first pass is otr_ctc_topk + otr_ctc_beam_search: per utterance b the W hypotheses h of the CTC beam, tokens int64
+ *      [B, W, T] padded with -1, out_len int32 [B, W], scores f32 [B, W] in descending order.  lambda = ctc_weight in [0, 1],
+ *      mu = lm_weight (0 without an LM).  BOS = EOS.  A hypothesis is RESCORABLE when its score is above -inf and len(h) + 1 <= max_len.
+ *   att(h) = sum over l = 0 .. len(h) of log_softmax(decoder([BOS] + h, memory_b, mask_b))[l, (h + [EOS])[l]]   (teacher-forced, one pass)
+ *   lm(h)  = the same sum over the language model's logits on [BOS] + h
+ *   ctc(h) = the beam's own score of h: log(pb + pnb) at the last frame, the beam's approximation of log P_ctc(h | x), taken as is
+ *   total(h) = (1 - lambda) att(h) + lambda ctc(h) + mu lm(h), the combination of the joint search above; with penalty != 0 divided by
+ *     ((lamda + len(h)) / (lamda + 1)) ** penalty, as the beam search's n-best selection does (recognize/speech2text.py:76-79).
+ *   Slots that are not rescorable (and NaN totals) get total = -inf.  Order: total descending, ties -> the lower CTC rank; -inf entries
+ *   come last in CTC order, so an utterance without a rescorable hypothesis returns its CTC order with scores -inf.  The empty
+ *   hypothesis is an ordinary one: input [BOS], target [EOS].
+ * otr_rescore_pack: for each of the n_hyp = B * W hypotheses: ys_in int64 [n_hyp, max_len] = BOS, the tokens, then EOS as filler (any
+ *   valid id would do: the causal mask keeps the tail from mattering; tokens are clamped into [0, V)); ys_out int64 [n_hyp, max_len] =
+ *   the tokens, EOS, then -1; n_rows int32 [n_hyp] = len + 1, or 0 where the slot is not rescorable (then ys_in = BOS, EOS ..., ys_out
+ *   = -1).  V <= 8192.
+ * otr_rescore_score: logits f32 [n_hyp * max_len, ld >= V], row (h, l) at logits + (h*max_len + l)*ld.  att_score[h] = sum over
+ *   l < n_rows[h] of logits[h, l, ys_out[h, l]] - logsumexp(logits[h, l, :V]); -inf where n_rows[h] == 0.  Rows l >= n_rows[h] are not
+ *   read; a row is read once, with 16-byte loads when logits % 16 == 0 and ld % 4 == 0; no [rows, V] log-softmax is written; the sum
+ *   runs in a fixed order (the same bits on every run).  lm_logits (may be NULL; row stride ld_lm) is scored the same way into lm_score
+ *   by the same launch.
+ * otr_rescore_select: one workgroup per utterance: forms total [B, W] (CTC order), ranks by counting, writes perm int32 [B, W] (rank ->
+ *   CTC slot) and the nbest best: nbest_tokens int64 [B, nbest, T] (the search's rows, -1 padded), nbest_len int32 [B, nbest],
+ *   nbest_score f32 [B, nbest].  lm_score may be NULL.  W <= 32, 1 <= nbest <= W, 0 <= ctc_weight <= 1.
+ * Three launches, no allocation, memset or host synchronisation: capturable into a graph behind the search. */
+int32_t otr_rescore_pack(const int64_t* tokens, const int32_t* out_len, const float* scores, int64_t n_hyp, int32_t T, int32_t max_len,
+                         int32_t V, int32_t bos, int32_t eos, int64_t* ys_in, int64_t* ys_out, int32_t* n_rows, void* stream);
+int32_t otr_rescore_score(const float* logits, int64_t ld, const float* lm_logits, int64_t ld_lm, const int64_t* ys_out, int64_t ld_ys,
+                          const int32_t* n_rows, int64_t n_hyp, int32_t max_len, int32_t V, float* att_score, float* lm_score, void* stream);
+int32_t otr_rescore_select(const int64_t* tokens, const int32_t* out_len, const float* ctc_score, const int32_t* n_rows,
+                           const float* att_score, const float* lm_score, int32_t B, int32_t W, int32_t T, int32_t nbest, float ctc_weight,
+                           float lm_weight, float penalty, float lamda, float* total, int32_t* perm, int64_t* nbest_tokens,
+                           int32_t* nbest_len, float* nbest_score, void* stream);
+
 /* ---- transposed copies of many matrices in ONE launch (the W^T bf16 shadows that turn dx = dy.W into a
  *      forward-type GEMM; refreshed after every optimizer step).  table: DEVICE int64 [n_mats,4] rows of
  *      {element offset, rows, cols, first tile}; matrix i is src+offset [rows,cols] row-major and is written to
@@ -859,6 +893,13 @@ int32_t otr_dec_self_step(const otr_dec_ln_t* ln, int64_t R, const void* wqkv_pa
 int32_t otr_dec_cross_fwd(const otr_dec_ln_t* ln, int32_t B, int32_t L, const void* wq_pack, const float* bq, const void* wo_pack,
                           const void* kv, int64_t kv_bs, int64_t kv_ts, int32_t koff, int32_t voff, const uint8_t* key_mask, int32_t Tk,
                           void* q16, void* ctx16, float* lse, void* slabs, void* stream);
+/* otr_dec_cross_fwd_shared: otr_dec_cross_fwd for B sequences of which every `share` consecutive ones attend to the SAME encoder memory
+ *      (the W hypotheses of an utterance in attention rescoring): sequence s reads kv[(s / share)*kv_bs + t*kv_ts + c] and key_mask row
+ *      s / share; kv and key_mask hold B / share memories, B % share == 0.  Everything else, and the result for share == 1, as
+ *      otr_dec_cross_fwd.  Forward only. */
+int32_t otr_dec_cross_fwd_shared(const otr_dec_ln_t* ln, int32_t B, int32_t L, const void* wq_pack, const float* bq, const void* wo_pack,
+                                 const void* kv, int64_t kv_bs, int64_t kv_ts, int32_t koff, int32_t voff, const uint8_t* key_mask,
+                                 int32_t Tk, int32_t share, void* q16, void* ctx16, float* lse, void* slabs, void* stream);
 int64_t otr_dec_ffn_hsave_bytes(int64_t R, int32_t F);
 int32_t otr_dec_ffn_fwd(const otr_dec_ln_t* ln, int64_t R, const void* w1_pack, const float* b1, const void* w2_pack, int32_t F, int32_t S,
                         void* slabs, void* hsave, void* stream);

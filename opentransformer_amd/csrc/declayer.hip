@@ -486,12 +486,15 @@ struct DlCrossArgs {
   float* lse;                                // [B, H, L] out
   uint16_t* slabs;                           // [H][R][256] 16-bit out
   float scale;
+  int share;                                 // SHARED kernel only: sequences per memory (sequence s reads memory and mask row s / share)
 };
 
 struct DlKvTile { uint4 k[4]; uint4 v[4]; uint32_t valid; };
 
+template <bool SHARED>
 __device__ __forceinline__ void dl_load_kv(DlKvTile& t, const DlCrossArgs& p, int b, int j0, int h, int lane) {
   const int m = lane & 31, hi = lane >> 5;
+  if constexpr (SHARED) b /= p.share;
   const uint16_t* base = p.kv + (int64_t)b * p.kv_bs;
   const uint16_t* kr = base + (int64_t)min(j0 + m, p.Tk - 1) * p.kv_ts + p.koff + DL_DK * h + 8 * hi;
 #pragma unroll
@@ -504,6 +507,7 @@ __device__ __forceinline__ void dl_load_kv(DlKvTile& t, const DlCrossArgs& p, in
   t.valid = (uint32_t)__ballot(ok != 0);
 }
 
+template <bool SHARED>
 __global__ __launch_bounds__(512, 1) void dec_cross_fwd_kernel(DlCrossArgs p) {
   constexpr int OS = DL_DK + 4;               // floats per row of a wave's partial context
   __shared__ __attribute__((aligned(16))) unsigned char smem[DL_RB * DL_YS + 2 * DL_RB * DL_HS + 8 * DL_DK * DL_VT + 8 * DL_RB * OS * 4 +
@@ -533,7 +537,7 @@ __global__ __launch_bounds__(512, 1) void dec_cross_fwd_kernel(DlCrossArgs p) {
   DlKvTile cur;
   {
     const int it = min(wid, nit - 1);
-    dl_load_kv(cur, p, u0 + it / ntile, (it % ntile) * 32, h, lane);
+    dl_load_kv<SHARED>(cur, p, u0 + it / ntile, (it % ntile) * 32, h, lane);
   }
   DlStream<1, 16, 16> sq;
   if (wid < 2) sq.fill(p.wq, 16, 2 * h + wid, 1, 0, lane);
@@ -543,7 +547,7 @@ __global__ __launch_bounds__(512, 1) void dec_cross_fwd_kernel(DlCrossArgs p) {
   DlKvTile alt;
   if (wid + 8 < nit) {                                                // this wave's second tile lands under the q projection; one utterance of
     const int it = wid + 8;                                           // <= 256 frames per workgroup (the shipped shapes) has none: 8 KiB per wave
-    dl_load_kv(alt, p, u0 + it / ntile, (it % ntile) * 32, h, lane);  // that the CU's ingest does not spend
+    dl_load_kv<SHARED>(alt, p, u0 + it / ntile, (it % ntile) * 32, h, lane);  // that the CU's ingest does not spend
   } else {
     alt = DlKvTile{};
   }
@@ -577,7 +581,7 @@ __global__ __launch_bounds__(512, 1) void dec_cross_fwd_kernel(DlCrossArgs p) {
   unsigned char* vt = vtw + wid * (DL_DK * DL_VT);
   auto load_tile = [&](DlKvTile& t, int it) {
     const int itc = min(it, nit - 1);                                   // past the end: a valid tile, loaded and never used
-    dl_load_kv(t, p, u0 + itc / ntile, (itc % ntile) * 32, h, lane);
+    dl_load_kv<SHARED>(t, p, u0 + itc / ntile, (itc % ntile) * 32, h, lane);
   };
   auto consume = [&](const DlKvTile& t, int it) {
     const int u = it / ntile;
@@ -1720,21 +1724,42 @@ extern "C" int32_t otr_dec_self_step_pair(const otr_dec_self_step_t* x, const ot
   return otr_check_launch("dec_self_step_pair");
 }
 
+static int32_t dl_fill_cross(const char* who, DlCrossArgs& a, const otr_dec_ln_t* ln, int32_t B, int32_t L, const void* wq_pack, const float* bq,
+                             const void* wo_pack, const void* kv, int64_t kv_bs, int64_t kv_ts, int32_t koff, int32_t voff, const uint8_t* key_mask,
+                             int32_t Tk, void* q16, void* ctx16, float* lse, void* slabs) {
+  if (int32_t e = dl_check_geom(who, B, L, a.g)) return e;
+  if (int32_t e = dl_check_ln(who, ln, (int64_t)B * L, a.ln)) return e;
+  OTR_REQUIRE(wq_pack && bq && wo_pack && kv && q16 && ctx16 && lse && slabs, "%s: null pointer", who);
+  OTR_REQUIRE(Tk > 0 && kv_ts % 8 == 0 && kv_bs % 8 == 0 && koff % 8 == 0 && voff % 8 == 0, "%s: key / value rows must be 16-byte aligned", who);
+  OTR_REQUIRE(((uintptr_t)wq_pack | (uintptr_t)bq | (uintptr_t)wo_pack | (uintptr_t)kv | (uintptr_t)q16 | (uintptr_t)ctx16 | (uintptr_t)slabs) % 16 == 0,
+              "%s: buffers must be 16-byte aligned", who);
+  a.wq = (const uint4*)wq_pack; a.bq = bq; a.wo = (const uint4*)wo_pack; a.kv = (const uint16_t*)kv; a.kv_bs = kv_bs; a.kv_ts = kv_ts;
+  a.koff = koff; a.voff = voff; a.kmask = key_mask; a.Tk = Tk; a.q16 = (uint16_t*)q16; a.ctx16 = (uint16_t*)ctx16; a.lse = lse; a.slabs = (uint16_t*)slabs;
+  a.scale = 0.125f; a.trace = g_otr_trace; a.share = 1;
+  return 0;
+}
+
 extern "C" int32_t otr_dec_cross_fwd(const otr_dec_ln_t* ln, int32_t B, int32_t L, const void* wq_pack, const float* bq, const void* wo_pack,
                                      const void* kv, int64_t kv_bs, int64_t kv_ts, int32_t koff, int32_t voff, const uint8_t* key_mask,
                                      int32_t Tk, void* q16, void* ctx16, float* lse, void* slabs, void* stream) {
   DlCrossArgs a{};
-  if (int32_t e = dl_check_geom("dec_cross_fwd", B, L, a.g)) return e;
-  if (int32_t e = dl_check_ln("dec_cross_fwd", ln, (int64_t)B * L, a.ln)) return e;
-  OTR_REQUIRE(wq_pack && bq && wo_pack && kv && q16 && ctx16 && lse && slabs, "dec_cross_fwd: null pointer");
-  OTR_REQUIRE(Tk > 0 && kv_ts % 8 == 0 && kv_bs % 8 == 0 && koff % 8 == 0 && voff % 8 == 0, "dec_cross_fwd: key / value rows must be 16-byte aligned");
-  OTR_REQUIRE(((uintptr_t)wq_pack | (uintptr_t)bq | (uintptr_t)wo_pack | (uintptr_t)kv | (uintptr_t)q16 | (uintptr_t)ctx16 | (uintptr_t)slabs) % 16 == 0,
-              "dec_cross_fwd: buffers must be 16-byte aligned");
-  a.wq = (const uint4*)wq_pack; a.bq = bq; a.wo = (const uint4*)wo_pack; a.kv = (const uint16_t*)kv; a.kv_bs = kv_bs; a.kv_ts = kv_ts;
-  a.koff = koff; a.voff = voff; a.kmask = key_mask; a.Tk = Tk; a.q16 = (uint16_t*)q16; a.ctx16 = (uint16_t*)ctx16; a.lse = lse; a.slabs = (uint16_t*)slabs;
-  a.scale = 0.125f; a.trace = g_otr_trace;
-  hipLaunchKernelGGL(dec_cross_fwd_kernel, dim3(dl_grid(DL_H, (B + a.g.G - 1) / a.g.G)), dim3(512), 0, (hipStream_t)stream, a);
+  if (int32_t e = dl_fill_cross("dec_cross_fwd", a, ln, B, L, wq_pack, bq, wo_pack, kv, kv_bs, kv_ts, koff, voff, key_mask, Tk, q16, ctx16, lse, slabs))
+    return e;
+  hipLaunchKernelGGL(dec_cross_fwd_kernel<false>, dim3(dl_grid(DL_H, (B + a.g.G - 1) / a.g.G)), dim3(512), 0, (hipStream_t)stream, a);
   return otr_check_launch("dec_cross_fwd");
+}
+
+extern "C" int32_t otr_dec_cross_fwd_shared(const otr_dec_ln_t* ln, int32_t B, int32_t L, const void* wq_pack, const float* bq, const void* wo_pack,
+                                            const void* kv, int64_t kv_bs, int64_t kv_ts, int32_t koff, int32_t voff, const uint8_t* key_mask,
+                                            int32_t Tk, int32_t share, void* q16, void* ctx16, float* lse, void* slabs, void* stream) {
+  DlCrossArgs a{};
+  OTR_REQUIRE(share >= 1 && B > 0 && B % share == 0, "dec_cross_fwd_shared: %d sequences are not a multiple of share=%d", B, share);
+  if (int32_t e = dl_fill_cross("dec_cross_fwd_shared", a, ln, B, L, wq_pack, bq, wo_pack, kv, kv_bs, kv_ts, koff, voff, key_mask, Tk, q16, ctx16,
+                                lse, slabs))
+    return e;
+  a.share = share;
+  hipLaunchKernelGGL(dec_cross_fwd_kernel<true>, dim3(dl_grid(DL_H, (B + a.g.G - 1) / a.g.G)), dim3(512), 0, (hipStream_t)stream, a);
+  return otr_check_launch("dec_cross_fwd_shared");
 }
 
 extern "C" int64_t otr_dec_ffn_hsave_bytes(int64_t R, int32_t F) { return R > 0 && F > 0 ? ((R + DL_RB - 1) / DL_RB) * (int64_t)(F / 32) * 4096 : 0; }

@@ -700,25 +700,42 @@ class TransformerDecoder(nn.Module):
         if share_embedding:
             self.output_layer.weight = self.embedding.weight      # decoder/transformer.py:156-158
 
-    def forward(self, targets, memory, memory_mask):
+    def hidden(self, targets, memory, memory_mask, share=1):
+        """the stack below the output layer.  share > 1 (inference: attention rescoring): every `share` consecutive rows of targets
+        attend to the same row of memory / memory_mask.  Where the fused stack serves the shape, the memory's keys / values are projected
+        once per memory row and the cross-attention launches address them through the divisor (otr_dec_cross_fwd_shared); every other
+        shape runs the per-operator layers on the memory repeated `share` times."""
         x = ops.embed_posenc(targets, self.embedding.weight)
+        cross_kv = len(self.blocks) > 1 and memory.is_cuda and not any(b.src_attn.share_vk_proj for b in self.blocks)
+        S = ops.decoder_stack_applies(x, memory, self.blocks, self.normalize_before) if cross_kv else 0
+        if S and not all(b.residual_dropout == self.blocks[0].residual_dropout and b.norm1.eps == self.blocks[0].norm1.eps
+                         and b.norm2.eps == b.norm1.eps and b.norm3.eps == b.norm1.eps for b in self.blocks):
+            S = 0
+        if share > 1 and not (S and not torch.is_grad_enabled()):
+            lp = ops.lp_of(memory)
+            memory = memory.repeat_interleave(share, dim=0)
+            if lp is not None:
+                memory = ops.attach_lp(memory, lp.repeat_interleave(share, dim=0))
+            memory_mask, share = memory_mask.repeat_interleave(share, dim=0), 1
         kv = None
-        if (len(self.blocks) > 1 and memory.is_cuda and not any(b.src_attn.share_vk_proj for b in self.blocks)):
+        if cross_kv:
             # keys / values of every layer from ONE GEMM over the shared memory (ops.CrossKVAllFn)
             shared = ops.CrossKVShared(len(self.blocks))
             wb = [t for b in self.blocks for t in (b.src_attn.vk_proj.weight, b.src_attn.vk_proj.bias)]
             kv = (ops.CrossKVAllFn.apply(memory, shared, *wb), shared)
-        S = ops.decoder_stack_applies(x, memory, self.blocks, self.normalize_before) if kv is not None else 0
-        if S and all(b.residual_dropout == self.blocks[0].residual_dropout and b.norm1.eps == self.blocks[0].norm1.eps
-                     and b.norm2.eps == b.norm1.eps and b.norm3.eps == b.norm1.eps for b in self.blocks):
+        if S:
             # the whole stack as three launches per layer (csrc/declayer.hip): cut along (utterance group, head) / (rows, hidden slice)
-            x = ops.decoder_stack(x, kv[0], ops._mask_u8(memory_mask, memory.size(0), memory.size(1)), self.blocks, S)
+            x = ops.decoder_stack(x, kv[0], ops._mask_u8(memory_mask, memory.size(0), memory.size(1)), self.blocks, S, share)
         else:
             mm = memory_mask.to(torch.uint8).unsqueeze(1)
             for i, block in enumerate(self.blocks):
                 x, _ = block(x, None, memory, mm, kv_all=(kv[0], i, kv[1]) if kv is not None else None)   # None -> causal self-attention
         if self.normalize_before:
             x = _norm(self.after_norm, x)
+        return x
+
+    def forward(self, targets, memory, memory_mask):
+        x = self.hidden(targets, memory, memory_mask)
         logits = ops.linear(x, self.output_layer.weight, self.output_layer.bias)
         return logits, {}
 

@@ -2304,10 +2304,12 @@ def _grad_b(a2, b):
 class DecoderStackFn(torch.autograd.Function):
     """TransformerDecoder.forward between the embedding and the output layer (decoder/transformer.py:172-176): n post-norm layers of
     [causal self-attention, cross-attention over the encoder memory, GLU feed-forward], each closed by dropout + residual + LayerNorm.
-    x0 [B,L,256] f32 with its 16-bit twin; kv_all [B,T,n*512] 16-bit = every layer's keys | values of the memory (CrossKVAllFn)."""
+    x0 [B,L,256] f32 with its 16-bit twin; kv_all [B,T,n*512] 16-bit = every layer's keys | values of the memory (CrossKVAllFn).
+    share > 1 (forward only): every `share` consecutive sequences attend to the same memory -- kv_all and kmask hold B / share
+    memories (otr_dec_cross_fwd_shared: the W hypotheses of an utterance in attention rescoring)."""
 
     @staticmethod
-    def forward(ctx, x0, kv_all, kmask, n_layers, p_drop, eps, S, *params):
+    def forward(ctx, x0, kv_all, kmask, n_layers, p_drop, eps, S, share, *params):
         _cuda(x0, kv_all)
         ctx.set_materialize_grads(False)
         lib = L.load()
@@ -2315,6 +2317,8 @@ class DecoderStackFn(torch.autograd.Function):
         R, H = B * Lq, 4
         T, W = kv_all.shape[1], kv_all.shape[2]
         dev, hdt = x0.device, half_dtype()
+        assert share >= 1 and kv_all.shape[0] * share == B
+        ctx.share = share
         assert d == 256 and kv_all.is_contiguous() and kv_all.dtype == hdt and W == n_layers * 512 and len(params) == DEC_LAYER_PARAMS * n_layers
         xres, x16 = x0.reshape(R, d).contiguous(), lp_of(x0).reshape(R, d).contiguous()
         seed = rng_seed_tensor(dev) if p_drop > 0 else None
@@ -2368,9 +2372,14 @@ class DecoderStackFn(torch.autograd.Function):
             lnB, y1, y116, rec['ln1'] = ln_out(y0, slA, 4, bo, g1, be1)
             q16, ctx2, lse2 = h16(R, d), h16(R, d), f32(B, H, Lq)
             fl_cross = 2.0 * R * d * (d + d) + 4.0 * R * T * d
-            L.check(_timed('dec_cross_fwd', {'flops': fl_cross}, lambda lnB=lnB, pk=pk, bq=bq, q16=q16, ctx2=ctx2, lse2=lse2, l=l: lib.otr_dec_cross_fwd(
-                C.byref(lnB), B, Lq, _p(pk[2][0]), _p(bq), _p(pk[3][0]), _p(kv_all), T * W, W, l * 512, l * 512 + 256, _p(kmask), T, _p(q16), _p(ctx2),
-                _p(lse2), _p(slB), _stream())), 'otr_dec_cross_fwd')
+            if share == 1:
+                L.check(_timed('dec_cross_fwd', {'flops': fl_cross}, lambda lnB=lnB, pk=pk, bq=bq, q16=q16, ctx2=ctx2, lse2=lse2, l=l: lib.otr_dec_cross_fwd(
+                    C.byref(lnB), B, Lq, _p(pk[2][0]), _p(bq), _p(pk[3][0]), _p(kv_all), T * W, W, l * 512, l * 512 + 256, _p(kmask), T, _p(q16), _p(ctx2),
+                    _p(lse2), _p(slB), _stream())), 'otr_dec_cross_fwd')
+            else:
+                L.check(lib.otr_dec_cross_fwd_shared(C.byref(lnB), B, Lq, _p(pk[2][0]), _p(bq), _p(pk[3][0]), _p(kv_all), T * W, W, l * 512,
+                                                     l * 512 + 256, _p(kmask), T, share, _p(q16), _p(ctx2), _p(lse2), _p(slB), _stream()),
+                        'otr_dec_cross_fwd_shared')
             lnC, y2, y216, rec['ln2'] = ln_out(y1, slB, 4, bo2, g2, be2)
             hsave = torch.empty(lib.otr_dec_ffn_hsave_bytes(R, F) // 2, dtype=hdt, device=dev) if need else None
             L.check(_timed('dec_ffn_fwd', {'flops': 6.0 * R * F * d}, lambda lnC=lnC, pk=pk, b1=b1, hsave=hsave: lib.otr_dec_ffn_fwd(
@@ -2391,7 +2400,8 @@ class DecoderStackFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, _dy16=None):
-        n_in = 7
+        n_in = 8
+        assert ctx.share == 1, 'the shared-memory decoder stack is forward only'
         if dy is None:
             return (None,) * (n_in + len(ctx.params))
         lib = L.load()
@@ -2452,7 +2462,7 @@ class DecoderStackFn(torch.autograd.Function):
                 dx0 = f32(R, d)
                 L.check(lib.otr_dec_sum(_p(dskip), _p(slabs), nslab, R, _p(dx0), st), 'otr_dec_sum')
                 dx0 = dx0.view(B, Lq, d)
-        return (dx0, dkv if ctx.needs_input_grad[1] else None, None, None, None, None, None, *grads)
+        return (dx0, dkv if ctx.needs_input_grad[1] else None, None, None, None, None, None, None, *grads)
 
 
 def decoder_stack_applies(x0, memory, blocks, normalize_before):
@@ -2482,7 +2492,7 @@ def decoder_stack_applies(x0, memory, blocks, normalize_before):
     return dec_ffn_slices(F)
 
 
-def decoder_stack(x0, kv_all, kmask_u8, blocks, S):
+def decoder_stack(x0, kv_all, kmask_u8, blocks, S, share=1):
     p = blocks[0].residual_dropout if blocks[0].training else 0.0
     params = []
     for b in blocks:
@@ -2490,7 +2500,7 @@ def decoder_stack(x0, kv_all, kmask_u8, blocks, S):
         params += [sa.qvk_proj.weight, sa.qvk_proj.bias, sa.output_proj.weight, sa.output_proj.bias, b.norm1.weight, b.norm1.bias,
                    ca.q_proj.weight, ca.q_proj.bias, ca.output_proj.weight, ca.output_proj.bias, b.norm2.weight, b.norm2.bias,
                    ff.w_1.weight, ff.w_1.bias, ff.w_2.weight, ff.w_2.bias, b.norm3.weight, b.norm3.bias]
-    y, y16 = DecoderStackFn.apply(x0, kv_all, kmask_u8, len(blocks), float(p), float(blocks[0].norm1.eps), S, *params)
+    y, y16 = DecoderStackFn.apply(x0, kv_all, kmask_u8, len(blocks), float(p), float(blocks[0].norm1.eps), S, int(share), *params)
     return attach_lp(y, y16)
 
 
@@ -3709,3 +3719,80 @@ def ctc_prefix_score(log_probs, lengths, cand_idx, preds, t, rows_per_utt, blank
                                           _p(k_idx) if k_idx is not None else None, _p(k_src) if k_src is not None else None, _stream()),
             'otr_ctc_prefix_score')
     return psi_o
+
+
+# ------------------------------------------------------------------ attention rescoring of the CTC n-best (csrc/rescore.hip)
+RESCORE_MAX_W, RESCORE_MAX_V = 32, 8192
+
+
+def _rescore_check(who, W, V, nbest, ctc_weight):
+    """the limits of include/otrans_hip.h, refused on the host before the first launch"""
+    if not 1 <= int(W) <= RESCORE_MAX_W:
+        raise ValueError('%s: W=%d hypotheses per utterance must be in [1, %d]' % (who, W, RESCORE_MAX_W))
+    if not 1 <= int(V) <= RESCORE_MAX_V:
+        raise ValueError('%s: vocabulary V=%d must be in [1, %d]' % (who, V, RESCORE_MAX_V))
+    if not 1 <= int(nbest) <= int(W):
+        raise ValueError('%s: nbest=%d must be in [1, W=%d]' % (who, nbest, W))
+    if not 0.0 <= float(ctc_weight) <= 1.0:
+        raise ValueError('%s: ctc_weight=%r must be in [0, 1]' % (who, ctc_weight))
+
+
+def rescore_pack(tokens, out_len, scores, max_len, V, bos=1, eos=1):
+    """The CTC beam (ops.ctc_prefix_beam_search's tokens int64 [B, W, T] padded with -1, out_len [B, W], scores [B, W]) as ONE
+    teacher-forced decoder batch (include/otrans_hip.h otr_rescore_pack): ys_in int64 [B*W, max_len] = BOS, the tokens, EOS filler;
+    ys_out int64 [B*W, max_len] = the tokens, EOS, then -1; n_rows int32 [B*W] = len + 1, or 0 for a dead or too long slot.  One launch
+    on the current stream, capturable."""
+    B, W, T = tokens.shape
+    _rescore_check('rescore_pack', W, V, 1, 0.0)
+    _cuda(tokens, out_len, scores)
+    if tokens.dtype != torch.int64 or out_len.dtype != torch.int32 or scores.dtype != torch.float32:
+        raise L.OtransHipError('rescore_pack: tokens int64, out_len int32, scores f32 expected')
+    tokens, out_len, scores = tokens.contiguous(), out_len.contiguous(), scores.contiguous()
+    dev = tokens.device
+    ys_in = torch.empty((B * W, max_len), dtype=torch.int64, device=dev)
+    ys_out = torch.empty((B * W, max_len), dtype=torch.int64, device=dev)
+    n_rows = torch.empty((B * W,), dtype=torch.int32, device=dev)
+    L.check(L.load().otr_rescore_pack(_p(tokens), _p(out_len), _p(scores), B * W, T, int(max_len), int(V), int(bos), int(eos), _p(ys_in),
+                                      _p(ys_out), _p(n_rows), _stream()), 'otr_rescore_pack')
+    return ys_in, ys_out, n_rows
+
+
+def attention_rescore(logits, tokens, out_len, scores, max_len, V, ctc_weight, lm_logits=None, lm_weight=0.0, nbest=1, penalty=0.0,
+                      lamda=5.0, packed=None, bos=1, eos=1):
+    """The second pass of two-pass decoding after the decoder (include/otrans_hip.h otr_rescore_*).  logits f32 [B*W * max_len, >= V]
+    (any leading shape; unit stride along the vocabulary): the teacher-forced decoder output on rescore_pack's ys_in; lm_logits the same
+    from the language model, or None.  tokens / out_len / scores: the search's outputs.  total = (1 - ctc_weight) att + ctc_weight ctc
+    + lm_weight lm (/ the length penalty), sorted descending, ties to the lower CTC rank, dead and too long slots (-inf) last.
+    `packed`: rescore_pack's result for these hypotheses (else it is formed here: one more launch).
+    Returns a dict: tokens int64 [B, nbest, T] (-1 padded), len int32 [B, nbest], scores f32 [B, nbest], perm int32 [B, W] (rank -> CTC
+    slot), total / att / lm f32 [B, W] in CTC order (lm None without lm_logits).  Two launches, no host synchronisation: capturable."""
+    B, W, T = tokens.shape
+    _rescore_check('attention_rescore', W, V, nbest, ctc_weight)
+    _cuda(logits, tokens, out_len, scores)
+    nh = B * W
+
+    def rows(t, who):
+        if t.dtype != torch.float32 or t.stride(-1) != 1 or t.shape[-1] < V:
+            raise L.OtransHipError('attention_rescore: %s must be f32 with >= V=%d contiguous columns' % (who, V))
+        t2 = t.reshape(-1, t.shape[-1])
+        if t2.shape[0] != nh * max_len:
+            raise L.OtransHipError('attention_rescore: %s has %d rows, B*W*max_len = %d expected' % (who, t2.shape[0], nh * max_len))
+        return t2 if t2.stride(1) == 1 and t2.stride(0) >= V else t2.contiguous()
+    lg = rows(logits, 'logits')
+    lmg = rows(lm_logits, 'lm_logits') if lm_logits is not None else None
+    tokens, out_len, scores = tokens.contiguous(), out_len.contiguous(), scores.contiguous()
+    _, ys_out, n_rows = packed if packed is not None else rescore_pack(tokens, out_len, scores, max_len, V, bos, eos)
+    dev = tokens.device
+    f32 = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)    # noqa: E731
+    i32 = lambda *sh: torch.empty(sh, dtype=torch.int32, device=dev)      # noqa: E731
+    att, lm = f32(B, W), (f32(B, W) if lmg is not None else None)
+    total, perm = f32(B, W), i32(B, W)
+    nb_tok, nb_len, nb_score = torch.empty((B, nbest, T), dtype=torch.int64, device=dev), i32(B, nbest), f32(B, nbest)
+    lib = L.load()
+    L.check(lib.otr_rescore_score(_p(lg), lg.stride(0), _p(lmg) if lmg is not None else None, lmg.stride(0) if lmg is not None else 0,
+                                  _p(ys_out), ys_out.stride(0), _p(n_rows), nh, int(max_len), int(V), _p(att),
+                                  _p(lm) if lm is not None else None, _stream()), 'otr_rescore_score')
+    L.check(lib.otr_rescore_select(_p(tokens), _p(out_len), _p(scores), _p(n_rows), _p(att), _p(lm) if lm is not None else None, B, W, T,
+                                   int(nbest), float(ctc_weight), float(lm_weight or 0.0), float(penalty or 0.0), float(lamda), _p(total),
+                                   _p(perm), _p(nb_tok), _p(nb_len), _p(nb_score), _stream()), 'otr_rescore_select')
+    return {'tokens': nb_tok, 'len': nb_len, 'scores': nb_score, 'perm': perm, 'total': total, 'att': att, 'lm': lm}

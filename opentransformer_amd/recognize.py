@@ -51,11 +51,14 @@ class TransformerLanguageModel(nn.Module):
             self.output_project.weight = self.embedding.weight
         self.crit = LabelSmoothingLoss(size=self.vocab_size, smoothing=self.smoothing, padding_idx=PAD)
 
-    def logits(self, tokens):
+    def hidden(self, tokens):
         x = ops.embed_posenc(tokens.contiguous(), self.embedding.weight)
         for block in self.blocks:
             x, _ = block(x, None, causal=True)
-        return ops.linear(x, self.output_project.weight, self.output_project.bias)
+        return x
+
+    def logits(self, tokens):
+        return ops.linear(self.hidden(tokens), self.output_project.weight, self.output_project.bias)
 
     def forward(self, inputs, targets):
         return self.crit(self.logits(inputs['inputs']), targets['targets']), None
@@ -380,11 +383,30 @@ class SpeechToTextRecognizer(Recognizer):
     CTC prefix score, and the beam best of them go to the usual prune.  The score of a hypothesis that ended in EOS is then
     (1 - ctc_weight) log P_att + ctc_weight log P_ctc + lm_weight log P_lm.  ctc_beam defaults to min(V, int(1.5 * beam_width)) as in
     ESPnet.  Both decode loops; under apply_cache the joint step is part of the captured graph.  include/otrans_hip.h states the
-    semantics and the limits (beam_width <= 16, beam_width <= ctc_beam <= min(V, 32), T' <= 2048)."""
+    semantics and the limits (beam_width <= 16, beam_width <= ctc_beam <= min(V, 32), T' <= 2048).
+    rescore=True: two-pass decoding, no step loop.  The beam_width best hypotheses of the CTC prefix beam search (cutoff_top_n candidates
+    per frame, ops.ctc_prefix_beam_search) are scored by the attention decoder -- and the LM -- in ONE teacher-forced pass each and
+    re-ranked by (1 - ctc_weight) att + ctc_weight ctc + lm_weight lm, ctc being the beam's own score (include/otrans_hip.h
+    otr_rescore_*, csrc/rescore.hip).  A hypothesis longer than max_len - 1 tokens is not rescored and sorts last.  Limits:
+    nbest <= beam_width <= 32, V <= 8192; not together with joint_ctc or apply_cache."""
 
     def __init__(self, model, lm=None, lm_weight=0.1, ctc_weight=0.0, beam_width=5, nbest=1, max_len=50,
-                 idx2unit=None, penalty=0, lamda=5, ngpu=1, apply_cache=False, joint_ctc=False, ctc_beam=None):
+                 idx2unit=None, penalty=0, lamda=5, ngpu=1, apply_cache=False, joint_ctc=False, ctc_beam=None, rescore=False,
+                 cutoff_top_n=40):
         super().__init__(model, idx2unit, lm, lm_weight, ngpu)
+        self.rescore, self.cutoff_top_n = bool(rescore), int(cutoff_top_n)
+        if self.rescore:
+            if joint_ctc or apply_cache:
+                raise ValueError('rescore=True replaces the step loop: not together with %s' % ('joint_ctc=True' if joint_ctc else 'apply_cache=True'))
+            if getattr(model, 'assistor', None) is None:
+                raise ValueError('rescore=True needs the model\'s CTC head (model.assistor): build the model with ctc_weight > 0')
+            ops._rescore_check('rescore=True', beam_width, model.decoder.output_layer.weight.shape[0], nbest, ctc_weight)
+            if max_len < 1 or self.cutoff_top_n < 1:
+                raise ValueError('rescore=True: max_len=%d and cutoff_top_n=%d must be >= 1' % (max_len, self.cutoff_top_n))
+            if lm is not None and getattr(lm, 'model_type', '') not in ('transformer_lm', 'recurrent_lm'):
+                raise ValueError('rescore=True: the language model %r cannot be scored teacher-forced here (TransformerLanguageModel and '
+                                 'RecurrentLanguageModel can)' % type(lm).__name__)
+            self._rescore_out = None
         self.beam_width, self.max_len, self.nbest = beam_width, max_len, nbest
         self.penalty, self.lamda, self.ctc_weight, self.lm_weight = penalty, lamda, ctc_weight, lm_weight
         self.joint_ctc, self.ctc_beam = bool(joint_ctc), None
@@ -462,8 +484,56 @@ class SpeechToTextRecognizer(Recognizer):
         cur, steps = st.run()
         return self._nbest(st.scores[cur], st.preds[cur], steps, b)
 
+    def _rescore_outputs(self):
+        """the row-padded output layers of the decoder and the LM (_PaddedOutput; None where ops.linear serves), rebuilt when the
+        weights or the compute type change"""
+        dec, lm = self.model.decoder, self.lm
+        ws = [dec.output_layer.weight] + ([lm.output_project.weight] if lm is not None else [])
+        key = (ops.get_compute_dtype(),) + tuple((w._version, w.data_ptr()) for w in ws)
+        if self._rescore_out is None or self._rescore_out[0] != key:
+            self._rescore_out = (key, _padded_output(dec.output_layer.weight, dec.output_layer.bias),
+                                 _padded_output(lm.output_project.weight, lm.output_project.bias) if lm is not None else None)
+        return self._rescore_out[1:]
+
+    @torch.no_grad()
+    def rescore_pass(self, memory, memory_mask, log_probs, lengths):
+        """Everything of the two-pass decode behind the CTC head, on the device: the search over log_probs f32 [B, T', V], the pack, the
+        decoder (and the LM) over all B x beam_width hypotheses at once, the scoring and the sorted n-best (ops.attention_rescore's
+        dict plus 'beam' = the search's own (tokens, out_len, scores)).  No host synchronisation: capturable into one graph once the weight packs exist (after one eager call)."""
+        dec, lm, W = self.model.decoder, self.lm, self.beam_width
+        V = dec.output_layer.weight.shape[0]
+        tokens, out_len, scores = ops.ctc_prefix_beam_search(log_probs, lengths, beam_width=W, cutoff_top_n=self.cutoff_top_n,
+                                                             blank=self.model.assistor.blank)
+        packed = ops.rescore_pack(tokens, out_len, scores, self.max_len, V, BOS, EOS)
+        ys_in = packed[0]
+        out_dec, out_lm = self._rescore_outputs()
+        logits = _output(out_dec, dec.output_layer, dec.hidden(ys_in, memory, memory_mask, share=W))
+        lm_logits = None
+        if lm is not None and lm.model_type == 'recurrent_lm':
+            # as in the beam search's shallow fusion (recognize/base.py:35-36): every token scored from the ZERO state -- one LSTM step
+            # over all positions at once
+            lm_logits = lm.logits_last(ys_in.reshape(-1, 1), out=out_lm)
+        elif lm is not None:
+            lm_logits = _output(out_lm, lm.output_project, lm.hidden(ys_in))
+        res = ops.attention_rescore(logits, tokens, out_len, scores, self.max_len, V, self.ctc_weight, lm_logits=lm_logits,
+                                    lm_weight=float(self.lm_weight or 0.0) if lm is not None else 0.0, nbest=self.nbest,
+                                    penalty=self.penalty, lamda=self.lamda, packed=packed, bos=BOS, eos=EOS)
+        res['beam'] = (tokens, out_len, scores)           # the first pass, in CTC order
+        return res
+
+    @torch.no_grad()
+    def recognize_rescore(self, inputs, inputs_mask):
+        memory, memory_mask, _, _ = self.encode(inputs, inputs_mask)
+        log_probs, length = self.model.assistor.inference(memory, memory_mask)
+        res = self.rescore_pass(memory, memory_mask, log_probs.float().contiguous(), length)
+        tok = res['tokens'].cpu()
+        preds = torch.cat((tok.masked_fill(tok < 0, EOS), torch.full_like(tok[:, :, :1], EOS)), dim=-1)      # EOS behind every hypothesis
+        return self.nbest_translate(preds), res['scores'].cpu()
+
     @torch.no_grad()
     def recognize(self, inputs, inputs_mask):
+        if self.rescore:
+            return self.recognize_rescore(inputs, inputs_mask)
         if self.apply_cache:
             return self.recognize_cached(inputs, inputs_mask)
         beam = self.beam_width
@@ -891,7 +961,8 @@ def build_recognizer(model_type, model, lm, args, idx2unit):
         return SpeechToTextRecognizer(model=model, lm=lm, lm_weight=args.lm_weight, ctc_weight=args.ctc_weight,
                                       beam_width=args.beam_width, nbest=args.nbest, max_len=args.max_len,
                                       idx2unit=idx2unit, penalty=args.penalty, lamda=args.lamda, ngpu=args.ngpu,
-                                      joint_ctc=getattr(args, 'joint_ctc', False), ctc_beam=getattr(args, 'ctc_beam', None))
+                                      joint_ctc=getattr(args, 'joint_ctc', False), ctc_beam=getattr(args, 'ctc_beam', None),
+                                      rescore=getattr(args, 'rescore', False))
     if model_type == 'ctc':
         return CTCRecognizer(model=model, lm=lm, lm_weight=args.lm_weight, ngram_lm=args.ngram_lm,
                              beam_width=args.beam_width, idx2unit=idx2unit, ngpu=args.ngpu, mode=args.mode,
