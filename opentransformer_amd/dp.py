@@ -12,11 +12,227 @@ gloo/CPU tests in tests/test_dp.py exercise exactly this code with world_size 2.
 """
 import contextlib
 import ctypes as C
+import dataclasses
+import math
 
 import torch
 import torch.distributed as dist
 
 from . import _lib as L
+from . import ops
+
+# every parameter starts on a 64-element (256-byte) boundary of the flat buffers: gradient kernels then see
+# 16-byte aligned outputs whatever the sizes before them (a 4234-wide bias would misalign everything after it)
+ALIGN = 64
+_COMM_CODE = {torch.float32: L.OTR_F32, torch.bfloat16: L.OTR_BF16, torch.float16: L.OTR_F16}
+
+
+def _align(n):                      # up to the 64-element alignment of the flat buffers
+    return (n + ALIGN - 1) // ALIGN * ALIGN
+
+
+def _rows8(rows):
+    return (rows + 7) // 8 * 8
+
+
+def _tiles(r, c):                   # 64x64 tiles of an [r, c] matrix (otr_transpose_batched works tile by tile)
+    return ((r + 63) // 64) * ((c + 63) // 64)
+
+
+def _spec(off, shape, stride=None):
+    """a view of a flat buffer as plain data: (element offset, shape, stride); stride None = contiguous"""
+    return (off, tuple(shape), tuple(stride or (math.prod(shape[k + 1:]) for k in range(len(shape)))))
+
+
+def _view(buf, spec):
+    return buf.as_strided(spec[1], spec[2], buf.storage_offset() + spec[0])
+
+
+# the views a plan hands out and the buffer each lies in ('pad': the same [rows8, K] image in flat_param, flat_grad, flat_param_lp)
+_VIEWS = {'pad': None, 'pad_lpt': 'flat_param_lpt', '_otr_regroup_grad': '_store_all', '_otr_lp_view': 'flat_param_lp',
+          '_otr_lpt_view': 'flat_param_lpt', '_otr_regroup_view': 'flat_param_lpt', '_otr_ffn_packs': 'flat_pack',
+          '_otr_lin_packs': 'flat_pack'}
+
+
+@dataclasses.dataclass
+class _Plan:
+    """Where everything lives, as plain Python data (see _plan)"""
+    offsets: list                   # element offset of every parameter in the flat buffers
+    row_groups: list                # [[indices of parameters stacked along dim 0]]
+    early_end: int                  # the early group is [0, early_end)
+    numel: int                      # flat length incl. alignment gaps
+    lp: bool = False                # the 16-bit shadow exists, and with it the transposed shadow and the packs
+    stage_total: int = 0            # elements of the staging images behind the gradient buffer
+    lpt_table: list = dataclasses.field(default_factory=list)       # otr_transpose_batched rows [src_off, rows, cols, first_tile]
+    lpt_tiles: int = 0
+    pack_table: list = dataclasses.field(default_factory=list)      # otr_pack_frags rows [..., dst_off, first_block]
+    pack_blocks: int = 0
+    pack_len: int = 0               # elements of the pack buffer
+    ffn_packed: list = dataclasses.field(default_factory=list)      # indices of the FFN weights that have packs
+    # name in _VIEWS -> {parameter index: (offset from the buffer's base, shape, stride)}; a tuple of those for the packs
+    views: dict = dataclasses.field(default_factory=lambda: {name: {} for name in _VIEWS})
+
+
+def _group_key(name, shape):
+    """parameters that one GEMM reads as ONE matrix sit next to each other: the decoder layers' cross-attention key / value
+    projections (module/attention.py:128-134 `vk_proj`, all applied to the same encoder memory: ops.CrossKVAllFn) -- their
+    concatenation is then a VIEW of the flat buffers instead of three torch.cat launches per step"""
+    for suffix in ('src_attn.vk_proj.weight', 'src_attn.vk_proj.bias'):
+        if name.endswith(suffix) and math.prod(shape) % ALIGN == 0:
+            return suffix, shape
+    return None
+
+
+def _slot_numel(shape):
+    """A Linear whose row count is not a multiple of 8 (the 4234-token output layer, decoder/transformer.py:153) gets the missing
+    rows as part of its slot: the GEMMs of that layer then see [rows8, K] operands with aligned rows everywhere (weight,
+    transposed shadow, gradient; the logits / their gradient with a leading dimension of rows8) and run on the branch-free
+    kernels.  The extra rows are zero and stay zero (zero gradient, zero weight: Adam and the decay leave them alone); the
+    parameter itself is the [rows, K] head of the slot.  A bias finds its 8-padding inside the alignment gap it has anyway."""
+    if len(shape) == 2 and shape[0] % 8 != 0 and shape[1] % 8 == 0 and shape[0] > 8:
+        return _rows8(shape[0]) * shape[1]
+    return math.prod(shape)
+
+
+def _plan_flat(shapes, names, early):
+    """offsets, row_groups, early_end, numel: the early group first, stacked groups adjacent, row-padded slots, every slot aligned"""
+    offs, total, row_groups, early_end = [None] * len(shapes), 0, [], 0
+    for want_early in (True, False):            # the early group first: [0, early_end), then everything else
+        todo = [i for i in range(len(shapes)) if early[i] == want_early]
+        groups = {}
+        for i in todo:
+            groups.setdefault(_group_key(names[i], shapes[i]), []).append(i)
+        for i in todo:
+            if offs[i] is not None:
+                continue
+            k = _group_key(names[i], shapes[i])
+            members = groups[k] if k is not None else [i]
+            if len(members) > 1:
+                row_groups.append(list(members))
+            for j in members:
+                offs[j] = total
+                total += _align(_slot_numel(shapes[j]))
+        if want_early:
+            early_end = total
+    return offs, row_groups, early_end, total
+
+
+def _plan_stage(plan, shapes, regrouped):
+    """Staging images for the gradients of weights a kernel reads with two axes swapped (nn.ConvFrontEnd.regrouped_weights):
+    the weight-gradient launch accumulates there in the kernel's order, one strided add regroups it into the parameter's
+    layout (ops.LinearFn.backward).  They lie behind the gradient buffer and its fault cell, each aligned."""
+    stage = plan.views['_otr_regroup_grad']
+    for i, (A, R, S), _ in regrouped:
+        if len(shapes[i]) == 2 and math.prod(shapes[i]) == A * R * S and i not in stage:
+            stage[i] = _spec(plan.numel + ALIGN + plan.stage_total, (A, S, R))
+            plan.stage_total += _align(A * R * S)
+
+
+def _plan_packs(plan, shapes, ffn, rb_shapes):
+    """Fragment-major copies of every GLU FFN's weights for the row-block fused FFN kernels (ops.FfnLnFn) and of every Linear
+    weight the row-block kernels can take: one flat buffer, one table, ONE otr_pack_frags launch per optimizer step
+    (csrc/ffn_fused.hip)."""
+    rows = []
+    for i1, i2 in ffn:
+        F2, d = shapes[i1]
+        if d != 256 or (F2 // 2) % 256 != 0:
+            continue
+        r, o, n = ops.ffn_pack_items(plan.offsets[i1], plan.offsets[i2], F2, d, F2 // 2, plan.pack_len)
+        n1, n2 = F2 * d, d * (F2 // 2)
+        rows += r
+        plan.views['_otr_ffn_packs'][i1] = (_spec(o[0], (n1,)), _spec(o[1], (n2,)), _spec(o[2], (n2,)), _spec(o[3], (n1,)))
+        plan.ffn_packed += [i1, i2]
+        plan.pack_len += n
+    # every Linear weight the row-block kernels can take (ops.lin_packs / ops._RB_SHAPES): forward + input-gradient pack
+    # each.  By SHAPE, not by attribute name: any such weight that reached ops.LinearFn without registered packs would
+    # otherwise be served from a cache keyed by (_version, data_ptr), which FusedAdam's raw-pointer update never changes
+    for i in [i for i, shape in enumerate(shapes) if shape in rb_shapes]:
+        r, n = ops.lin_pack_items(plan.offsets[i], shapes[i][0], shapes[i][1], plan.pack_len)
+        rows += r
+        plan.views['_otr_lin_packs'][i] = (_spec(plan.pack_len, (n // 2,)), _spec(plan.pack_len + n // 2, (n // 2,)))
+        plan.pack_len += n
+    for r in rows:
+        plan.pack_table.append(list(r) + [plan.pack_blocks])
+        plan.pack_blocks += ((r[3] // 32) * (r[4] // 16) + 3) // 4
+
+
+def _plan_transposed(plan, shapes, regrouped):
+    """Transposed 16-bit shadows of the 2-D weights ([K,N]: dgrad becomes a forward-type GEMM) -- except the weights that
+    have fragment-major packs (the FFNs' w_1 / w_2, the 256- and 768-wide projections: 33 of the 36.5 M parameters
+    of the AISHELL model): their input gradients run on the packs, and refreshing 66 MB of transposes nobody reads
+    cost 35 us of every step.  A path that does not take the packs (fewer than 1024 rows) finds no transposed
+    shadow for them and uses the plain input-gradient GEMM (ops.weight_lpt returns None)."""
+    lpt, pads, done = plan.views['_otr_lpt_view'], plan.views['pad'], set(plan.ffn_packed) | set(plan.views['_otr_lin_packs'])
+
+    def transpose(off, rows, cols):
+        plan.lpt_table.append([off, rows, cols, plan.lpt_tiles])
+        plan.lpt_tiles += _tiles(rows, cols)
+    for members in plan.row_groups:     # a stacked group is transposed as ONE matrix: its members' shadows are column slices
+        if len(shapes[members[0]]) != 2:
+            continue
+        rows, cols, o0 = sum(shapes[j][0] for j in members), shapes[members[0]][1], plan.offsets[members[0]]
+        transpose(o0, rows, cols)
+        for j in members:
+            lpt[j] = _spec(o0, (cols, shapes[j][0]), (rows, 1))
+            o0 += shapes[j][0]
+        done.update(members)
+    # weights a kernel reads with two axes swapped (nn.ConvFrontEnd.regrouped_weights): [A, R, S] -> [A, S, R] is A
+    # small transposes, done in the same launch instead of a copy per forward pass
+    for i, (A, R, S), contiguous in regrouped:
+        if i in done or math.prod(shapes[i]) != A * R * S or not contiguous:
+            continue
+        plan.views['_otr_regroup_view'][i] = _spec(plan.offsets[i], (A, S, R))
+        for a in range(A):
+            transpose(plan.offsets[i] + a * R * S, R, S)
+        done.add(i)
+    for i, (shape, off) in enumerate(zip(shapes, plan.offsets)):
+        if i in done or len(shape) != 2:
+            continue
+        rows = pads[i][1][0] if i in pads else shape[0]         # the padded matrix: [K, rows8], zero tail columns
+        lpt[i] = _spec(off, (shape[1], shape[0]), (rows, 1))
+        if i in pads:
+            plan.views['pad_lpt'][i] = _spec(off, (shape[1], rows))
+        transpose(off, rows, shape[1])
+
+
+def _plan(shapes, names, early, regrouped=(), ffn=(), *, cuda=False, fp32=True, half=False, flatten=True, rb_shapes=()):
+    """The whole layout from shapes, names and flags: no tensor is touched, so this runs (and is tested) without a GPU.
+    shapes / names / early: per trainable parameter, its shape, its name in the module and whether it is in the early group;
+    regrouped: [(index, (A, R, S), is_contiguous)] of nn.ConvFrontEnd.regrouped_weights, in module order;
+    ffn: [(index of w_1, index of w_2)] of the GLU feed-forward modules;
+    cuda / fp32: device and dtype of the parameters; half: ops.is_half(); flatten: flatten_params;
+    rb_shapes: the Linear shapes that get row-block packs (ops._RB_SHAPES, empty when ops._RB is off)."""
+    shapes = [tuple(s) for s in shapes]
+    plan = _Plan(*_plan_flat(shapes, names, early), lp=flatten and cuda and fp32 and half)
+    for i, s in enumerate(shapes if flatten and cuda else []):
+        # the row-padded images of a parameter and of its gradient (ops.padded_rows): [rows8, K] / [n8], inside the slot / the gap
+        if (len(s) == 1 and s[0] % 8 != 0) or _slot_numel(s) != math.prod(s):
+            plan.views['pad'][i] = _spec(plan.offsets[i], (_rows8(s[0]),) + s[1:])
+    if cuda and fp32:
+        _plan_stage(plan, shapes, regrouped)
+    if plan.lp:
+        plan.views['_otr_lp_view'] = {i: _spec(off, s) for i, (s, off) in enumerate(zip(shapes, plan.offsets))}
+        _plan_packs(plan, shapes, ffn, rb_shapes)       # before the transposed shadows: a weight that has packs gets none
+        _plan_transposed(plan, shapes, regrouped)
+    return plan
+
+
+def _describe(module, params, early_modules=None):
+    """what _plan needs to know about a module, read off its tensors: _plan's positional arguments as a dict"""
+    index = {id(p): i for i, p in enumerate(params)}
+    name_of = {id(p): n for n, p in module.named_parameters()}
+    early_ids = {id(p) for m in (early_modules or []) for p in m.parameters()}
+    regrouped, ffn = [], []
+    for mod in module.modules():
+        regroup = getattr(mod, 'regrouped_weights', None)
+        for p, ars in (regroup() if callable(regroup) else []):
+            if id(p) in index:
+                regrouped.append((index[id(p)], tuple(ars), p.is_contiguous()))
+        w1, w2 = getattr(getattr(mod, 'w_1', None), 'weight', None), getattr(getattr(mod, 'w_2', None), 'weight', None)
+        if getattr(mod, 'activation', None) == 'glu' and id(w1) in index and id(w2) in index:
+            ffn.append((index[id(w1)], index[id(w2)]))
+    return dict(shapes=[tuple(p.shape) for p in params], names=[name_of.get(id(p), '') for p in params],
+                early=[id(p) in early_ids for p in params], regrouped=regrouped, ffn=ffn)
 
 
 class FlatDataParallel:
@@ -34,253 +250,119 @@ class FlatDataParallel:
         all-reduced on a side stream WHILE the encoder / frontend backward runs; all_reduce_gradients() then reduces only the rest
         and joins.  Two collectives instead of one; same sums (the reference's nn.DataParallel reduces per parameter,
         train/trainer.py:56-66).  None = one collective at the end."""
-        self.module = module
-        self.group = process_group
         assert comm in ('torch', 'rccl')
+        self.module, self.group = module, process_group
         self.comm, self.grad_comm_dtype = comm, grad_comm_dtype
-        self._rccl = None
-        self._payload = None
-        seen, params = set(), []
+        self._rccl = self._payload = self._side = None
+        self._early_state = None                    # None: not issued this step; else (work handle or None, payload slice or None)
+        self._accumulating = False                  # inside no_sync(): backward passes accumulate, no collective may start
+        self.skip_collectives = False               # measurement only (bench.py: exposed all-reduce time = step - step without)
+        self._single_writer = set()
+        self.flat_param = self.flat_param_lp = self.flat_param_lpt = self.flat_pack = None
+        self._lpt_table, self._lpt_tiles, self._pack_table, self._pack_blocks, self._ffn_packed = None, 0, None, 0, set()
+        seen, self.params = set(), []
         for p in module.parameters():
             if p.requires_grad and id(p) not in seen:      # tied weights appear once
                 seen.add(id(p))
-                params.append(p)
-        self.params = params
-        # every parameter starts on a 64-element (256-byte) boundary of the flat buffers: gradient kernels then see
-        # 16-byte aligned outputs whatever the sizes before them (a 4234-wide bias would misalign everything after it)
-        ALIGN = 64
-        early_ids = set()
-        for m in (early_modules or []):
-            early_ids.update(id(p) for p in m.parameters())
-        # parameters that one GEMM reads as ONE matrix sit next to each other: the decoder layers' cross-attention key / value
-        # projections (module/attention.py:128-134 `vk_proj`, all applied to the same encoder memory: ops.CrossKVAllFn) -- their
-        # concatenation is then a VIEW of the flat buffers instead of three torch.cat launches per step
-        name_of = {id(p): n for n, p in module.named_parameters()}
-        def group_key(p):
-            n = name_of.get(id(p), '')
-            for suffix in ('src_attn.vk_proj.weight', 'src_attn.vk_proj.bias'):
-                if n.endswith(suffix) and p.numel() % ALIGN == 0:
-                    return suffix
-            return None
-        # A Linear whose row count is not a multiple of 8 (the 4234-token output layer, decoder/transformer.py:153) gets the missing
-        # rows as part of its slot: the GEMMs of that layer then see [rows8, K] operands with aligned rows everywhere (weight,
-        # transposed shadow, gradient; the logits / their gradient with a leading dimension of rows8) and run on the branch-free
-        # kernels.  The extra rows are zero and stay zero (zero gradient, zero weight: Adam and the decay leave them alone); the
-        # parameter itself is the [rows, K] head of the slot.  A bias finds its 8-padding inside the alignment gap it has anyway.
-        def slot_numel(q):
-            if q.dim() == 2 and q.shape[0] % 8 != 0 and q.shape[1] % 8 == 0 and q.shape[0] > 8:
-                return (q.shape[0] + 7) // 8 * 8 * q.shape[1]
-            return q.numel()
-        offs, total = [None] * len(params), 0
-        self._row_groups = []                       # [(indices of params stacked along dim 0)]
-        for want_early in (True, False):            # the early group first: [0, early_end), then everything else
-            todo = [i for i, p in enumerate(params) if (id(p) in early_ids) == want_early]
-            groups = {}
-            for i in todo:
-                k = group_key(params[i])
-                if k is not None:
-                    groups.setdefault((k, tuple(params[i].shape)), []).append(i)
-            done = set()
-            for i in todo:
-                if i in done:
-                    continue
-                k = group_key(params[i])
-                members = groups.get((k, tuple(params[i].shape)), [i]) if k is not None else [i]
-                if len(members) > 1:
-                    self._row_groups.append(list(members))
-                for j in members:
-                    offs[j] = total
-                    total += (slot_numel(params[j]) + ALIGN - 1) // ALIGN * ALIGN
-                    done.add(j)
-            if want_early:
-                self.early_end = total
-        self.offsets = offs
-        self._early_state = None                    # None: not issued this step; else (work handle or None, payload slice or None)
-        self._side = None
-        self.skip_collectives = False               # measurement only (bench.py: exposed all-reduce time = step - step without)
-        self.numel = total                                  # flat length incl. alignment gaps
-        self.param_numel = sum(p.numel() for p in params)   # true parameter count
-        padded = total
-        dev, dt = params[0].device, params[0].dtype
-        # the gradient buffer carries one extra cell behind the parameters' range (its own 64-element block): the collective
-        # sums it like any gradient, and all_reduce_gradients() uses it to make the fault word GLOBAL (see there).  Optimizer
-        # and norm only ever see the first `padded` elements.
-        # ... and behind that, staging images for the gradients of weights a kernel reads with two axes swapped
-        # (nn.ConvFrontEnd.regrouped_weights): the weight-gradient launch accumulates there in the kernel's order, one strided add
-        # regroups it into the parameter's layout (ops.LinearFn.backward).  Part of the one allocation zero_grad() clears; NOT part of
-        # the buffer the collectives move.
-        stage_of, stage_total = {}, 0
-        if dev.type == 'cuda' and dt == torch.float32:
-            for mod in module.modules():
-                regroup = getattr(mod, 'regrouped_weights', None)
-                for p, (A, R, S) in (regroup() if callable(regroup) else []):
-                    if any(p is q for q in params) and p.dim() == 2 and p.numel() == A * R * S and id(p) not in stage_of:
-                        stage_of[id(p)] = (stage_total, (A, S, R))
-                        stage_total += (p.numel() + ALIGN - 1) // ALIGN * ALIGN
-        self._store_all = torch.zeros(padded + ALIGN + stage_total, device=dev, dtype=dt)
-        self._grad_store = self._store_all[:padded + ALIGN]
-        for p in params:
-            if id(p) in stage_of:
-                o, shp = stage_of[id(p)]
-                p._otr_regroup_grad = self._store_all[padded + ALIGN + o:padded + ALIGN + o + p.numel()].view(shp)
-                p._otr_regroup_state = {'dirty': False}      # True once a backward pass has added the image to the gradient
-        self._staged = [p for p in params if id(p) in stage_of]
-        self.flat_grad = self._grad_store[:padded]
-        self._fault_cell = self._grad_store[padded:padded + 1]
-        self.flat_param = torch.empty(padded, device=dev, dtype=dt) if flatten_params else None
+                self.params.append(p)
+        dev, dt = self.params[0].device, self.params[0].dtype
+        cuda = dev.type == 'cuda'
+        self._plan = plan = _plan(**_describe(module, self.params, early_modules), cuda=cuda, fp32=dt == torch.float32,
+                                  half=ops.is_half(), flatten=flatten_params, rb_shapes=ops._RB_SHAPES if ops._RB else ())
+        self.offsets, self._row_groups, self.early_end, self.numel = plan.offsets, plan.row_groups, plan.early_end, plan.numel
+        self.param_numel = sum(p.numel() for p in self.params)   # true parameter count
+        self._alloc_gradients(dev, dt)
+        self._install_params(dev, dt, flatten_params)
+        if cuda and flatten_params:
+            self._register_single_writers()
+        if plan.lp:
+            self._install_shadows(dev)
+            self._install_packs(dev)
+            self._install_transposed(dev)
+            self.refresh_lp()
+        if cuda:
+            ops.defer_weight_grads(True)    # weight / bias gradients run as grouped launches at the end of backward
+        if self.early_end > 0:
+            ops.set_early_callback(self._on_early_mark, modules=list(module.modules()))
+
+    def _install(self, *names):
+        """set the planned views `names` on their parameters, each a view of its buffer (_VIEWS)"""
+        for name in names:
+            buf = getattr(self, _VIEWS[name])
+            for i, spec in self._plan.views[name].items():
+                setattr(self.params[i], name, tuple(_view(buf, s) for s in spec) if name.endswith('packs') else _view(buf, spec))
+
+    def _install_pad(self, key, buf, name='pad'):
+        for i, spec in self._plan.views[name].items():
+            self.params[i]._otr_pad[key] = _view(buf, spec)
+
+    def _alloc_gradients(self, dev, dt):
+        """The gradient buffer carries one extra cell behind the parameters' range (its own 64-element block): the collective
+        sums it like any gradient, and all_reduce_gradients() uses it to make the fault word GLOBAL (see there).  Optimizer
+        and norm only ever see the first `numel` elements.  Behind that, the staging images (_plan_stage): part of the one
+        allocation zero_grad() clears; NOT part of the buffer the collectives move."""
+        n = self.numel
+        self._store_all = torch.zeros(n + ALIGN + self._plan.stage_total, device=dev, dtype=dt)
+        self._grad_store = self._store_all[:n + ALIGN]
+        self.flat_grad = self._grad_store[:n]
+        self._fault_cell = self._grad_store[n:n + 1]
+        self._install('_otr_regroup_grad')
+        self._staged = [self.params[i] for i in sorted(self._plan.views['_otr_regroup_grad'])]
+        for p in self._staged:
+            p._otr_regroup_state = {'dirty': False}      # True once a backward pass has added the image to the gradient
+
+    def _install_params(self, dev, dt, flatten_params):
+        """parameters and gradients become views of the flat buffers; so do their row-padded images"""
         if flatten_params:
+            self.flat_param = torch.empty(self.numel, device=dev, dtype=dt)
             self.flat_param.zero_()         # alignment gaps stay zero: their gradient is zero, Adam leaves them at zero
-        for p, off in zip(params, offs):
+        for p, off in zip(self.params, self.offsets):
             n = p.numel()
             if flatten_params:
                 self.flat_param[off:off + n].copy_(p.data.reshape(-1))
                 p.data = self.flat_param[off:off + n].view_as(p.data)
             p.grad = self.flat_grad[off:off + n].view_as(p.data)
             p._otr_grad_inplace = True      # ops.grad_target(): backward kernels accumulate straight into the view
-            if flatten_params and dev.type == 'cuda' and ((p.dim() == 1 and n % 8 != 0) or slot_numel(p) != n):
-                # the row-padded images of this parameter and of its gradient (ops.padded_rows): [rows8, K] / [n8]
-                shape8 = ((p.shape[0] + 7) // 8 * 8,) + tuple(p.shape[1:])
-                n8 = shape8[0] * (p.shape[1] if p.dim() == 2 else 1)
-                if p.dim() <= 2 and n8 <= (slot_numel(p) + ALIGN - 1) // ALIGN * ALIGN:
-                    p._otr_pad = {'param': self.flat_param[off:off + n8].view(shape8), 'grad': self.flat_grad[off:off + n8].view(shape8)}
-        # gradient buffers with ONE writer per backward pass (ops.register_single_writer_grads): the 2-D weights whose gradient is a
-        # deferred Linear weight-gradient product and nothing else -- not an embedding matrix (its scatter-add, and with
-        # share_embedding the output layer's product, land in one buffer) -- plus the staging images above
-        self._single_writer = set()
-        if dev.type == 'cuda' and flatten_params:
-            emb = {id(m.weight) for m in module.modules() if isinstance(m, torch.nn.Embedding)}
-            for p in params:
-                if p.dim() == 2 and id(p) not in emb:
-                    self._single_writer.add(p.grad.data_ptr())
-                if id(p) in stage_of:
-                    self._single_writer.add(p._otr_regroup_grad.data_ptr())
-            from . import ops
-            ops.register_single_writer_grads(self._single_writer)
-        # bf16 shadow of every parameter (GEMM operand form), kept fresh by FusedAdam in the same pass
-        self.flat_param_lp = None
-        if flatten_params and dev.type == 'cuda' and dt == torch.float32:
-            from . import ops
-            if ops.is_half():
-                self.flat_param_lp = torch.empty(padded, device=dev, dtype=ops.half_dtype())
-                for p, off in zip(params, offs):
-                    n = p.numel()
-                    p._otr_lp_view = self.flat_param_lp[off:off + n].view(p.shape)
-                    pad = getattr(p, '_otr_pad', None)
-                    if pad is not None:
-                        pad['lp'] = self.flat_param_lp[off:off + pad['param'].numel()].view(pad['param'].shape)
-                self._build_ffn_packs(module, dev)
-                # transposed bf16 shadows of the 2-D weights ([K,N]: dgrad becomes a forward-type GEMM) -- except the weights that
-                # have fragment-major packs (the FFNs' w_1 / w_2, the 256- and 768-wide projections: 33 of the 36.5 M parameters
-                # of the AISHELL model): their input gradients run on the packs, and refreshing 66 MB of transposes nobody reads
-                # cost 35 us of every step.  A path that does not take the packs (fewer than 1024 rows) finds no transposed
-                # shadow for them and uses the plain input-gradient GEMM (ops.weight_lpt returns None).
-                self.flat_param_lpt = torch.empty(padded, device=dev, dtype=ops.half_dtype())
-                table, tiles = [], 0
-                grouped = set()
-                for members in self._row_groups:     # a stacked group is transposed as ONE matrix: its members' shadows are column slices
-                    ps = [params[j] for j in members]
-                    if ps[0].dim() != 2:
-                        continue
-                    rows, cols, o0 = sum(q.shape[0] for q in ps), ps[0].shape[1], offs[members[0]]
-                    big = self.flat_param_lpt[o0:o0 + rows * cols].view(cols, rows)
-                    r0 = 0
-                    for q in ps:
-                        q._otr_lpt_view = big[:, r0:r0 + q.shape[0]]
-                        r0 += q.shape[0]
-                        grouped.add(id(q))
-                    table.append([o0, rows, cols, tiles])
-                    tiles += ((rows + 63) // 64) * ((cols + 63) // 64)
-                # weights a kernel reads with two axes swapped (nn.ConvFrontEnd.regrouped_weights): [A, R, S] -> [A, S, R] is A
-                # small transposes, done in the same launch instead of a copy per forward pass
-                off_of = {id(p): o for p, o in zip(params, offs)}
-                for mod in module.modules():
-                    regroup = getattr(mod, 'regrouped_weights', None)
-                    for p, (A, R, S) in (regroup() if callable(regroup) else []):
-                        if id(p) not in off_of or id(p) in grouped or p.numel() != A * R * S or not p.is_contiguous():
-                            continue
-                        o0 = off_of[id(p)]
-                        p._otr_regroup_view = self.flat_param_lpt[o0:o0 + A * R * S].view(A, S, R)
-                        for a in range(A):
-                            table.append([o0 + a * R * S, R, S, tiles])
-                            tiles += ((R + 63) // 64) * ((S + 63) // 64)
-                        grouped.add(id(p))
-                for p, off in zip(params, offs):
-                    n = p.numel()
-                    if id(p) in grouped:
-                        continue
-                    if p.dim() == 2 and getattr(p, '_otr_lin_packs', None) is None and id(p) not in self._ffn_packed:
-                        pad = getattr(p, '_otr_pad', None)
-                        rows = pad['param'].shape[0] if pad is not None else p.shape[0]       # the padded matrix: [K, rows8], zero tail columns
-                        full = self.flat_param_lpt[off:off + rows * p.shape[1]].view(p.shape[1], rows)
-                        p._otr_lpt_view = full[:, :p.shape[0]]
-                        if pad is not None:
-                            pad['lpt'] = full
-                        table.append([off, rows, p.shape[1], tiles])
-                        tiles += ((rows + 63) // 64) * ((p.shape[1] + 63) // 64)
-                # one launch transposes every such shadow (include/otrans_hip.h: otr_transpose_batched)
-                self._lpt_table = torch.tensor(table, dtype=torch.int64, device=dev).reshape(-1, 4)
-                self._lpt_tiles = tiles
-                self.refresh_lp()
-        if dev.type == 'cuda':
-            from . import ops
-            ops.defer_weight_grads(True)    # weight / bias gradients run as grouped launches at the end of backward
-        self._accumulating = False                  # inside no_sync(): backward passes accumulate, no collective may start
-        if self.early_end > 0:
-            from . import ops
-            ops.set_early_callback(self._on_early_mark, modules=list(module.modules()))
+        for i, spec in self._plan.views['pad'].items():
+            self.params[i]._otr_pad = {'param': _view(self.flat_param, spec), 'grad': _view(self.flat_grad, spec)}
 
-    def _build_ffn_packs(self, module, dev):
-        """Fragment-major copies of every GLU FFN's weights for the row-block fused FFN kernels (ops.FfnLnFn): one flat
-        buffer, one device table, ONE otr_pack_frags launch per optimizer step (csrc/ffn_fused.hip)."""
-        from . import ops
-        self.flat_pack, self._pack_table, self._pack_blocks, self._ffn_packed = None, None, 0, set()
-        off_of = {id(p): o for p, o in zip(self.params, self.offsets)}
-        rows, total, views = [], 0, []
-        for mod in module.modules():
-            w1, w2 = getattr(getattr(mod, 'w_1', None), 'weight', None), getattr(getattr(mod, 'w_2', None), 'weight', None)
-            if w1 is None or w2 is None or getattr(mod, 'activation', None) != 'glu':
-                continue
-            if id(w1) not in off_of or id(w2) not in off_of or w1.shape[1] != 256 or (w1.shape[0] // 2) % 256 != 0:
-                continue
-            F2, d = w1.shape
-            r, offs, n = ops.ffn_pack_items(off_of[id(w1)], off_of[id(w2)], F2, d, F2 // 2, total)
-            rows += r
-            views.append((w1, offs, F2 * d, d * (F2 // 2)))
-            total += n
-        # every Linear weight the row-block kernels can take (ops.lin_packs / ops._RB_SHAPES): forward + input-gradient pack
-        # each.  By SHAPE, not by attribute name: any such weight that reached ops.LinearFn without registered packs would
-        # otherwise be served from a cache keyed by (_version, data_ptr), which FusedAdam's raw-pointer update never changes
-        lin_views = []
-        for w in self.params:
-            if w.dim() != 2 or tuple(w.shape) not in ops._RB_SHAPES or not ops._RB:
-                continue
-            r, n = ops.lin_pack_items(off_of[id(w)], w.shape[0], w.shape[1], total)
-            rows += r
-            lin_views.append((w, total, w.numel()))
-            total += n
-        if not rows:
-            return
-        self.flat_pack = torch.empty(total, device=dev, dtype=self.flat_param_lp.dtype)
-        table, blocks = [], 0
-        for r in rows:
-            table.append(list(r) + [blocks])
-            blocks += ((r[3] // 32) * (r[4] // 16) + 3) // 4
-        self._pack_table = torch.tensor(table, dtype=torch.int64, device=dev)
-        self._pack_blocks = blocks
-        for mod in module.modules():
-            w1, w2 = getattr(getattr(mod, 'w_1', None), 'weight', None), getattr(getattr(mod, 'w_2', None), 'weight', None)
-            if w1 is not None and w2 is not None and any(v[0] is w1 for v in views):
-                self._ffn_packed.update((id(w1), id(w2)))
-        for w1, offs, n1, n2 in views:
-            w1._otr_ffn_packs = (self.flat_pack[offs[0]:offs[0] + n1], self.flat_pack[offs[1]:offs[1] + n2],
-                                 self.flat_pack[offs[2]:offs[2] + n2], self.flat_pack[offs[3]:offs[3] + n1])
-        for w, o, n in lin_views:
-            w._otr_lin_packs = (self.flat_pack[o:o + n], self.flat_pack[o + n:o + 2 * n])
+    def _register_single_writers(self):
+        """gradient buffers with ONE writer per backward pass (ops.register_single_writer_grads): the 2-D weights whose gradient is a
+        deferred Linear weight-gradient product and nothing else -- not an embedding matrix (its scatter-add, and with
+        share_embedding the output layer's product, land in one buffer) -- plus the staging images"""
+        emb = {id(m.weight) for m in self.module.modules() if isinstance(m, torch.nn.Embedding)}
+        self._single_writer = {p.grad.data_ptr() for p in self.params if p.dim() == 2 and id(p) not in emb}
+        self._single_writer.update(p._otr_regroup_grad.data_ptr() for p in self._staged)
+        ops.register_single_writer_grads(self._single_writer)
+
+    def _install_shadows(self, dev):
+        """bf16 shadow of every parameter (GEMM operand form), kept fresh by FusedAdam in the same pass"""
+        self.flat_param_lp = torch.empty(self.numel, device=dev, dtype=ops.half_dtype())
+        self._install('_otr_lp_view')
+        self._install_pad('lp', self.flat_param_lp)
+
+    def _install_packs(self, dev):
+        """the pack buffer, its device table and the views the kernels take (_plan_packs)"""
+        plan = self._plan
+        if plan.pack_table:
+            self.flat_pack = torch.empty(plan.pack_len, device=dev, dtype=self.flat_param_lp.dtype)
+            self._pack_table = torch.tensor(plan.pack_table, dtype=torch.int64, device=dev)
+            self._pack_blocks = plan.pack_blocks
+            self._ffn_packed = {id(self.params[i]) for i in plan.ffn_packed}
+            self._install('_otr_ffn_packs', '_otr_lin_packs')
+
+    def _install_transposed(self, dev):
+        """the transposed shadow and its table: one launch transposes every such shadow (include/otrans_hip.h:
+        otr_transpose_batched; which weights, and why not all: _plan_transposed)"""
+        self.flat_param_lpt = torch.empty(self.numel, device=dev, dtype=ops.half_dtype())
+        self._install('_otr_lpt_view', '_otr_regroup_view')
+        self._install_pad('lpt', self.flat_param_lpt, 'pad_lpt')
+        self._lpt_table = torch.tensor(self._plan.lpt_table, dtype=torch.int64, device=dev).reshape(-1, 4)
+        self._lpt_tiles = self._plan.lpt_tiles
 
     def refresh_lp(self):
         """re-cast the 16-bit shadows after any out-of-band parameter change (load_state_dict, broadcast, ...)."""
         if self.flat_param_lp is not None:
-            from . import ops
             ops.cast_bf16(self.flat_param, self.flat_param_lp)
             self.refresh_transposed()
 
@@ -291,7 +373,7 @@ class FlatDataParallel:
                 C.c_void_p(self.flat_param_lp.data_ptr()), C.c_void_p(self.flat_param_lpt.data_ptr()),
                 C.c_void_p(self._lpt_table.data_ptr()), self._lpt_table.shape[0], self._lpt_tiles, 2,
                 C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'otr_transpose_batched')
-        if self.flat_param_lp is not None and getattr(self, '_pack_blocks', 0):
+        if self.flat_param_lp is not None and self._pack_blocks:
             L.check(L.load().otr_pack_frags(
                 C.c_void_p(self.flat_param_lp.data_ptr()), C.c_void_p(self.flat_pack.data_ptr()),
                 C.c_void_p(self._pack_table.data_ptr()), self._pack_table.shape[0], self._pack_blocks,
@@ -345,7 +427,6 @@ class FlatDataParallel:
         for p in self._staged:
             p._otr_regroup_state['dirty'] = False
         if self.flat_grad.is_cuda:
-            from . import ops
             if next_dropout_step and self._store_all.dtype == torch.float32:
                 ops.zero_and_next_dropout_step(self._store_all)
             else:
@@ -387,8 +468,7 @@ class FlatDataParallel:
         return self._rccl
 
     def close(self):
-        if getattr(self, '_single_writer', None):
-            from . import ops
+        if self._single_writer:
             ops.unregister_single_writer_grads(self._single_writer)
             self._single_writer = set()
         if self._rccl is not None:
@@ -401,23 +481,21 @@ class FlatDataParallel:
         except Exception:                   # noqa: BLE001  (interpreter shutdown: the library may be gone)
             pass
 
-    def _reduce_slice(self, lo, hi, stream=None):
-        """in-place sum over ranks of _grad_store[lo:hi] (through the 16-bit payload if configured); returns a work handle or None"""
-        buf, pay = self._grad_store[lo:hi], None
+    def _reduce_slice(self, lo, hi, async_op=True):
+        """in-place sum over ranks of _grad_store[lo:hi] (through the 16-bit payload if configured: half the bytes over xGMI);
+        returns (work handle or None, payload slice or None) -- the caller widens the payload back after the wait"""
+        buf, pay, work = self._grad_store[lo:hi], None, None
         if self.grad_comm_dtype is not None:
             if self._payload is None:
                 self._payload = torch.empty_like(self._grad_store, dtype=self.grad_comm_dtype)
-            pay = self._payload[lo:hi]
-            pay.copy_(buf)
-            buf = pay
-        work = None
+            pay = buf = self._payload[lo:hi]
+            pay.copy_(self._grad_store[lo:hi])
         if self.comm == 'rccl':
-            code = {torch.float32: L.OTR_F32, torch.bfloat16: L.OTR_BF16, torch.float16: L.OTR_F16}[buf.dtype]
-            L.check(L.load().otr_allreduce_run(self._rccl_handle(), C.c_void_p(buf.data_ptr()), buf.numel(), code,
+            L.check(L.load().otr_allreduce_run(self._rccl_handle(), C.c_void_p(buf.data_ptr()), buf.numel(), _COMM_CODE[buf.dtype],
                                                C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'otr_allreduce_run')
         elif self.world_size > 1:
-            work = dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
-        return work, (pay if self.grad_comm_dtype is not None else None)
+            work = dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self.group, async_op=async_op)
+        return work, pay
 
     @contextlib.contextmanager
     def no_sync(self):
@@ -469,7 +547,6 @@ class FlatDataParallel:
 
     def backward_staged(self, loss, between=None):
         """loss.backward() cut at the marks of ops.set_stage_split(True); `between` (default: start_early_reduce) runs after stage 1"""
-        from . import ops
         ops.backward(loss)
         stages = ops.take_stages()
         (between or self.start_early_reduce)()
@@ -482,58 +559,36 @@ class FlatDataParallel:
         """single collective over the flat buffer; returns 1/world_size for the optimizer to fold in.
         force: run the collective even at world_size 1 (self-test of the RCCL path on a one-GPU box)."""
         ws = self.world_size
-        work = None
-        from . import ops as _ops
-        _ops.check_no_pending_stages('all_reduce_gradients')
+        ops.check_no_pending_stages('all_reduce_gradients')
         self._check_grad_views()
-        if self.skip_collectives:
+        if self.skip_collectives or not (ws > 1 or force):
             return 1.0 / ws, None
-        if ws > 1 or force:
-            # The sticky fault word (a bounded in-kernel wait gave up on THIS rank: its gradient sums may be wrong) is local, but
-            # the gradient it taints is about to be summed into every replica.  It rides in the cell behind the gradients
-            # through the same collective, and comes back as the sum over ranks: every rank's optimizer step then sees a
-            # non-zero word and skips together -- the replicas stay identical (a rank skipping alone would diverge for good).
-            fault = None
-            if self.flat_grad.is_cuda:
-                from . import ops
-                fault = ops.fault_counter(self.flat_grad.device)
-                self._fault_cell.copy_(fault)
-            if self._early_state is not None:
-                # the early group is already on its way (side stream): reduce the rest [early_end, end) incl. the fault cell here,
-                # then join
-                work_e, pay_e = self._early_state
-                self._early_state = None
-                work_l, pay_l = self._reduce_slice(self.early_end, self._grad_store.numel())
-                if work_l is not None:
-                    work_l.wait()
-                if pay_l is not None:
-                    self._grad_store[self.early_end:].copy_(pay_l)
-                if work_e is not None:
-                    work_e.wait()
-                if self._side is not None:
-                    torch.cuda.current_stream().wait_stream(self._side)
-                if pay_e is not None:
-                    self._grad_store[:self.early_end].copy_(pay_e)
-                if fault is not None:
-                    fault.copy_(self._fault_cell)
-                return 1.0 / ws, None
-            buf = self._grad_store
-            if self.grad_comm_dtype is not None:            # 16-bit payload: half the bytes over xGMI
-                if self._payload is None:
-                    self._payload = torch.empty_like(self._grad_store, dtype=self.grad_comm_dtype)
-                self._payload.copy_(self._grad_store)
-                buf = self._payload
-            if self.comm == 'rccl':
-                code = {torch.float32: L.OTR_F32, torch.bfloat16: L.OTR_BF16, torch.float16: L.OTR_F16}[buf.dtype]
-                L.check(L.load().otr_allreduce_run(self._rccl_handle(), C.c_void_p(buf.data_ptr()), buf.numel(), code,
-                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'otr_allreduce_run')
-            elif ws > 1:
-                work = dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self.group,
-                                       async_op=async_op and buf is self._grad_store and fault is None)
-            if buf is not self._grad_store:
-                self._grad_store.copy_(buf)
-            if fault is not None:
-                fault.copy_(self._fault_cell)               # float -> int32: the number of give-ups over all ranks
+        # The sticky fault word (a bounded in-kernel wait gave up on THIS rank: its gradient sums may be wrong) is local, but
+        # the gradient it taints is about to be summed into every replica.  It rides in the cell behind the gradients
+        # through the same collective, and comes back as the sum over ranks: every rank's optimizer step then sees a
+        # non-zero word and skips together -- the replicas stay identical (a rank skipping alone would diverge for good).
+        fault = None
+        if self.flat_grad.is_cuda:
+            fault = ops.fault_counter(self.flat_grad.device)
+            self._fault_cell.copy_(fault)
+        # when the early group is already on its way (side stream): reduce the rest [early_end, end) incl. the fault cell here,
+        # then join
+        early = self._early_state
+        lo = self.early_end if early is not None else 0
+        # the caller gets a live handle only where nothing has to follow the collective here
+        hand_out = async_op and early is None and self.grad_comm_dtype is None and fault is None
+        work, pay = self._reduce_slice(lo, self._grad_store.numel(), async_op=hand_out or early is not None)
+        if work is not None and not hand_out:
+            work.wait()
+            work = None
+        if pay is not None:
+            self._grad_store[lo:].copy_(pay)
+        if early is not None:
+            self._join_early()
+            if early[1] is not None:
+                self._grad_store[:self.early_end].copy_(early[1])
+        if fault is not None:
+            fault.copy_(self._fault_cell)               # float -> int32: the number of give-ups over all ranks
         return 1.0 / ws, work
 
 
@@ -559,7 +614,6 @@ class FusedAdam:
         self.grad_noise = float(grad_noise)
         self.step_offset = 2.0          # Noam step of update t+1 = t + 1 + step_offset (scheduler.py:16-53); load_state_dict may move it
         if dp.flat_param.is_cuda:
-            from . import ops
             ops.fault_counter(dp.flat_param.device)     # the update skips when a spin-bounded kernel of the step gave up
             if loss_scale is None:
                 loss_scale = 4096.0 if ops.get_compute_dtype() == 'fp16' else 0.0
@@ -575,8 +629,7 @@ class FusedAdam:
             raise L.OtransHipError('FusedAdam runs on the GPU only')
         n = self.dp.flat_param.numel()
         nm = self.noam or {}
-        from . import ops as _ops
-        _ops.check_no_pending_stages('FusedAdam.step')
+        ops.check_no_pending_stages('FusedAdam.step')
         self._last_grad_scale = float(grad_scale)
         ret = L.load().otr_optimizer_step(
             C.c_void_p(self.dp.flat_param.data_ptr()), C.c_void_p(self.dp.flat_grad.data_ptr()),

@@ -13,6 +13,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from opentransformer_amd.dp import FlatDataParallel
+from tests import helpers as H
 
 
 class Tiny(torch.nn.Module):
@@ -428,7 +429,7 @@ def test_mask_cast_is_remembered_on_the_tensor():
 
 
 def test_row_padded_slots_in_the_flat_layout():
-    """dp.py `slot_numel`: a 2-D parameter whose row count is not a multiple of 8 (the 4234-token output layer,
+    """dp.py `_slot_numel`: a 2-D parameter whose row count is not a multiple of 8 (the 4234-token output layer,
     decoder/transformer.py:153) owns the rows up to the next multiple of 8 inside its slot of the flat buffers; the parameter and
     its gradient stay the [rows, K] head of the slot, everything behind starts 64-element aligned, the extra rows are zero and take
     no gradient (host layout only here: the padded operand images themselves are device-side, tests/test_gpu_dp.py)."""
@@ -461,3 +462,38 @@ def test_row_padded_slots_in_the_flat_layout():
     m(torch.randn(5, 16)).backward()
     assert m.a.weight.grad.abs().sum() > 0 and not dp.flat_grad[o + 11 * 16:o + 16 * 16].any()
     assert dp.packed_grads().numel() == sum(p.numel() for p in m.parameters())
+
+
+@pytest.mark.parametrize('case', sorted(H.dp_layout_golden()['host']))
+def test_flat_layout_is_the_recorded_one(case):
+    """The host layout of the shipped configurations (offsets, stacked groups, early group, lengths) is what the commit before
+    the layout plan (dp._plan) computed: tests/golden/dp_layout.json, 'host'."""
+    from opentransformer_amd import ops
+    want = H.dp_layout_golden()['host'][case]
+    model, early = H.dp_layout_model(case)
+    try:
+        dp = FlatDataParallel(model, early_modules=early)
+    finally:
+        ops.set_early_callback(None)
+    assert (len(dp.params), dp.numel, dp.param_numel, dp.early_end) == (want['n_params'], want['numel'], want['param_numel'], want['early_end'])
+    assert dp._row_groups == want['row_groups'] and len(dp._row_groups) == 2
+    assert H.dp_layout_sha256(dp.offsets) == want['offsets_sha256']
+    assert dp.offsets == want.get('offsets', dp.offsets)
+    assert dp.flat_param_lp is None and dp._lpt_table is None and dp._pack_blocks == 0      # nothing device-side on the CPU
+
+
+@pytest.mark.parametrize('case', sorted(H.dp_layout_golden()['device']))
+def test_planned_device_layout_is_the_recorded_one(case):
+    """dp._plan is pure: asked on the CPU for the layout of a GPU replica in a 16-bit mode, it gives the transposed-shadow table,
+    the pack table, the staging images and every per-parameter view (offset, shape, stride) that the commit before it installed
+    on an MI355X (tests/golden/dp_layout.json, 'device'; fp16 and bf16 mode share one layout)."""
+    from opentransformer_amd import dp as dpm, ops
+    model, early = H.dp_layout_model(case)
+    params = [p for p in model.parameters() if p.requires_grad]
+    assert len({id(p) for p in params}) == len(params)
+    described = dpm._describe(model, params, early)
+    plan = dpm._plan(**described, cuda=True, fp32=True, half=True, rb_shapes=ops._RB_SHAPES)
+    H.check_dp_layout(H.dp_planned_layout(plan, described['shapes']), H.dp_layout_golden()['device'][case])
+    host = dpm._plan(**described)           # the same call for a CPU replica: the flat layout alone
+    assert (host.offsets, host.row_groups, host.early_end, host.numel) == (plan.offsets, plan.row_groups, plan.early_end, plan.numel)
+    assert not host.lp and not host.lpt_table and not host.pack_table and not host.stage_total and not any(host.views.values())

@@ -456,3 +456,34 @@ def test_output_layer_on_row_padded_operands(V):
         assert rel(xa, xb) < 2e-3 and rel(wa, wb) < 2e-3 and rel(ba, bb) < 1e-4, (rel(xa, xb), rel(wa, wb), rel(ba, bb))
     finally:
         ops.set_compute_dtype('bf16')
+
+
+@pytest.mark.parametrize('case', ['c2/fp16/early', 'c2/bf16/single', 'conformer/fp16/early', 'conformer/bf16/single'])
+def test_installed_layout_is_the_planned_one(case):
+    """What FlatDataParallel installs on the GPU is what its pure plan (dp._plan) says: every _otr_* view by offset from its
+    buffer's base, shape and stride, the two device tables element for element -- and both are the layout recorded from the
+    commit before the plan (tests/golden/dp_layout.json)."""
+    from opentransformer_amd import ops
+    from opentransformer_amd.dp import FlatDataParallel
+    ops.set_compute_dtype(case.split('/')[1])
+    try:
+        model, early = H.dp_layout_model(case)
+        dp = FlatDataParallel(model.to('cuda').train(), early_modules=early)
+        try:
+            plan = dp._plan
+            got, planned = H.dp_installed_layout(dp), H.dp_planned_layout(plan, [tuple(p.shape) for p in dp.params])
+            for k in planned:
+                assert got[k] == planned[k], k
+            assert torch.equal(dp._lpt_table.cpu(), torch.tensor(plan.lpt_table, dtype=torch.int64).reshape(-1, 4))
+            assert dp._lpt_tiles == plan.lpt_tiles and dp._pack_blocks == plan.pack_blocks
+            if plan.pack_table:
+                assert torch.equal(dp._pack_table.cpu(), torch.tensor(plan.pack_table, dtype=torch.int64))
+                assert dp.flat_pack.numel() == plan.pack_len
+            else:
+                assert dp._pack_table is None and dp.flat_pack is None
+            H.check_dp_layout(got, H.dp_layout_golden()['device'][case])
+        finally:
+            dp.close()
+            ops.set_early_callback(None)
+    finally:
+        ops.set_compute_dtype('bf16')
