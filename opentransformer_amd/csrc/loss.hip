@@ -270,14 +270,15 @@ __global__ __launch_bounds__(256) void log_softmax_kernel(const float* x, float*
   float se = 0.f;
   for (int v = threadIdx.x; v < V; v += blockDim.x) se += expf(xr[v] - mx);
   se = block_reduce(se, sh, false);
-  const float lse = mx + logf(se);
-  for (int v = threadIdx.x; v < V; v += blockDim.x) yr[v] = xr[v] - lse;
+  // (x - max) - log(sum), not x - (max + log(sum)): the latter rounds the result to an ulp of |max| (1e-3 for logits near 1e4)
+  const float lg = logf(se);
+  for (int v = threadIdx.x; v < V; v += blockDim.x) yr[v] = (xr[v] - mx) - lg;
 }
 
 extern "C" int32_t otr_log_softmax(const float* x, float* y, int64_t R, int32_t V, void* stream) {
-  OTR_REQUIRE(x && y, "log_softmax: null pointer");
   OTR_REQUIRE(R >= 0 && V > 0, "log_softmax: bad shape");
-  if (R == 0) return 0;
+  if (R == 0) return 0;                              // an empty tensor's data pointer is null: nothing to read or write
+  OTR_REQUIRE(x && y, "log_softmax: null pointer");
   hipLaunchKernelGGL(log_softmax_kernel, dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, x, y, V);
   return otr_check_launch("log_softmax");
 }
