@@ -37,9 +37,9 @@ extern "C" {
 
 /* ABI version of THIS header: bumped whenever a signature, a descriptor struct or the meaning of an argument changes (600: round 6;
  * 300 was rounds 3-5, during which otr_optimizer_step, otr_ln_desc_t, otr_wgrad_item_t and otr_beam_prune_cached changed without a
- * bump; 602: the rescoring entries, additions only).  A binding compares otr_version() with the OTR_ABI_VERSION it was written against BEFORE its first call and refuses a
+ * bump; 602: the rescoring entries, additions only; 603: otr_ctc_align, additions only).  A binding compares otr_version() with the OTR_ABI_VERSION it was written against BEFORE its first call and refuses a
  * library that answers anything else: descriptors are passed by pointer and read at the library's idea of their size. */
-#define OTR_ABI_VERSION 602
+#define OTR_ABI_VERSION 603
 int32_t otr_version(void);
 /* OTR_BF16 or OTR_F16: the 16-bit type this library was built for */
 int32_t otr_half_type(void);
@@ -692,6 +692,33 @@ int32_t otr_ctc_topk(const float* log_probs, int64_t ld, const int32_t* lengths,
 int32_t otr_ctc_beam_search(const float* top_lp, const int32_t* top_tok, const int32_t* lengths, int32_t B, int32_t T, int32_t V,
                             int32_t K, int32_t blank, int32_t W, void* workspace, int64_t ws_bytes, int64_t* tokens,
                             int32_t* out_len, float* scores, void* stream);
+
+/* ---- CTC forced alignment (token time stamps from the CTC head: what ctcdecode's `timesteps`, dropped at recognize/ctc.py:64, gives
+ *      for the decoded string), csrc/ctcalign.hip.  The most probable CTC path of a KNOWN label sequence.  f32 in both builds.
+ * log_probs f32 [B, T, V]: frame (b, t) at log_probs + (b*T + t)*ld; in_len int32 [B] on the device, clamped to [0, T] (= T_b); frames
+ * t >= T_b are not read.  targets int64 [B, ldt], tgt_len int32 [B]: L = tgt_len[b], 0 <= L <= max_tgt <= 127 (the limit of
+ * otr_ctc_loss).  An utterance whose tgt_len is negative or above max_tgt, or one of whose L labels lies outside [0, V), is infeasible:
+ * nothing of it is computed.
+ * Extended states s = 0 .. 2L as in the loss: even s is blank, odd s is label s>>1 (= ext(s)).  With x_t(c) the log-prob of token c:
+ *   v_0(0) = x_0(blank), v_0(1) = x_0(label 0), v_0(s) = -inf otherwise;
+ *   v_t(s) = max(v_{t-1}(s), v_{t-1}(s-1), v_{t-1}(s-2) if allowed) + x_t(ext(s)),  one f32 add after an exact max;
+ *   the step from s-2 is allowed exactly as in the loss: ext(s) is a label and differs from ext(s-2).
+ * Ties: among equal predecessors the smallest step wins (stay, then s-1, then s-2); at the end v_{T_b-1}(2L) wins a tie against
+ * v_{T_b-1}(2L-1).  The path is the one these choices trace back from the end.
+ * Outputs: score f32 [B] = the path's log-probability; frame_token int32 [B, T] = the token of the path's state at each frame (blank on
+ * blank frames, -1 for t >= T_b); spans int32 [B, max_tgt, 2] = first frame and one-past-last frame at which label j's state is
+ * occupied (-1, -1 for j >= L); label_logp f32 [B, max_tgt] = sum of x_t(label j) over that span, added in ascending t (0 for j >= L).
+ * Infeasible (score -inf: T_b = 0 with L > 0, fewer frames than labels plus adjacent repeats, log-probs of -inf on every path, a bad
+ * length or label): score = -inf, frame_token and spans all -1, label_logp all 0.  T_b = 0 with L = 0: score 0, the empty path.
+ * One launch, one workgroup per utterance.  The 2-bit back-pointers (64 B per frame) stay in LDS while T <= 960 and go to `workspace`
+ * above that: otr_ctc_align_workspace_bytes(B, T, max_tgt) bytes (8 where T <= 960, B*T*64 above), 8-byte aligned, never NULL.
+ * Every argument is checked before the launch (null pointers, V <= 1, blank outside [0, V), ld < V, ldt < max_tgt, max_tgt > 127, the
+ * workspace's size and alignment): a refused call leaves the outputs untouched.
+ * otr_ctc_align_workspace_bytes: pure host function, -1 for a bad shape (B < 1, T < 1, max_tgt outside [0, 127]). */
+int64_t otr_ctc_align_workspace_bytes(int32_t B, int32_t T, int32_t max_tgt);
+int32_t otr_ctc_align(const float* log_probs, int64_t ld, const int64_t* targets, int64_t ldt, const int32_t* in_len,
+                      const int32_t* tgt_len, int32_t B, int32_t T, int32_t V, int32_t max_tgt, int32_t blank, void* workspace,
+                      int64_t ws_bytes, int32_t* frame_token, int32_t* spans, float* label_logp, float* score, void* stream);
 
 /* ---- joint CTC/attention beam search (SpeechToTextRecognizer joint_ctc=True; Watanabe et al. 2017, Algorithm 2; ESPnet's
  *      CTCPrefixScore), csrc/ctcscore.hip.  f32 in every build.  lambda = ctc_weight in [0, 1]; x_t(c) = log_probs of token c at frame

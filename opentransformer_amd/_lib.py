@@ -14,7 +14,7 @@ LIB_PATHS = {'bf16': os.path.join(_LIB_DIR, 'libotrans_hip.so'), 'fp16': os.path
 LIB_PATH = LIB_PATHS['bf16']
 
 OTR_F32, OTR_BF16, OTR_F16 = 0, 1, 2
-OTR_ABI_VERSION = 602           # include/otrans_hip.h: the header this binding's structures and SIGNATURES were written against
+OTR_ABI_VERSION = 603           # include/otrans_hip.h: the header this binding's structures and SIGNATURES were written against
 OTR_OPT_STATE_FLOATS = 528      # include/otrans_hip.h: floats of otr_optimizer_step's device state block
 ACT_NONE, ACT_RELU = 0, 1
 
@@ -204,6 +204,8 @@ SIGNATURES = {
     'otr_ctc_beam_workspace_bytes': [_I32, _I32, _I32],
     'otr_ctc_topk': [_P, _I64, _P, _I32, _I32, _I32, _I32, _P, _P, _P],
     'otr_ctc_beam_search': [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P, _P, _P, _P],
+    'otr_ctc_align_workspace_bytes': [_I32, _I32, _I32],
+    'otr_ctc_align': [_P, _I64, _P, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P],
     'otr_joint_prebeam': [_P, _I64, _P, _I64, _F32, _F32, _I64, _I32, _I32, _P, _P, _P],
     'otr_ctc_prefix_score': [_P, _I64, _P, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _P, _P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P,
                              _F32, _P, _P, _P, _I32, _P, _P, _P, _P],
@@ -249,7 +251,7 @@ _RESTYPE = {'otr_last_error_string': C.c_char_p, 'otr_dec_ffn_hsave_bytes': C.c_
             'otr_ffn_split_padded_rows': C.c_int64, 'otr_add_layernorm_bwd_partial_rows': C.c_int64,
             'otr_ln_bwd_proj_partial_rows': C.c_int64, 'otr_dwconv_bwd_partial_rows': C.c_int64, 'otr_dwconv_fwd_partial_rows': C.c_int64,
             'otr_conv2_wide_scratch_bytes': C.c_int64, 'otr_add2_colsum_partial_rows': C.c_int64,
-            'otr_ctc_beam_workspace_bytes': C.c_int64}
+            'otr_ctc_beam_workspace_bytes': C.c_int64, 'otr_ctc_align_workspace_bytes': C.c_int64}
 
 _libs = {}
 _kind = 'bf16'

@@ -4,7 +4,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .nn import (BLK, ConformerEncoder, ConvFrontEnd, LabelSmoothingLoss, TransformerDecoder, TransformerEncoder,
+from .nn import (BLK, EOS, ConformerEncoder, ConvFrontEnd, LabelSmoothingLoss, TransformerDecoder, TransformerEncoder,
                  _unsupported)
 
 BuildFrontEnd = {'conv': ConvFrontEnd}                 # otrans/frontend/__init__.py:8-12
@@ -44,6 +44,13 @@ class CTCAssistor(nn.Module):
         logits = self.compute_logits(self._look_ahead(memory))
         memory_length = torch.sum(memory_mask.squeeze(1) if memory_mask.dim() == 3 else memory_mask, dim=-1)
         return ops.log_softmax(logits), memory_length
+
+    @torch.no_grad()
+    def align(self, memory, memory_mask, labels, labels_length):
+        """CTC forced alignment of `labels` [B, max_tgt] (plain units, `labels_length` [B] of them) on this head's log-probs:
+        (frame_token, spans, label_logp, score) of ops.ctc_forced_align, in encoder frames"""
+        log_probs, memory_length = self.inference(memory, memory_mask)
+        return ops.ctc_forced_align(log_probs, memory_length, labels, labels_length, blank=self.blank)
 
 
 class SpeechToText(nn.Module):
@@ -94,6 +101,25 @@ class SpeechToText(nn.Module):
         memory_length = torch.sum(memory_mask, dim=-1)
         return self.assistor(memory, memory_length, targets_out, targets_length)
 
+    @torch.no_grad()
+    def align(self, inputs, inputs_mask, labels, labels_length):
+        """CTC forced alignment with the model's CTC head.  `labels` [B, max_tgt] are plain units without BOS / EOS, `labels_length` [B]
+        their counts.  The CTC term of forward() is trained on the labels followed by EOS (target_out = truth[:, 1:]), so that is the
+        sequence aligned: frame_token [B, T'] (the EOS frames included) and score [B] are those of the whole path, spans
+        [B, max_tgt, 2] and label_logp [B, max_tgt] are the labels' alone, the EOS column dropped."""
+        if getattr(self, 'assistor', None) is None:
+            raise ValueError('align needs the model\'s CTC head (model.assistor): build the model with ctc_weight > 0')
+        n = labels_length.to(torch.int64)
+        ext = torch.cat((labels.to(torch.int64), labels.new_zeros((labels.size(0), 1), dtype=torch.int64)), dim=1)
+        ext.scatter_(1, n.clamp(0, labels.size(1)).unsqueeze(1), EOS)          # a length outside [0, max_tgt] stays infeasible below
+        enc_inputs, enc_mask = self.frontend(inputs, inputs_mask)
+        memory, memory_mask, _ = self.encoder(enc_inputs, enc_mask)
+        frame_token, spans, label_logp, score = self.assistor.align(memory, memory_mask, ext, torch.where(n < 0, n, n + 1))
+        keep = torch.arange(labels.size(1), device=labels.device).unsqueeze(0) < n.unsqueeze(1)       # the EOS is label n of its row
+        spans = torch.where(keep.unsqueeze(-1), spans[:, :-1], torch.full_like(spans[:, :-1], -1))
+        label_logp = torch.where(keep, label_logp[:, :-1], torch.zeros_like(label_logp[:, :-1]))
+        return frame_token, spans, label_logp, score
+
     def save_checkpoint(self, params, name):
         checkpoint = {'params': params, 'frontend': self.frontend.state_dict(), 'encoder': self.encoder.state_dict(),
                       'decoder': self.decoder.state_dict()}
@@ -140,6 +166,15 @@ class CTCModel(nn.Module):
         return self.assistor.inference(memory, memory_mask)
 
     recognize = inference
+
+    @torch.no_grad()
+    def align(self, inputs, inputs_mask, labels, labels_length):
+        """CTC forced alignment of `labels` [B, max_tgt] (plain units without BOS / EOS, `labels_length` [B] of them): the head is
+        trained on the labels as they are (forward()), so they are aligned as they are.  Returns ops.ctc_forced_align's
+        (frame_token, spans, label_logp, score) in encoder frames."""
+        enc_inputs, enc_mask = self.frontend(inputs, inputs_mask)
+        memory, memory_mask, _ = self.encoder(enc_inputs, enc_mask)
+        return self.assistor.align(memory, memory_mask, labels, labels_length)
 
     def save_checkpoint(self, params, name):
         torch.save({'params': params, 'frontend': self.frontend.state_dict(), 'encoder': self.encoder.state_dict(),

@@ -3678,6 +3678,52 @@ def ctc_prefix_beam_search(log_probs, lengths, beam_width=5, cutoff_top_n=40, bl
     return tokens, out_len, scores
 
 
+CTC_ALIGN_MAX_TGT = 127
+
+
+def ctc_forced_align(log_probs, in_len, targets, tgt_len, blank=0):
+    """CTC forced alignment on the device (include/otrans_hip.h otr_ctc_align): the most probable CTC path of each utterance's known
+    label sequence.  log_probs f32 [B, T, V] (log-softmax output), in_len [B] frames, targets int64 [B, max_tgt] labels, tgt_len [B]
+    their counts.  Returns (frame_token int32 [B, T]: the path's token per frame, blank on blank frames, -1 past in_len; spans int32
+    [B, max_tgt, 2]: first and one-past-last frame of each label, -1 past tgt_len; label_logp f32 [B, max_tgt]: the label's log-probs
+    summed over its span; score f32 [B]: the path's log-probability).  An utterance that cannot be aligned (fewer frames than labels
+    plus adjacent repeats, a length beyond max_tgt) has score -inf, frame_token and spans -1, label_logp 0.  No autograd; one launch
+    on the current stream, no host synchronisation."""
+    if targets.dim() != 2 or targets.shape[1] > CTC_ALIGN_MAX_TGT:
+        raise ValueError('ctc_forced_align: targets must be [B, max_tgt] with max_tgt <= %d label columns, got %s'
+                         % (CTC_ALIGN_MAX_TGT, tuple(targets.shape)))
+    _cuda(log_probs, in_len, targets, tgt_len)
+    if log_probs.dim() != 3 or log_probs.dtype != torch.float32:
+        raise L.OtransHipError('ctc_forced_align: log_probs must be f32 [B, T, V], got %s %s' % (log_probs.dtype, tuple(log_probs.shape)))
+    B, T, V = log_probs.shape
+    max_tgt = targets.shape[1]
+    lib = L.load()
+    dev = log_probs.device
+    lp = log_probs if log_probs.stride(2) == 1 and log_probs.stride(0) == T * log_probs.stride(1) else log_probs.contiguous()
+    tg = targets.to(torch.int64)
+    if max_tgt == 0:                                  # no label column: the library still wants a row to point at
+        tg = torch.zeros((B, 1), dtype=torch.int64, device=dev)
+    elif tg.stride(1) != 1:
+        tg = tg.contiguous()
+    il = in_len.to(torch.int32).contiguous()
+    tl = tgt_len.to(torch.int32).contiguous()
+    need = lib.otr_ctc_align_workspace_bytes(B, T, max_tgt)
+    if need < 0 or targets.shape[0] != B or il.numel() != B or tl.numel() != B or not 0 <= blank < V:
+        raise L.OtransHipError('ctc_forced_align: bad arguments B=%d T=%d V=%d targets %s blank=%d'
+                               % (B, T, V, tuple(targets.shape), blank))
+    ws = torch.empty(need // 8, dtype=torch.int64, device=dev)
+    frame_token = torch.empty((B, T), dtype=torch.int32, device=dev)
+    spans = torch.empty((B, max_tgt, 2), dtype=torch.int32, device=dev)
+    label_logp = torch.empty((B, max_tgt), dtype=torch.float32, device=dev)
+    score = torch.empty((B,), dtype=torch.float32, device=dev)
+    dummy = torch.empty(2, dtype=torch.int32, device=dev) if max_tgt == 0 else None      # empty outputs have no address
+    L.check(_timed('ctc_align %dx%dx%d' % (B, T, max_tgt), {'bytes': B * T * (2 * max_tgt + 1) * 4},
+                   lambda: lib.otr_ctc_align(_p(lp), lp.stride(1), _p(tg), tg.stride(0), _p(il), _p(tl), B, T, V, max_tgt, blank,
+                                             _p(ws), need, _p(frame_token), _p(spans if dummy is None else dummy),
+                                             _p(label_logp if dummy is None else dummy), _p(score), _stream())), 'otr_ctc_align')
+    return frame_token, spans, label_logp, score
+
+
 # ------------------------------------------------------------------ joint CTC/attention beam search (csrc/ctcscore.hip)
 JOINT_MAX_K, JOINT_MAX_T, JOINT_MAX_V, JOINT_MAX_BEAM = 32, 2048, 8192, 16
 

@@ -954,6 +954,79 @@ class CTCRecognizer(Recognizer):
             return self.translate(self.recognize_beam(inputs, inputs_mask))
         return self.translate(self.recognize_greedy(inputs, inputs_mask))
 
+    def _span_lists(self, labels, labels_length, spans, label_logp, score):
+        """per utterance [(unit, start_frame, end_frame, logp), ...]; like translate() a list ends before its first EOS and skips PAD;
+        an utterance that could not be aligned (score -inf) gives an empty list"""
+        labels, n, spans, label_logp, score = labels.cpu(), labels_length.cpu(), spans.cpu(), label_logp.cpu(), score.cpu()
+        out = []
+        for b in range(labels.size(0)):
+            items = []
+            for j in range(int(n[b]) if score[b] > -float('inf') else 0):
+                k = int(labels[b, j])
+                if k == EOS:
+                    break
+                if k == PAD:
+                    continue
+                items.append((self.idx2unit[k], int(spans[b, j, 0]), int(spans[b, j, 1]), float(label_logp[b, j])))
+            out.append(items)
+        return out
+
+    @torch.no_grad()
+    def align(self, inputs, inputs_mask, labels, labels_length):
+        """CTC forced alignment of known transcripts: `labels` [B, max_tgt] unit ids without BOS / EOS, `labels_length` [B] their counts
+        (at most 127).  Per utterance a list of (unit, start_frame, end_frame, logp): the encoder frames [start, end) the most probable
+        CTC path gives the unit, and the unit's log-probs summed over them; frames_to_seconds() turns a frame into a time."""
+        x, mask, _ = self.model.frontend.inference(inputs, inputs_mask, None)
+        memory, memory_mask, _ = self.model.encoder(x, mask)
+        _, spans, label_logp, score = self.model.assistor.align(memory, memory_mask, labels, labels_length)
+        return self._span_lists(labels, labels_length, spans, label_logp, score)
+
+    @torch.no_grad()
+    def recognize_with_times(self, inputs, inputs_mask):
+        """recognize() with time stamps (what ctcdecode's `timesteps` give the reference's users): one encoder pass, greedy or beam
+        decoding as `mode` says, then the 1-best aligned on the log-probs it was decoded from.  Returns (texts, per-utterance lists of
+        (unit, start_frame, end_frame, logp)); the units of a list, read in order, are the words of its text."""
+        x, mask, _ = self.model.frontend.inference(inputs, inputs_mask, None)
+        memory, memory_mask, _ = self.model.encoder(x, mask)
+        blank = self.model.assistor.blank
+        if self.mode == 'beam':
+            log_probs, length = self.model.assistor.inference(memory, memory_mask)
+            tokens, out_len, _ = ops.ctc_prefix_beam_search(log_probs, length, beam_width=self.beam_width, cutoff_top_n=self.cutoff_top_n,
+                                                            blank=blank)
+            best, n = tokens[:, 0].cpu(), out_len[:, 0].cpu()
+            preds = [best[b, :int(n[b])].tolist() for b in range(best.size(0))]
+        else:                                                                   # recognize_greedy's logits: no look-ahead
+            logits = self.model.assistor.compute_logits(memory)
+            B, T, V = logits.shape
+            best_s = torch.empty((B * T, 1), dtype=torch.float32, device=logits.device)
+            best_i = torch.empty((B * T, 1), dtype=torch.long, device=logits.device)
+            L.check(L.load().otr_beam_topk(_ptr(logits), V, None, 0, 0.0, B * T, V, 1, _ptr(best_s), _ptr(best_i),
+                                           C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'otr_beam_topk')
+            log_probs, length = ops.log_softmax(logits), memory_mask.sum(-1)
+            best, n = best_i.view(B, T).cpu(), length.cpu()
+            preds = []
+            for b in range(best.size(0)):
+                pred, last_k = [], PAD
+                for k in best[b, :int(n[b])].tolist():
+                    if k != last_k and k != PAD:
+                        pred.append(k)
+                    last_k = k
+                preds.append(pred)
+        width = max(1, max(len(p) for p in preds))
+        if width > ops.CTC_ALIGN_MAX_TGT:
+            raise ValueError('recognize_with_times: a 1-best of %d units, the alignment takes at most %d' % (width, ops.CTC_ALIGN_MAX_TGT))
+        labels = torch.tensor([p + [PAD] * (width - len(p)) for p in preds], dtype=torch.int64, device=log_probs.device)
+        labels_length = torch.tensor([len(p) for p in preds], dtype=torch.int32, device=log_probs.device)
+        _, spans, label_logp, score = ops.ctc_forced_align(log_probs, length, labels, labels_length, blank=blank)
+        return self.translate(preds), self._span_lists(labels, labels_length, spans, label_logp, score)
+
+
+def frames_to_seconds(frame, subsample=4, frame_shift_ms=10.0):
+    """Start time, in seconds, of the input window of encoder frame `frame` (a span's end_frame gives the start of the first frame
+    after the unit).  The ConvFrontEnd built here is two stride-2 convolutions, so an encoder frame advances subsample = 4 feature
+    frames of frame_shift_ms each; a frontend with another stride passes its own product."""
+    return frame * subsample * frame_shift_ms / 1000.0
+
 
 def build_recognizer(model_type, model, lm, args, idx2unit):
     """recognize/__init__.py:5-16."""
