@@ -37,9 +37,9 @@ extern "C" {
 
 /* ABI version of THIS header: bumped whenever a signature, a descriptor struct or the meaning of an argument changes (600: round 6;
  * 300 was rounds 3-5, during which otr_optimizer_step, otr_ln_desc_t, otr_wgrad_item_t and otr_beam_prune_cached changed without a
- * bump; 602: the rescoring entries, additions only; 603: otr_ctc_align, additions only).  A binding compares otr_version() with the OTR_ABI_VERSION it was written against BEFORE its first call and refuses a
+ * bump; 602: the rescoring entries, additions only; 603: otr_ctc_align, additions only; 604: otr_ngram_lookup and otr_ctc_beam_search_lm, additions only).  A binding compares otr_version() with the OTR_ABI_VERSION it was written against BEFORE its first call and refuses a
  * library that answers anything else: descriptors are passed by pointer and read at the library's idea of their size. */
-#define OTR_ABI_VERSION 603
+#define OTR_ABI_VERSION 604
 int32_t otr_version(void);
 /* OTR_BF16 or OTR_F16: the 16-bit type this library was built for */
 int32_t otr_half_type(void);
@@ -692,6 +692,39 @@ int32_t otr_ctc_topk(const float* log_probs, int64_t ld, const int32_t* lengths,
 int32_t otr_ctc_beam_search(const float* top_lp, const int32_t* top_tok, const int32_t* lengths, int32_t B, int32_t T, int32_t V,
                             int32_t K, int32_t blank, int32_t W, void* workspace, int64_t ws_bytes, int64_t* tokens,
                             int32_t* out_len, float* scores, void* stream);
+
+/* ---- n-gram LM fusion for the CTC prefix beam search (the ngram_lm / alpha / beta that recognize/ctc.py:22-25 hands to
+ *      ctcdecode.CTCBeamDecoder; character based, ctcdecode's is_character_based case), csrc/ngram.hip + csrc/ctcbeam.hip.  f32.
+ * The model: a backoff n-gram of order N <= 5 over the acoustic model's units.  Ids [0, V) are the units, id V is <s>; V <= 8192, so
+ * an id fits 16 bits.  Log-probs and backoff weights are natural logs in f32 (ARPA's log10 values converted once at load).
+ * The table: `capacity` entries of 32 bytes, capacity a power of two, the base 32-byte aligned; open addressing with linear probing
+ * from hash(key) & (capacity - 1), load <= 0.5, nothing ever deleted.  Entry = { u64 lo, u64 hi, f32 log-prob, f32 backoff, 8 bytes
+ * of padding }.  The key of the n-gram w_0 .. w_{m-1} is exact, not a fingerprint: id w_{m-1-j} sits at bits [16j, 16j+16) of an
+ * 80-bit value, lo = its bits 0-63, hi = its bits 64-79 | m << 16; hi == 0 marks an empty entry.  hash = the splitmix64 finaliser of
+ * lo ^ (hi * 0x9e3779b97f4a7c15) (csrc/ngram.h ng_hash).  A lookup walks from the home entry until it meets the key, an empty entry,
+ * or has read max_probe entries: max_probe is the longest chain of the build (opentransformer_amd/ngram.py records it).
+ * Context: the context of a prefix s is <s> followed by s, cut to its last N-1 ids (ctcdecode's make_ngram: one <s>, no padding).
+ * ln P(c | h), h of length L <= N-1: for k = L down to 0: if the n-gram (last k ids of h, c) is stored, the result is the backoffs
+ *   accumulated so far plus its log-prob; otherwise the backoff of (last k ids of h) is added if that n-gram is stored (0 if not, and
+ *   for k = 0) and the context is shortened.  The sum runs in f32, longest context first.  If c or any id of h has no unigram entry
+ *   the result is oov_score (ctcdecode's OOV_SCORE is -1000.0), before alpha is applied.
+ * otr_ngram_lookup: out f32 [n] = ln P(tok[q] | ctx row q).  ctx int32 [n, N-1]: row q holds its ctx_len[q] ids oldest first, left
+ *   aligned (ctx_len clamped to [0, N-1]; ctx and ctx_len may be NULL when N = 1); tok int32 [n].  An id outside [0, V] gives
+ *   oov_score.  One thread per query; every probe it can need is issued before any result is consumed.  n = 0: nothing to do.
+ * Fusion (otr_ctc_beam_search_lm): every contribution to pnb'(s+c) in the recursion of otr_ctc_beam_search gains the addend
+ *   a(s+c) = alpha * ln P(c | context(s)) + beta.  It depends on the new string only, so the extension from the parent and the merge
+ *   of that extension into a string already in the beam add the same value.  Blank and repeat stays gain nothing.  With nothing
+ *   pruned, score(s) = ln P_ctc(s) + alpha * ln P_LM(s) + beta * |s|.  Candidates, ranking, tie order, the per-slot cut and the
+ *   outputs are those of otr_ctc_beam_search, whose arguments keep their meaning; the addend enters an extension's score before it
+ *   is ranked.  New output lm_scores f32 [B, W]: the sum of the addends of the hypothesis (0 for the empty one and for slots past
+ *   the live beam), so scores - lm_scores is the acoustic part.  alpha = beta = 0 gives otr_ctc_beam_search's outputs bit for bit.
+ *   One launch, no allocation, no host synchronisation. */
+int32_t otr_ngram_lookup(const void* table, int64_t capacity, int32_t max_probe, int32_t order, int32_t V, const int32_t* ctx,
+                         const int32_t* ctx_len, const int32_t* tok, int64_t n, float oov_score, float* out, void* stream);
+int32_t otr_ctc_beam_search_lm(const float* top_lp, const int32_t* top_tok, const int32_t* lengths, int32_t B, int32_t T, int32_t V,
+                               int32_t K, int32_t blank, int32_t W, void* workspace, int64_t ws_bytes, int64_t* tokens,
+                               int32_t* out_len, float* scores, const void* table, int64_t capacity, int32_t max_probe,
+                               int32_t order, float alpha, float beta, float oov_score, float* lm_scores, void* stream);
 
 /* ---- CTC forced alignment (token time stamps from the CTC head: what ctcdecode's `timesteps`, dropped at recognize/ctc.py:64, gives
  *      for the decoded string), csrc/ctcalign.hip.  The most probable CTC path of a KNOWN label sequence.  f32 in both builds.

@@ -5,8 +5,12 @@
 //                     bitwise search over wave-wide counts, then the <= K winners are compacted and ranked in LDS.
 //  * ctc_beam_search: one workgroup per utterance runs every frame.  Beam state (pb, pnb, last token, length, prefix hash, parent
 //                     hash, trie node) lives in LDS; the back-pointer trie {parent node, token} lives in the caller's workspace and
-//                     is walked once after the last frame to write the hypotheses.
-#include "common.h"
+//                     is walked once after the last frame to write the hypotheses.  The kernel is a template: <false> is the plain
+//                     search, <true> (otr_ctc_beam_search_lm) adds the n-gram LM addend of include/otrans_hip.h to every
+//                     extension.  There a slot also carries its LM context (ids, the backoffs of its suffixes, an OOV mask),
+//                     the addend of its last token and its summed LM score; the table (ngram.h) is probed once per
+//                     (slot, candidate) in step 1 and once per new slot in step 3.
+#include "ngram.h"
 
 #define NEG_INF (-__builtin_huge_valf())
 
@@ -108,9 +112,27 @@ __device__ __forceinline__ uint64_t cb_hash(uint64_t h, int c) {   // prefix has
 __device__ __forceinline__ bool cb_better(float s, int key, float s2, int key2) { return s > s2 || (s == s2 && key < key2); }
 struct CbPair { float s; int k; };   // (score, token) of an extension / (score, key) of a candidate: one 8-byte LDS read per compare
 
+struct CbLm {          // the LM path's arguments (unused by the plain instantiation)
+  NgTable t;
+  int order, V;        // V = the id of <s>
+  float alpha, beta, oov_score;
+  float* lm_scores;
+};
+// alpha * ln P(c | context) + beta from the probes of (context suffix, c): `bad` = the context window holds an OOV id
+__device__ __forceinline__ float cb_addend(const CbLm& lm, uint32_t found, const float (&lp)[NG_MAXN], const float* ctx_bo, int L, bool bad) {
+  const float p = (bad || !(found & 1u)) ? lm.oov_score : ng_combine(found, lp, ctx_bo, L);
+  return lm.alpha * p + lm.beta;
+}
+
+template <bool LM>
 __global__ __launch_bounds__(CB_NT) void ctc_beam_search_kernel(const float* top_lp, const int32_t* top_tok, const int32_t* lengths,
                                                                int T, int K, int blank, int W, int2* trie, int64_t* tokens,
-                                                               int32_t* out_len, float* scores) {
+                                                               int32_t* out_len, float* scores, CbLm lm) {
+  constexpr int LW = LM ? CB_MAXW : 1;
+  __shared__ uint64_t s_cx[2][LW];                     // LM context: <s> + prefix cut to its newest order-1 ids, newest id lowest
+  __shared__ float s_bo[2][LW][NG_MAXN - 1];           // backoff of the newest k ids of the context at [k - 1], 0 where not stored
+  __shared__ int s_cl[2][LW];                          // context length | OOV mask << 8 (bit j: the j-th newest id has no unigram)
+  __shared__ float s_add[2][LW], s_lm[2][LW];          // addend of the slot's last token (the 1b merge adds it), summed addends
   __shared__ float f_lp[CB_MAXK];
   __shared__ int f_tok[CB_MAXK];
   __shared__ float s_pb[2][CB_MAXW], s_pnb[2][CB_MAXW];
@@ -126,6 +148,19 @@ __global__ __launch_bounds__(CB_NT) void ctc_beam_search_kernel(const float* top
   if (tid == 0) {
     s_pb[0][0] = 0.f; s_pnb[0][0] = NEG_INF; s_last[0][0] = -1; s_len[0][0] = 0; s_node[0][0] = -1;
     s_h[0][0] = CB_H0; s_ph[0][0] = 0;
+    if constexpr (LM) {
+      s_add[0][0] = 0.f; s_lm[0][0] = 0.f;
+      s_cx[0][0] = (uint64_t)lm.V;
+      int cl = 0;
+      for (int k = 0; k < NG_MAXN - 1; ++k) s_bo[0][0][k] = 0.f;
+      if (lm.order > 1) {                              // the context is <s>: its backoff, or the OOV mark where it has no unigram
+        float lp[NG_MAXN], bo[NG_MAXN];
+        const uint32_t f = ng_probe_grams(lm.t, 0, 0, lm.V, lp, bo);
+        if (f & 1u) s_bo[0][0][0] = bo[0];
+        cl = 1 | ((f & 1u) ? 0 : 1 << 8);
+      }
+      s_cl[0][0] = cl;
+    }
   }
   int cur = 0, n = 1;
   const bool loader = tid < K;                         // K <= 128 < CB_NT
@@ -153,6 +188,14 @@ __global__ __launch_bounds__(CB_NT) void ctc_beam_search_kernel(const float* top
 #pragma unroll 8
         for (int j = 0; j < n; ++j)
           if (s_len[cur][j] == l1 && s_last[cur][j] == c && s_ph[cur][j] == h) s = NEG_INF;
+        if constexpr (LM) {
+          if (s != NEG_INF) {                          // the <= order probes of (context suffix, c), all in flight together
+            float lp[NG_MAXN], bo[NG_MAXN];
+            const int cl = s_cl[cur][i], L = cl & 0xff;
+            const uint32_t f = ng_probe_grams(lm.t, s_cx[cur][i], L, c, lp, bo);
+            s += cb_addend(lm, f, lp, s_bo[cur][i], L, (cl >> 8) != 0);
+          }
+        }
       }
       x_s[e] = CbPair{s, c};
     }
@@ -172,8 +215,12 @@ __global__ __launch_bounds__(CB_NT) void ctc_beam_search_kernel(const float* top
         const int l0 = s_len[cur][j] - 1;
 #pragma unroll 8
         for (int i = 0; i < n; ++i)
-          if (s_len[cur][i] == l0 && s_h[cur][i] == ph)
-            pnb = cb_lae(pnb, (s_last[cur][i] == lj ? s_pb[cur][i] : cb_lae(s_pb[cur][i], s_pnb[cur][i])) + pl);
+          if (s_len[cur][i] == l0 && s_h[cur][i] == ph) {
+            if constexpr (LM)                            // the same string: the same addend as when slot j was made
+              pnb = cb_lae(pnb, (s_last[cur][i] == lj ? s_pb[cur][i] : cb_lae(s_pb[cur][i], s_pnb[cur][i])) + pl + s_add[cur][j]);
+            else
+              pnb = cb_lae(pnb, (s_last[cur][i] == lj ? s_pb[cur][i] : cb_lae(s_pb[cur][i], s_pnb[cur][i])) + pl);
+          }
       }
       st_pb[j] = pb;
       st_pnb[j] = pnb;
@@ -215,12 +262,32 @@ __global__ __launch_bounds__(CB_NT) void ctc_beam_search_kernel(const float* top
         s_pb[nxt][r] = st_pb[i]; s_pnb[nxt][r] = st_pnb[i];
         s_last[nxt][r] = s_last[cur][i]; s_len[nxt][r] = s_len[cur][i]; s_node[nxt][r] = s_node[cur][i];
         s_h[nxt][r] = s_h[cur][i]; s_ph[nxt][r] = s_ph[cur][i];
+        if constexpr (LM) {
+          s_cx[nxt][r] = s_cx[cur][i]; s_cl[nxt][r] = s_cl[cur][i]; s_add[nxt][r] = s_add[cur][i]; s_lm[nxt][r] = s_lm[cur][i];
+          for (int k = 0; k < NG_MAXN - 1; ++k) s_bo[nxt][r][k] = s_bo[cur][i][k];
+        }
       } else {
         const int c = tp - 1;
         s_pb[nxt][r] = NEG_INF; s_pnb[nxt][r] = s;
         s_last[nxt][r] = c; s_len[nxt][r] = s_len[cur][i] + 1; s_node[nxt][r] = t * W + r;
         s_h[nxt][r] = cb_hash(s_h[cur][i], c); s_ph[nxt][r] = s_h[cur][i];
         tr[t * W + r] = make_int2(s_node[cur][i], c);
+        if constexpr (LM) {
+          // the probes of step 1 again (the entries are in cache): their log-probs give the addend, their backoffs are those of
+          // the new context's suffixes, and a missing unigram marks c as OOV for the slots that will hold it in their window
+          float lp[NG_MAXN], bo[NG_MAXN];
+          const int cl = s_cl[cur][i], L = cl & 0xff, N1 = lm.order - 1;
+          const uint32_t f = ng_probe_grams(lm.t, s_cx[cur][i], L, c, lp, bo);
+          const float a = cb_addend(lm, f, lp, s_bo[cur][i], L, (cl >> 8) != 0);
+          s_add[nxt][r] = a;
+          s_lm[nxt][r] = s_lm[cur][i] + a;
+          const int L2 = min(L + 1, N1);
+          const uint64_t keep = N1 >= 4 ? ~0ull : (1ull << (16 * N1)) - 1ull;
+          s_cx[nxt][r] = ((s_cx[cur][i] << 16) | (uint64_t)(uint32_t)c) & keep;
+          const int oov = (((cl >> 8) << 1) | ((f & 1u) ? 0 : 1)) & ((1 << N1) - 1);
+          s_cl[nxt][r] = L2 | (oov << 8);
+          for (int k = 0; k < NG_MAXN - 1; ++k) s_bo[nxt][r][k] = (k < L2 && (f >> k & 1)) ? bo[k] : 0.f;
+        }
       }
     }
     __syncthreads();
@@ -238,6 +305,7 @@ __global__ __launch_bounds__(CB_NT) void ctc_beam_search_kernel(const float* top
     const bool live = r < n;
     const int l = live ? s_len[cur][r] : 0;
     scores[b * W + r] = live ? cb_lae(s_pb[cur][r], s_pnb[cur][r]) : NEG_INF;
+    if constexpr (LM) lm.lm_scores[b * W + r] = live ? s_lm[cur][r] : 0.f;
     out_len[b * W + r] = l;
     int node = live ? s_node[cur][r] : -1;
     for (int pos = l - 1; pos >= 0; --pos) {
@@ -283,7 +351,30 @@ extern "C" int32_t otr_ctc_beam_search(const float* top_lp, const int32_t* top_t
   const int64_t need = otr_ctc_beam_workspace_bytes(B, T, W);
   OTR_REQUIRE(ws_bytes >= need, "ctc_beam_search: workspace of %lld bytes, %lld needed (otr_ctc_beam_workspace_bytes)",
               (long long)ws_bytes, (long long)need);
-  hipLaunchKernelGGL(ctc_beam_search_kernel, dim3(B), dim3(CB_NT), 0, (hipStream_t)stream, top_lp, top_tok, lengths, T, K, blank, W,
-                     (int2*)workspace, tokens, out_len, scores);
+  hipLaunchKernelGGL(ctc_beam_search_kernel<false>, dim3(B), dim3(CB_NT), 0, (hipStream_t)stream, top_lp, top_tok, lengths, T, K, blank,
+                     W, (int2*)workspace, tokens, out_len, scores, CbLm{});
   return otr_check_launch("ctc_beam_search");
+}
+
+extern "C" int32_t otr_ctc_beam_search_lm(const float* top_lp, const int32_t* top_tok, const int32_t* lengths, int32_t B, int32_t T,
+                                          int32_t V, int32_t K, int32_t blank, int32_t W, void* workspace, int64_t ws_bytes,
+                                          int64_t* tokens, int32_t* out_len, float* scores, const void* table, int64_t capacity,
+                                          int32_t max_probe, int32_t order, float alpha, float beta, float oov_score,
+                                          float* lm_scores, void* stream) {
+  OTR_REQUIRE(top_lp && top_tok && lengths && workspace && tokens && out_len && scores && lm_scores, "ctc_beam_search_lm: null pointer");
+  OTR_REQUIRE(B >= 1 && T >= 1, "ctc_beam_search_lm: bad shape B=%d T=%d", B, T);
+  OTR_REQUIRE(W >= 1 && W <= CB_MAXW, "ctc_beam_search_lm: beam width W=%d must be in [1, %d]", W, CB_MAXW);
+  OTR_REQUIRE(V >= 1 && V <= CB_MAXV, "ctc_beam_search_lm: V=%d must be in [1, %d]", V, CB_MAXV);
+  OTR_REQUIRE(K >= 1 && K <= CB_MAXK && K <= V, "ctc_beam_search_lm: K=%d must be in [1, min(%d, V=%d)]", K, CB_MAXK, V);
+  OTR_REQUIRE(blank >= 0 && blank < V, "ctc_beam_search_lm: blank=%d must be in [0, V=%d)", blank, V);
+  OTR_REQUIRE(((uintptr_t)workspace & 7) == 0, "ctc_beam_search_lm: workspace must be 8-byte aligned");
+  const int64_t need = otr_ctc_beam_workspace_bytes(B, T, W);
+  OTR_REQUIRE(ws_bytes >= need, "ctc_beam_search_lm: workspace of %lld bytes, %lld needed (otr_ctc_beam_workspace_bytes)",
+              (long long)ws_bytes, (long long)need);
+  if (otr_ngram_check_table("ctc_beam_search_lm", table, capacity, max_probe, order, V) < 0) return -1;
+  OTR_REQUIRE(alpha == alpha && beta == beta && oov_score == oov_score, "ctc_beam_search_lm: alpha, beta and oov_score must be numbers");
+  const CbLm lm{NgTable{(const uint4*)table, (uint32_t)(capacity - 1), max_probe}, order, V, alpha, beta, oov_score, lm_scores};
+  hipLaunchKernelGGL(ctc_beam_search_kernel<true>, dim3(B), dim3(CB_NT), 0, (hipStream_t)stream, top_lp, top_tok, lengths, T, K, blank,
+                     W, (int2*)workspace, tokens, out_len, scores, lm);
+  return otr_check_launch("ctc_beam_search_lm");
 }

@@ -3651,10 +3651,14 @@ def ctc_prefix_beam_search(log_probs, lengths, beam_width=5, cutoff_top_n=40, bl
     each utterance's beam in descending score order; slots past the live beam have score -inf and length 0.  cutoff_top_n is
     clamped to V.  ctcdecode's score-threshold pruning (cutoff_prob / "min_cutoff") is not applied.  Two launches on the current
     stream, no host synchronisation: capturable into a graph (pass `workspace`, otr_ctc_beam_workspace_bytes bytes, to reuse one)."""
+    return _ctc_prefix_beam_search('ctc_prefix_beam_search', log_probs, lengths, beam_width, cutoff_top_n, blank, workspace, None)
+
+
+def _ctc_prefix_beam_search(who, log_probs, lengths, beam_width, cutoff_top_n, blank, workspace, lm):
+    """the argument checks, the buffers and the top-K pass both searches share; lm = None or (NGramLM, alpha, beta)"""
     _cuda(log_probs, lengths)
     if log_probs.dim() != 3 or log_probs.dtype != torch.float32:
-        raise L.OtransHipError('ctc_prefix_beam_search: log_probs must be f32 [B, T, V], got %s %s'
-                               % (log_probs.dtype, tuple(log_probs.shape)))
+        raise L.OtransHipError('%s: log_probs must be f32 [B, T, V], got %s %s' % (who, log_probs.dtype, tuple(log_probs.shape)))
     B, T, V = log_probs.shape
     W, K = int(beam_width), min(int(cutoff_top_n), V)
     lib = L.load()
@@ -3663,7 +3667,9 @@ def ctc_prefix_beam_search(log_probs, lengths, beam_width=5, cutoff_top_n=40, bl
     dev = log_probs.device
     need = lib.otr_ctc_beam_workspace_bytes(B, T, W)
     if need < 0 or not 0 <= blank < V:            # refused before the first launch (the library checks everything again)
-        raise L.OtransHipError('ctc_prefix_beam_search: bad arguments B=%d T=%d beam_width=%d blank=%d V=%d' % (B, T, W, blank, V))
+        raise L.OtransHipError('%s: bad arguments B=%d T=%d beam_width=%d blank=%d V=%d' % (who, B, T, W, blank, V))
+    if lm is not None and lm[0].vocab_size != V:
+        raise L.OtransHipError('%s: the n-gram LM was loaded for %d units, log_probs has V=%d' % (who, lm[0].vocab_size, V))
     top_lp = torch.empty((B * T, K), dtype=torch.float32, device=dev)
     top_tok = torch.empty((B * T, K), dtype=torch.int32, device=dev)
     if workspace is None:
@@ -3672,10 +3678,45 @@ def ctc_prefix_beam_search(log_probs, lengths, beam_width=5, cutoff_top_n=40, bl
     out_len = torch.empty((B, W), dtype=torch.int32, device=dev)
     scores = torch.empty((B, W), dtype=torch.float32, device=dev)
     L.check(lib.otr_ctc_topk(_p(lp), lp.stride(1), _p(ln), B, T, V, K, _p(top_lp), _p(top_tok), _stream()), 'otr_ctc_topk')
-    L.check(lib.otr_ctc_beam_search(_p(top_lp), _p(top_tok), _p(ln), B, T, V, K, blank, W, _p(workspace),
-                                    workspace.numel() * workspace.element_size(), _p(tokens), _p(out_len), _p(scores), _stream()),
-            'otr_ctc_beam_search')
-    return tokens, out_len, scores
+    if lm is None:
+        L.check(lib.otr_ctc_beam_search(_p(top_lp), _p(top_tok), _p(ln), B, T, V, K, blank, W, _p(workspace),
+                                        workspace.numel() * workspace.element_size(), _p(tokens), _p(out_len), _p(scores), _stream()),
+                'otr_ctc_beam_search')
+        return tokens, out_len, scores
+    ngram, alpha, beta = lm
+    table = ngram.device_table(dev)
+    lm_scores = torch.empty((B, W), dtype=torch.float32, device=dev)
+    L.check(lib.otr_ctc_beam_search_lm(_p(top_lp), _p(top_tok), _p(ln), B, T, V, K, blank, W, _p(workspace),
+                                       workspace.numel() * workspace.element_size(), _p(tokens), _p(out_len), _p(scores), _p(table),
+                                       ngram.capacity, ngram.max_probe, ngram.order, float(alpha), float(beta), ngram.oov_score,
+                                       _p(lm_scores), _stream()), 'otr_ctc_beam_search_lm')
+    return tokens, out_len, scores, lm_scores
+
+
+def ctc_prefix_beam_search_lm(log_probs, lengths, ngram, alpha, beta, beam_width=5, cutoff_top_n=40, blank=0, workspace=None):
+    """ctc_prefix_beam_search with a backoff n-gram LM fused into the search (include/otrans_hip.h otr_ctc_beam_search_lm): every
+    extension s -> s+c gains alpha * ln P_LM(c | <s> s) + beta, what ctcdecode.CTCBeamDecoder does with a character-based scorer.
+    `ngram`: an opentransformer_amd.ngram.NGramLM loaded for the V units of log_probs (uploaded on first use; graph capture wants
+    ngram.to(device) called before).  Returns (tokens, out_len, scores, lm_scores f32 [B, W]): scores include the LM term,
+    lm_scores is that term alone (scores - lm_scores: the acoustic log-probability).  Same launches, same capturability."""
+    return _ctc_prefix_beam_search('ctc_prefix_beam_search_lm', log_probs, lengths, beam_width, cutoff_top_n, blank, workspace,
+                                   (ngram, alpha, beta))
+
+
+def ngram_lookup(ngram, ctx, ctx_len, tok):
+    """ln P(tok | ctx) of an NGramLM on the device (include/otrans_hip.h otr_ngram_lookup): ctx int32 [n, max(order-1, 1)] rows of
+    context ids oldest first, left aligned, ctx_len int32 [n], tok int32 [n] -> f32 [n].  NGramLM.lookup builds these from lists."""
+    _cuda(ctx, ctx_len, tok)
+    n = tok.numel()
+    ctx, ctx_len, tok = ctx.to(torch.int32).contiguous(), ctx_len.to(torch.int32).contiguous(), tok.to(torch.int32).contiguous()
+    if ctx_len.numel() != n or ctx.numel() != n * max(ngram.order - 1, 1):
+        raise L.OtransHipError('ngram_lookup: ctx %s / ctx_len %s do not match %d tokens at order %d'
+                               % (tuple(ctx.shape), tuple(ctx_len.shape), n, ngram.order))
+    table = ngram.device_table(tok.device)
+    out = torch.empty(n, dtype=torch.float32, device=tok.device)
+    L.check(L.load().otr_ngram_lookup(_p(table), ngram.capacity, ngram.max_probe, ngram.order, ngram.vocab_size, _p(ctx), _p(ctx_len),
+                                      _p(tok), n, ngram.oov_score, _p(out), _stream()), 'otr_ngram_lookup')
+    return out
 
 
 CTC_ALIGN_MAX_TGT = 127

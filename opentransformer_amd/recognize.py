@@ -21,6 +21,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
+from .ngram import NGramLM
 from .nn import (BOS, EOS, PAD, LabelSmoothingLoss, PositionalEncoding, TransformerEncoderLayer)
 
 _DECODE_STEP_FUSED = True   # cached beam step on otr_dec_self_step + the fused tail
@@ -903,17 +904,21 @@ class CTCRecognizer(Recognizer):
     mode 'greedy': per-frame arg-max, repeats and blanks collapsed.  mode 'beam': CTC prefix beam search on the device
     (ops.ctc_prefix_beam_search; cutoff_top_n defaults to 40 as in ctcdecode.CTCBeamDecoder) in place of the reference's ctcdecode_edited; the
     1-best of the beam.  The two differ in general, also at beam_width 1: the beam sums the probability of every path of a prefix,
-    greedy follows the single best path.  There is no KenLM here, so ngram_lm must be None; alpha / beta are then unused, as in
-    ctcdecode without a scorer, and lm / lm_weight are unused in beam mode as in the reference."""
+    greedy follows the single best path.  ngram_lm: None, or an ngram.NGramLM (a backoff n-gram over the units, NGramLM.from_arpa):
+    in beam mode every extension then gains alpha * ln P_LM + beta inside the search (ops.ctc_prefix_beam_search_lm), ctcdecode's
+    character-based scorer; greedy mode ignores it, as the reference does.  A path is not loaded here (build_recognizer does that);
+    without an LM alpha / beta are unused, as in ctcdecode without a scorer.  lm / lm_weight are unused in beam mode as in the
+    reference."""
 
     def __init__(self, model, lm=None, lm_weight=0.1, ngram_lm=None, beam_width=5, idx2unit=None, ngpu=1,
                  mode='greedy', alpha=0.1, beta=0.0, cutoff_top_n=40):
         super().__init__(model, idx2unit, lm, lm_weight, ngpu)
         if mode not in ('greedy', 'beam'):
             raise NotImplementedError("CTCRecognizer mode '%s': 'greedy' and 'beam' are built" % mode)
-        if mode == 'beam' and ngram_lm is not None:
-            raise NotImplementedError('CTCRecognizer: n-gram LM scoring (KenLM) is not built; use ngram_lm=None')
-        self.beam_width, self.mode = beam_width, mode
+        if mode == 'beam' and ngram_lm is not None and not isinstance(ngram_lm, NGramLM):
+            raise NotImplementedError('CTCRecognizer: ngram_lm must be an NGramLM, not %s: load the ARPA file with '
+                                      'NGramLM.from_arpa(path, idx2unit) (KenLM binaries are not read)' % type(ngram_lm).__name__)
+        self.beam_width, self.mode, self.ngram_lm = beam_width, mode, ngram_lm
         self.alpha, self.beta, self.cutoff_top_n = alpha, beta, cutoff_top_n
 
     @torch.no_grad()
@@ -944,10 +949,16 @@ class CTCRecognizer(Recognizer):
         x, mask, _ = self.model.frontend.inference(inputs, inputs_mask, None)
         memory, memory_mask, _ = self.model.encoder(x, mask)
         log_probs, length = self.model.assistor.inference(memory, memory_mask)      # look-ahead conv + log_softmax, f32
-        tokens, out_len, _ = ops.ctc_prefix_beam_search(log_probs, length, beam_width=self.beam_width, cutoff_top_n=self.cutoff_top_n,
-                                                        blank=self.model.assistor.blank)
+        tokens, out_len = self._beam(log_probs, length)
         best, n = tokens[:, 0].cpu(), out_len[:, 0].cpu()
         return [best[b, :int(n[b])].tolist() for b in range(best.size(0))]
+
+    def _beam(self, log_probs, length):
+        """the beam of the CTC head's log-probs, with the n-gram LM fused in where one was given: (tokens, out_len)"""
+        kw = dict(beam_width=self.beam_width, cutoff_top_n=self.cutoff_top_n, blank=self.model.assistor.blank)
+        if self.ngram_lm is None:
+            return ops.ctc_prefix_beam_search(log_probs, length, **kw)[:2]
+        return ops.ctc_prefix_beam_search_lm(log_probs, length, self.ngram_lm, self.alpha, self.beta, **kw)[:2]
 
     def recognize(self, inputs, inputs_mask):
         if self.mode == 'beam':
@@ -991,8 +1002,7 @@ class CTCRecognizer(Recognizer):
         blank = self.model.assistor.blank
         if self.mode == 'beam':
             log_probs, length = self.model.assistor.inference(memory, memory_mask)
-            tokens, out_len, _ = ops.ctc_prefix_beam_search(log_probs, length, beam_width=self.beam_width, cutoff_top_n=self.cutoff_top_n,
-                                                            blank=blank)
+            tokens, out_len = self._beam(log_probs, length)       # the alignment below runs on the acoustic log-probs alone
             best, n = tokens[:, 0].cpu(), out_len[:, 0].cpu()
             preds = [best[b, :int(n[b])].tolist() for b in range(best.size(0))]
         else:                                                                   # recognize_greedy's logits: no look-ahead
@@ -1037,7 +1047,10 @@ def build_recognizer(model_type, model, lm, args, idx2unit):
                                       joint_ctc=getattr(args, 'joint_ctc', False), ctc_beam=getattr(args, 'ctc_beam', None),
                                       rescore=getattr(args, 'rescore', False))
     if model_type == 'ctc':
-        return CTCRecognizer(model=model, lm=lm, lm_weight=args.lm_weight, ngram_lm=args.ngram_lm,
+        ngram_lm = args.ngram_lm
+        if isinstance(ngram_lm, str):                                           # the reference passes the path on to ctcdecode
+            ngram_lm = NGramLM.from_arpa(ngram_lm, idx2unit)
+        return CTCRecognizer(model=model, lm=lm, lm_weight=args.lm_weight, ngram_lm=ngram_lm,
                              beam_width=args.beam_width, idx2unit=idx2unit, ngpu=args.ngpu, mode=args.mode,
                              alpha=args.alpha, beta=args.beta)
     raise NotImplementedError
