@@ -37,9 +37,10 @@ extern "C" {
 
 /* ABI version of THIS header: bumped whenever a signature, a descriptor struct or the meaning of an argument changes (600: round 6;
  * 300 was rounds 3-5, during which otr_optimizer_step, otr_ln_desc_t, otr_wgrad_item_t and otr_beam_prune_cached changed without a
- * bump; 602: the rescoring entries, additions only; 603: otr_ctc_align, additions only; 604: otr_ngram_lookup and otr_ctc_beam_search_lm, additions only).  A binding compares otr_version() with the OTR_ABI_VERSION it was written against BEFORE its first call and refuses a
+ * bump; 602: the rescoring entries, additions only; 603: otr_ctc_align, additions only; 604: otr_ngram_lookup and otr_ctc_beam_search_lm, additions only; 605:
+ * otr_edit_distance, additions only).  A binding compares otr_version() with the OTR_ABI_VERSION it was written against BEFORE its first call and refuses a
  * library that answers anything else: descriptors are passed by pointer and read at the library's idea of their size. */
-#define OTR_ABI_VERSION 604
+#define OTR_ABI_VERSION 605
 int32_t otr_version(void);
 /* OTR_BF16 or OTR_F16: the 16-bit type this library was built for */
 int32_t otr_half_type(void);
@@ -752,6 +753,30 @@ int64_t otr_ctc_align_workspace_bytes(int32_t B, int32_t T, int32_t max_tgt);
 int32_t otr_ctc_align(const float* log_probs, int64_t ld, const int64_t* targets, int64_t ldt, const int32_t* in_len,
                       const int32_t* tgt_len, int32_t B, int32_t T, int32_t V, int32_t max_tgt, int32_t blank, void* workspace,
                       int64_t ws_bytes, int32_t* frame_token, int32_t* spans, float* label_logp, float* score, void* stream);
+
+/* ---- WER / CER scoring: batched edit distance with corpus totals (the editdistance.eval calls of eval.py:160-178 and
+ *      tools/computer_wer.py), csrc/editdist.hip.  Integer only, identical in both builds.
+ * Pair (b, n) scores hypothesis n of utterance b against reference b.  ref int64 [B, Lr], row b at ref + b*ref_bs, ref_len int32 [B];
+ * hyp int64 [B, N, Lh], hypothesis (b, n) at hyp + b*hyp_bs + n*hyp_ns, hyp_len int32 [B, N] (contiguous); all on the device.
+ * eos >= 0: a hypothesis ends before its first token equal to eos among its first hyp_len tokens; eos = -1: none.
+ * Tokens are compared as integers.  Nothing at or beyond a length is ever read: the padding may hold anything.
+ * D[i][j] is the textbook Levenshtein table with unit costs, i over the R reference tokens and j over the H hypothesis tokens:
+ *   D[0][j] = j, D[i][0] = i, D[i][j] = min(D[i-1][j-1] + (ref[i-1] != hyp[j-1]), D[i-1][j] + 1, D[i][j-1] + 1);  dist = D[R][H].
+ * counts = (substitutions, deletions, insertions) of ONE canonical alignment, defined recursively: cell (i, j) takes, among the
+ *   predecessors that achieve D[i][j], the diagonal first (a match, or one substitution more), then the cell above (i-1, j) (one
+ *   deletion more), then the cell to the left (i, j-1) (one insertion more); row 0 is all insertions, column 0 all deletions.
+ *   S + D + I == dist always.
+ * A ref_len outside [0, Lr] makes every pair of the utterance invalid, a hyp_len outside [0, Lh] that pair: dist = -1, counts = -1.
+ * Outputs: dist int32 [B, N], counts int32 [B, N, 3], and totals int64 [8], ACCUMULATED into (the caller zeroes it once):
+ *   {utterances, ref_tokens, errors_1best, S_1best, D_1best, I_1best, errors_oracle, bad}.  1-best is n = 0; oracle is the least dist
+ *   over the valid n of the utterance.  An utterance enters the first seven only if its reference and its hypothesis 0 are valid,
+ *   otherwise it adds 1 to `bad` and nothing else; invalid hypotheses n > 0 are left out of the oracle.
+ * Limits, checked before the launch (a refused call returns < 0, launches nothing and leaves the outputs untouched): 1 <= N <= 32,
+ *   0 <= Lr, Lh <= 2048, B >= 0 (B = 0 returns 0 without a launch), eos >= -1, strides >= 0, totals 8-byte aligned.
+ * One launch (one workgroup per utterance, one wave per pair), no workspace, no allocation, no host synchronisation; capturable. */
+int32_t otr_edit_distance(const int64_t* ref, int64_t ref_bs, const int32_t* ref_len, const int64_t* hyp, int64_t hyp_bs,
+                          int64_t hyp_ns, const int32_t* hyp_len, int32_t B, int32_t N, int32_t Lr, int32_t Lh, int32_t eos,
+                          int32_t* dist, int32_t* counts, int64_t* totals, void* stream);
 
 /* ---- joint CTC/attention beam search (SpeechToTextRecognizer joint_ctc=True; Watanabe et al. 2017, Algorithm 2; ESPnet's
  *      CTCPrefixScore), csrc/ctcscore.hip.  f32 in every build.  lambda = ctc_weight in [0, 1]; x_t(c) = log_probs of token c at frame

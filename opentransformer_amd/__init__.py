@@ -9,6 +9,8 @@ from . import data, tools                                # noqa: F401  (batch as
 from .ops import set_compute_dtype, get_compute_dtype     # noqa: F401
 from .model import (BuildFrontEnd, BuildEncoder, BuildDecoder, End2EndModel, SpeechToText, CTCModel,   # noqa: F401
                     CTCAssistor)
+from . import evaluate                                   # noqa: F401  (WER / CER scoring on the device: evaluate.evaluate(recognizer, batches))
+from .evaluate import ErrorRateMeter, score_texts        # noqa: F401
 from .nn import (ConvFrontEnd, ConformerEncoder, ConformerEncoderBlock, ConformerConvolutionModule,   # noqa: F401
                  MultiHeadedSelfAttentionWithRelPos)
 from .nn import (ConvFrontEnd, TransformerEncoder, TransformerEncoderLayer, TransformerDecoder,   # noqa: F401

@@ -14,7 +14,7 @@ LIB_PATHS = {'bf16': os.path.join(_LIB_DIR, 'libotrans_hip.so'), 'fp16': os.path
 LIB_PATH = LIB_PATHS['bf16']
 
 OTR_F32, OTR_BF16, OTR_F16 = 0, 1, 2
-OTR_ABI_VERSION = 604           # include/otrans_hip.h: the header this binding's structures and SIGNATURES were written against
+OTR_ABI_VERSION = 605           # include/otrans_hip.h: the header this binding's structures and SIGNATURES were written against
 OTR_OPT_STATE_FLOATS = 528      # include/otrans_hip.h: floats of otr_optimizer_step's device state block
 ACT_NONE, ACT_RELU = 0, 1
 
@@ -209,6 +209,7 @@ SIGNATURES = {
                                _F32, _P, _P],
     'otr_ctc_align_workspace_bytes': [_I32, _I32, _I32],
     'otr_ctc_align': [_P, _I64, _P, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P],
+    'otr_edit_distance': [_P, _I64, _P, _P, _I64, _I64, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P],
     'otr_joint_prebeam': [_P, _I64, _P, _I64, _F32, _F32, _I64, _I32, _I32, _P, _P, _P],
     'otr_ctc_prefix_score': [_P, _I64, _P, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _P, _P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P,
                              _F32, _P, _P, _P, _I32, _P, _P, _P, _P],

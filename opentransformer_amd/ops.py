@@ -3765,6 +3765,57 @@ def ctc_forced_align(log_probs, in_len, targets, tgt_len, blank=0):
     return frame_token, spans, label_logp, score
 
 
+# ------------------------------------------------------------------ WER / CER scoring (csrc/editdist.hip)
+EDIT_MAX_LEN, EDIT_MAX_NBEST = 2048, 32
+
+
+def _rows_by_stride(t):
+    """int64 tokens whose last dimension is contiguous: widened / copied only where needed, outer strides kept"""
+    t = t.to(torch.int64)
+    return t if t.shape[-1] <= 1 or t.stride(-1) == 1 else t.contiguous()
+
+
+def edit_distance(ref, ref_len, hyp, hyp_len=None, eos=-1, totals=None):
+    """Edit distance of n-best hypotheses against their references on the device (include/otrans_hip.h otr_edit_distance).  ref int
+    [B, Lr] tokens, ref_len [B]; hyp int [B, N, Lh] (or [B, Lh]: N = 1, the outputs keep the N axis), hyp_len [B, N] (None: the full
+    width, useful with eos); eos >= 0: a hypothesis ends before its first eos.  Pair (b, n) scores hypothesis n of utterance b against
+    reference b.  Returns (dist int32 [B, N], counts int32 [B, N, 3] = substitutions / deletions / insertions of the canonical
+    alignment, totals int64 [8] = {utterances, ref_tokens, errors_1best, S, D, I, errors_oracle, bad}); `totals` is accumulated into
+    when given (a zeroed one is made otherwise).  A length outside its width gives -1s for the pair.  int32 tokens are widened; views
+    with a contiguous last dimension are passed by stride.  One launch on the current stream, no host synchronisation, capturable."""
+    if hyp.dim() == 2:
+        hyp = hyp.unsqueeze(1)
+    if ref.dim() != 2 or hyp.dim() != 3 or hyp.shape[0] != ref.shape[0]:
+        raise ValueError('edit_distance: ref must be [B, Lr] and hyp [B, N, Lh] or [B, Lh], got %s and %s' % (tuple(ref.shape), tuple(hyp.shape)))
+    B, N, Lh = hyp.shape
+    Lr = ref.shape[1]
+    if not 1 <= N <= EDIT_MAX_NBEST:
+        raise ValueError('edit_distance: %d hypotheses per utterance, 1 .. %d supported' % (N, EDIT_MAX_NBEST))
+    if Lr > EDIT_MAX_LEN or Lh > EDIT_MAX_LEN:
+        raise ValueError('edit_distance: widths Lr=%d Lh=%d, at most %d supported' % (Lr, Lh, EDIT_MAX_LEN))
+    _cuda(ref, ref_len, hyp, hyp_len, totals)
+    if ref.dtype not in (torch.int32, torch.int64) or hyp.dtype not in (torch.int32, torch.int64):
+        raise L.OtransHipError('edit_distance: tokens must be int32 or int64, got %s and %s' % (ref.dtype, hyp.dtype))
+    dev = ref.device
+    if totals is None:
+        totals = torch.zeros(8, dtype=torch.int64, device=dev)
+    elif totals.dtype != torch.int64 or totals.shape != (8,) or not totals.is_contiguous():
+        raise L.OtransHipError('edit_distance: totals must be a contiguous int64 [8] tensor')
+    r, h = _rows_by_stride(ref), _rows_by_stride(hyp)
+    rl = ref_len.to(torch.int32).contiguous()
+    hl = (torch.full((B, N), Lh, dtype=torch.int32, device=dev) if hyp_len is None
+          else hyp_len.to(torch.int32).reshape(B, N).contiguous())
+    if rl.numel() != B or min(r.stride(0), h.stride(0), h.stride(1)) < 0:
+        raise L.OtransHipError('edit_distance: bad arguments ref %s ref_len %s hyp %s' % (tuple(ref.shape), tuple(ref_len.shape), tuple(hyp.shape)))
+    dist = torch.empty((B, N), dtype=torch.int32, device=dev)
+    counts = torch.empty((B, N, 3), dtype=torch.int32, device=dev)
+    lib = L.load()
+    L.check(_timed('edit_distance %dx%dx%dx%d' % (B, N, Lr, Lh), {'bytes': B * (Lr + N * Lh) * 8},
+                   lambda: lib.otr_edit_distance(_p(r), r.stride(0), _p(rl), _p(h), h.stride(0), h.stride(1), _p(hl), B, N, Lr, Lh,
+                                                 int(eos), _p(dist), _p(counts), _p(totals), _stream())), 'otr_edit_distance')
+    return dist, counts, totals
+
+
 # ------------------------------------------------------------------ joint CTC/attention beam search (csrc/ctcscore.hip)
 JOINT_MAX_K, JOINT_MAX_T, JOINT_MAX_V, JOINT_MAX_BEAM = 32, 2048, 8192, 16
 

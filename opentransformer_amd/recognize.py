@@ -457,8 +457,46 @@ class SpeechToTextRecognizer(Recognizer):
         nbest_scores = sorted_scores[:, :min(beam, self.nbest)]
         return self.nbest_translate(nbest_preds), nbest_scores
 
+    def _nbest_device(self, scores, preds, steps, b):
+        """_nbest's selection with torch ops on the device, no copy to the host: (tokens int64 [B, n, steps] without BOS, lengths int32
+        [B, n]: a hypothesis ends before its first EOS, scores f32 [B, n]).  Equal scores may sort in another order than on the host.
+        Without a length penalty the scores are the search's own, bit for bit _nbest's; with one the pow and the division run on
+        the device here and on the host there, so they agree to float32 rounding only."""
+        beam = self.beam_width
+        scores_d = scores.view(b, beam)
+        preds_d = preds[:, :steps + 1].reshape(b, beam, -1)
+        if self.penalty:
+            lengths = torch.sum(torch.ne(preds_d, EOS).float(), dim=-1)
+            scores_d = scores_d / torch.pow((self.lamda + lengths) / (self.lamda + 1), self.penalty)
+        sorted_scores, offset = torch.sort(scores_d, dim=-1, descending=True)
+        n = min(beam, self.nbest)
+        tokens = torch.gather(preds_d, 1, offset[:, :n].unsqueeze(-1).expand(b, n, preds_d.size(-1)))[:, :, 1:].contiguous()
+        is_eos = torch.eq(tokens, EOS)
+        first = torch.where(is_eos.any(-1), is_eos.to(torch.int32).argmax(-1), torch.full_like(offset[:, :n], tokens.size(-1)))
+        return tokens, first.to(torch.int32), sorted_scores[:, :n].contiguous()
+
+    @torch.no_grad()
+    def recognize_tokens(self, inputs, inputs_mask):
+        """recognize() without the host: the n-best as device tensors (tokens int64 [B, n, L] without BOS, lengths int32 [B, n], scores
+        f32 [B, n]), best first, for ops.edit_distance / evaluate.ErrorRateMeter.  The same searches and the same selection as
+        recognize(): nbest_translate(tokens) gives its strings (it stops at the first EOS, which is where a length ends).  On the re-forward and cached
+        paths a hypothesis ends before its first EOS; on the rescore path the search's < 0 padding marks the end."""
+        if self.rescore:
+            memory, memory_mask, _, _ = self.encode(inputs, inputs_mask)
+            log_probs, length = self.model.assistor.inference(memory, memory_mask)
+            res = self.rescore_pass(memory, memory_mask, log_probs.float().contiguous(), length)
+            tok = res['tokens']
+            return tok.masked_fill(tok < 0, EOS), torch.sum(tok >= 0, dim=-1, dtype=torch.int32), res['scores']
+        search = self._search_cached if self.apply_cache else self._search
+        return self._nbest_device(*search(inputs, inputs_mask))
+
     @torch.no_grad()
     def recognize_cached(self, inputs, inputs_mask):
+        return self._nbest(*self._search_cached(inputs, inputs_mask))
+
+    @torch.no_grad()
+    def _search_cached(self, inputs, inputs_mask):
+        """the cached beam search: (scores [B*beam], prefixes [B*beam, >= steps + 1] with BOS, steps, B) on the device"""
         memory, memory_mask, _, _ = self.encode(inputs, inputs_mask)
         b, t, _ = memory.size()
         if self.joint_ctc and t > ops.JOINT_MAX_T:
@@ -483,7 +521,7 @@ class SpeechToTextRecognizer(Recognizer):
         if st.joint is not None:
             st.joint.load(*self._ctc_head(memory, memory_mask))
         cur, steps = st.run()
-        return self._nbest(st.scores[cur], st.preds[cur], steps, b)
+        return st.scores[cur], st.preds[cur], steps, b
 
     def _rescore_outputs(self):
         """the row-padded output layers of the decoder and the LM (_PaddedOutput; None where ops.linear serves), rebuilt when the
@@ -537,6 +575,11 @@ class SpeechToTextRecognizer(Recognizer):
             return self.recognize_rescore(inputs, inputs_mask)
         if self.apply_cache:
             return self.recognize_cached(inputs, inputs_mask)
+        return self._nbest(*self._search(inputs, inputs_mask))
+
+    @torch.no_grad()
+    def _search(self, inputs, inputs_mask):
+        """the re-forward beam search: (scores [B*beam], prefixes [B*beam, max_len + 2] with BOS, steps, B) on the device"""
         beam = self.beam_width
         lib = L.load()
         memory, memory_mask, _, _ = self.encode(inputs, inputs_mask)
@@ -591,7 +634,7 @@ class SpeechToTextRecognizer(Recognizer):
                 self.trace.append((preds[cur][:, :step + 1].clone(), scores[cur].clone()))
             if int(n_fin.item()) == R:           # the reference syncs here every step too (speech2text.py:67)
                 break
-        return self._nbest(scores[cur], preds[cur], steps, b)
+        return scores[cur], preds[cur], steps, b
 
 
 class CachedBeamState:
@@ -953,12 +996,31 @@ class CTCRecognizer(Recognizer):
         best, n = tokens[:, 0].cpu(), out_len[:, 0].cpu()
         return [best[b, :int(n[b])].tolist() for b in range(best.size(0))]
 
-    def _beam(self, log_probs, length):
-        """the beam of the CTC head's log-probs, with the n-gram LM fused in where one was given: (tokens, out_len)"""
+    def _beam(self, log_probs, length, with_scores=False):
+        """the beam of the CTC head's log-probs, with the n-gram LM fused in where one was given: (tokens, out_len[, scores])"""
         kw = dict(beam_width=self.beam_width, cutoff_top_n=self.cutoff_top_n, blank=self.model.assistor.blank)
         if self.ngram_lm is None:
-            return ops.ctc_prefix_beam_search(log_probs, length, **kw)[:2]
-        return ops.ctc_prefix_beam_search_lm(log_probs, length, self.ngram_lm, self.alpha, self.beta, **kw)[:2]
+            return ops.ctc_prefix_beam_search(log_probs, length, **kw)[:3 if with_scores else 2]
+        return ops.ctc_prefix_beam_search_lm(log_probs, length, self.ngram_lm, self.alpha, self.beta, **kw)[:3 if with_scores else 2]
+
+    @torch.no_grad()
+    def recognize_tokens(self, inputs, inputs_mask):
+        """recognize() as device tensors (tokens int64 [B, 1, L], lengths int32 [B, 1], scores f32 [B, 1]) for ops.edit_distance /
+        evaluate.ErrorRateMeter; translate(tokens[b, 0, :lengths[b, 0]]) gives recognize()'s strings.  Beam mode: the search's own
+        outputs narrowed to the 1-best, nothing goes through the host.  Greedy mode: the collapse of repeats and blanks is the existing
+        host loop of recognize_greedy, its lists padded with PAD and uploaded (one host round trip per batch); the score is 0."""
+        if self.mode == 'beam':
+            x, mask, _ = self.model.frontend.inference(inputs, inputs_mask, None)
+            memory, memory_mask, _ = self.model.encoder(x, mask)
+            log_probs, length = self.model.assistor.inference(memory, memory_mask)
+            tokens, out_len, scores = self._beam(log_probs, length, with_scores=True)
+            return tokens[:, :1], out_len[:, :1].to(torch.int32), scores[:, :1].float()
+        lists = self.recognize_greedy(inputs, inputs_mask)
+        B, width = len(lists), max([len(p) for p in lists] + [1])
+        tokens = torch.tensor([p + [PAD] * (width - len(p)) for p in lists], dtype=torch.long).view(B, 1, width)
+        lengths = torch.tensor([len(p) for p in lists], dtype=torch.int32).view(B, 1)
+        dev = inputs.device
+        return tokens.to(dev), lengths.to(dev), torch.zeros((B, 1), dtype=torch.float32, device=dev)
 
     def recognize(self, inputs, inputs_mask):
         if self.mode == 'beam':
