@@ -38,9 +38,9 @@ extern "C" {
 /* ABI version of THIS header: bumped whenever a signature, a descriptor struct or the meaning of an argument changes (600: round 6;
  * 300 was rounds 3-5, during which otr_optimizer_step, otr_ln_desc_t, otr_wgrad_item_t and otr_beam_prune_cached changed without a
  * bump; 602: the rescoring entries, additions only; 603: otr_ctc_align, additions only; 604: otr_ngram_lookup and otr_ctc_beam_search_lm, additions only; 605:
- * otr_edit_distance, additions only).  A binding compares otr_version() with the OTR_ABI_VERSION it was written against BEFORE its first call and refuses a
+ * otr_edit_distance, additions only; 606: otr_ngram_score_cands, otr_ngram_score_seqs and otr_rescore_select_add, additions only).  A binding compares otr_version() with the OTR_ABI_VERSION it was written against BEFORE its first call and refuses a
  * library that answers anything else: descriptors are passed by pointer and read at the library's idea of their size. */
-#define OTR_ABI_VERSION 605
+#define OTR_ABI_VERSION 606
 int32_t otr_version(void);
 /* OTR_BF16 or OTR_F16: the 16-bit type this library was built for */
 int32_t otr_half_type(void);
@@ -855,6 +855,48 @@ int32_t otr_rescore_select(const int64_t* tokens, const int32_t* out_len, const 
                            const float* att_score, const float* lm_score, int32_t B, int32_t W, int32_t T, int32_t nbest, float ctc_weight,
                            float lm_weight, float penalty, float lamda, float* total, int32_t* perm, int64_t* nbest_tokens,
                            int32_t* nbest_len, float* nbest_score, void* stream);
+
+/* ---- n-gram LM fusion for the attention, joint and two-pass decoders (SpeechToTextRecognizer ngram_lm=...; ESPnet's partial
+ *      scorers: the n-gram sees the pre-beam candidates, not all V tokens), csrc/ngramattn.hip + csrc/rescore.hip.  f32 in every build.
+ * The table, its arguments (checked as otr_ngram_lookup checks them) and ln P are those of the n-gram section above; N = order <= 5,
+ * <s> = id V, </s> = the EOS unit.  BOS == EOS here, so column 0 of a preds row is <s> by POSITION, never by value.
+ * Context of a hypothesis g = preds[r, 0:t]: <s> followed by preds[r, 1:t], cut to its last N-1 ids (the rule of the section above).
+ * Addend of extending g by candidate c:  a(g, c) = alpha * ln P(c | context(g)) + (c == eos ? 0 : beta), formed in f32 as alpha * lnP
+ *   (one rounding), then + beta (one rounding).  ln P includes oov_score (a candidate or context id without a unigram, or outside
+ *   [0, V]), applied before alpha.  EOS is scored as </s> and earns no length bonus.
+ * Candidate stage: per unfinished hypothesis the K' candidates come from otr_joint_prebeam, unchanged; a(g, c) is added to their
+ *   cand_score.  With nothing pruned (K' = V, beam >= the number of strings) a hypothesis that ended in EOS scores
+ *   (1 - lambda) ln P_att + lambda ln P_ctc + mu ln P_lm + alpha * ln P_ng(h </s>) + beta * |h|   (plain mode: lambda = 0).
+ * otr_ngram_score_cands: preds int64 [rows, ldp]; the prefix has t columns (t = *pos + 1 where pos, a device scalar, is given; else
+ *   the host t, 1 <= t <= ldp), exactly as otr_ctc_prefix_score takes them; flags u8 [rows] (may be NULL); cand_idx int32 / cand_score
+ *   f32 [rows, K'], K' <= 32.  cand_out f32 [rows, K'] = cand_score + a (may alias cand_score); rows with flags != 0 are copied
+ *   unchanged; a -inf score stays -inf, never NaN.  cand_add f32 [rows, K'] (may be NULL) = the addend alone, 0 on finished rows.
+ *   beam > 0 (select mode, beam <= min(16, K')): also the `beam` best of the K' totals in the layout otr_beam_prune /
+ *   otr_beam_prune_cached read: k_score f32 / k_idx int64 [rows, beam], descending, ties -> lower token (NaN ranks as -inf); finished
+ *   rows get k_score = -inf, k_idx = eos (the prune masks them).  beam = 0: k_score / k_idx are not touched (may be NULL).
+ *   One thread per (row, candidate); a row's context-suffix backoffs and context unigrams are probed once per row and shared by
+ *   shuffle; every probe of a thread is issued before any is consumed.  One launch, no allocation, memset or host synchronisation.
+ * otr_ngram_score_seqs: tokens int64 [n_hyp, T] (negative = padding), out_len int32 [n_hyp].  out f32 [n_hyp] =
+ *   ng(h) = alpha * (sum_l ln P(h_l | context(h_{<l})) + ln P(</s> | context(h))) + beta * |h|  for every slot with 0 <= out_len <= T
+ *   (0 otherwise); the empty hypothesis gives alpha * ln P(</s> | <s>).  A token outside [0, V] inside the length scores oov_score.
+ *   logp f32 [n_hyp] (may be NULL) = the bare sum of ln P.  One wave per hypothesis, one lane per position 0 .. len (the last is </s>),
+ *   summed in a fixed order: the same bits on every run.
+ * otr_rescore_select_add: otr_rescore_select plus add_score f32 [B, W] (may be NULL), added to total before the division by the length
+ *   penalty.  otr_rescore_select is this entry with add_score = NULL: one kernel body, its outputs bit for bit what they were.
+ *   In SpeechToTextRecognizer(rescore=True, ngram_lm=...) the first pass is otr_ctc_beam_search_lm, ctc(h) = scores - lm_scores of
+ *   that search, and add_score = ng(h) from otr_ngram_score_seqs, computed afresh (it carries the </s> term and does not inherit the
+ *   search's rounding): total(h) = (1 - lambda) att + lambda ctc + mu lm + ng, then the penalty. */
+int32_t otr_ngram_score_cands(const void* table, int64_t capacity, int32_t max_probe, int32_t order, int32_t V, const int64_t* preds,
+                              int64_t ldp, int32_t t, const int32_t* pos, const uint8_t* flags, const int32_t* cand_idx,
+                              const float* cand_score, int64_t rows, int32_t K, float alpha, float beta, float oov_score, int32_t eos,
+                              float* cand_out, float* cand_add, int32_t beam, float* k_score, int64_t* k_idx, void* stream);
+int32_t otr_ngram_score_seqs(const void* table, int64_t capacity, int32_t max_probe, int32_t order, int32_t V, const int64_t* tokens,
+                             const int32_t* out_len, int64_t n_hyp, int32_t T, float alpha, float beta, float oov_score, int32_t eos,
+                             float* out, float* logp, void* stream);
+int32_t otr_rescore_select_add(const int64_t* tokens, const int32_t* out_len, const float* ctc_score, const int32_t* n_rows,
+                               const float* att_score, const float* lm_score, const float* add_score, int32_t B, int32_t W, int32_t T,
+                               int32_t nbest, float ctc_weight, float lm_weight, float penalty, float lamda, float* total, int32_t* perm,
+                               int64_t* nbest_tokens, int32_t* nbest_len, float* nbest_score, void* stream);
 
 /* ---- transposed copies of many matrices in ONE launch (the W^T bf16 shadows that turn dx = dy.W into a
  *      forward-type GEMM; refreshed after every optimizer step).  table: DEVICE int64 [n_mats,4] rows of

@@ -91,3 +91,35 @@ __device__ __forceinline__ float ng_combine(uint32_t found, const float (&lp)[NG
   }
   return acc + lp[0];
 }
+
+// ln P(c | context) for one query that shares nothing with its neighbours (the lookup kernel, the sentence scorer).  Every probe the
+// rule can need -- the L+1 n-grams (suffix, c), the L context suffixes whose backoffs a miss adds, and the unigrams of the L-1 older
+// context ids that decide whether the window holds an OOV id -- is issued together, then combined: no probe waits for the result
+// of another.  cx: the context packed newest id first, every id in [0, V]; 0 <= L <= NG_MAXN - 1; c in [0, V].
+__device__ __forceinline__ float ng_lookup(const NgTable& t, uint64_t cx, int L, int c, float oov_score) {
+  constexpr int NP = 3 * NG_MAXN - 3;                  // 5 n-grams, 4 context suffixes, 3 older unigrams
+  uint64_t klo[NP], khi[NP];
+  float lp[NP], bo[NP];
+  const uint64_t glo = (cx << 16) | (uint64_t)(uint32_t)c;
+  const uint32_t ghi = (uint32_t)(cx >> 48);
+#pragma unroll
+  for (int k = 0; k < NG_MAXN; ++k) ng_key(glo, ghi, k + 1, klo[k], khi[k]);
+#pragma unroll
+  for (int k = 1; k < NG_MAXN; ++k) ng_key(cx, 0u, k, klo[NG_MAXN - 1 + k], khi[NG_MAXN - 1 + k]);
+#pragma unroll
+  for (int j = 1; j < NG_MAXN - 1; ++j) ng_key(cx >> (16 * j), 0u, 1, klo[2 * NG_MAXN - 2 + j], khi[2 * NG_MAXN - 2 + j]);
+  uint32_t want = (2u << L) - 1u;                                            // n-grams k = 0 .. L
+  want |= ((1u << L) - 1u) << NG_MAXN;                                       // context suffixes k = 1 .. L
+  if (L > 1) want |= ((1u << (L - 1)) - 1u) << (2 * NG_MAXN - 1);           // unigrams of context ids 1 .. L-1 (0 = the newest)
+  const uint32_t found = ng_find<NP>(t, klo, khi, want, lp, bo);
+  uint32_t need = 1u;                                  // the unigrams of c, of the newest context id and of the older ones
+  if (L > 0) need |= 1u << NG_MAXN;
+  if (L > 1) need |= ((1u << (L - 1)) - 1u) << (2 * NG_MAXN - 1);
+  if ((found & need) != need) return oov_score;        // c, the newest context id or an older one has no unigram
+  float glp[NG_MAXN], cbo[NG_MAXN - 1];
+#pragma unroll
+  for (int k = 0; k < NG_MAXN; ++k) glp[k] = lp[k];
+#pragma unroll
+  for (int k = 1; k < NG_MAXN; ++k) cbo[k - 1] = (found >> (NG_MAXN - 1 + k) & 1) ? bo[NG_MAXN - 1 + k] : 0.f;
+  return ng_combine(found, glp, cbo, L);
+}

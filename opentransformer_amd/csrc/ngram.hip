@@ -3,9 +3,7 @@
 // combine; include/otrans_hip.h states the scoring rule.
 #include "ngram.h"
 
-// One thread per query.  Every probe the rule can need -- the L+1 n-grams (suffix, tok), the L context suffixes whose backoffs a miss
-// adds, and the unigrams of the L-1 older context ids that decide whether the window holds an OOV id -- is issued together, then
-// combined: no probe waits for the result of another.
+// One thread per query (ngram.h ng_lookup: every probe the rule can need is issued together, then combined).
 __global__ __launch_bounds__(256) void ngram_lookup_kernel(NgTable t, int order, int V, const int32_t* ctx, const int32_t* ctx_len,
                                                            const int32_t* tok, int64_t n, float oov_score, float* out) {
   const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -21,34 +19,7 @@ __global__ __launch_bounds__(256) void ngram_lookup_kernel(NgTable t, int order,
     cx = (cx << 16) | (uint64_t)(uint32_t)(id & 0xffff);
   }
   if (bad) { out[q] = oov_score; return; }
-  constexpr int NP = 3 * NG_MAXN - 3;                  // 5 n-grams, 4 context suffixes, 3 older unigrams
-  uint64_t klo[NP], khi[NP];
-  float lp[NP], bo[NP];
-  const uint64_t glo = (cx << 16) | (uint64_t)(uint32_t)c;
-  const uint32_t ghi = (uint32_t)(cx >> 48);
-#pragma unroll
-  for (int k = 0; k < NG_MAXN; ++k) ng_key(glo, ghi, k + 1, klo[k], khi[k]);
-#pragma unroll
-  for (int k = 1; k < NG_MAXN; ++k) ng_key(cx, 0u, k, klo[NG_MAXN - 1 + k], khi[NG_MAXN - 1 + k]);
-#pragma unroll
-  for (int j = 1; j < NG_MAXN - 1; ++j) ng_key(cx >> (16 * j), 0u, 1, klo[2 * NG_MAXN - 2 + j], khi[2 * NG_MAXN - 2 + j]);
-  uint32_t want = (2u << L) - 1u;                                            // n-grams k = 0 .. L
-  want |= ((1u << L) - 1u) << NG_MAXN;                                       // context suffixes k = 1 .. L
-  if (L > 1) want |= ((1u << (L - 1)) - 1u) << (2 * NG_MAXN - 1);           // unigrams of context ids 1 .. L-1 (0 = the newest)
-  const uint32_t found = ng_find<NP>(t, klo, khi, want, lp, bo);
-  uint32_t need = 1u;                                  // the unigrams of tok, of the newest context id and of the older ones
-  if (L > 0) need |= 1u << NG_MAXN;
-  if (L > 1) need |= ((1u << (L - 1)) - 1u) << (2 * NG_MAXN - 1);
-  if ((found & need) != need) {
-    out[q] = oov_score;                                // tok, the newest context id or an older one has no unigram
-    return;
-  }
-  float glp[NG_MAXN], cbo[NG_MAXN - 1];
-#pragma unroll
-  for (int k = 0; k < NG_MAXN; ++k) glp[k] = lp[k];
-#pragma unroll
-  for (int k = 1; k < NG_MAXN; ++k) cbo[k - 1] = (found >> (NG_MAXN - 1 + k) & 1) ? bo[NG_MAXN - 1 + k] : 0.f;
-  out[q] = ng_combine(found, glp, cbo, L);
+  out[q] = ng_lookup(t, cx, L, c, oov_score);
 }
 
 int32_t otr_ngram_check_table(const char* who, const void* table, int64_t capacity, int32_t max_probe, int32_t order, int32_t V) {

@@ -7,7 +7,7 @@
 //                     (hypothesis, logits tensor), one WAVE per row: the row is read once (16-byte loads where its address allows) into
 //                     an online max / sum, rows at or past n_rows are never touched, no log-softmax tensor is written.  Wave w adds up
 //                     rows w, w + 4, ... in order and thread 0 adds the four partials in order: the same sum on every run.
-//  * rescore_select:  one workgroup per utterance: total = (1 - lambda) att + lambda ctc + mu lm, the length penalty, the rank of each
+//  * rescore_select:  one workgroup per utterance: total = (1 - lambda) att + lambda ctc + mu lm (+ add), the length penalty, the rank of each
 //                     of the W <= 32 entries by counting (ties -> lower CTC rank, -inf last in CTC order), then the n-best rows leave.
 #include "common.h"
 
@@ -136,8 +136,8 @@ extern "C" int32_t otr_rescore_score(const float* logits, int64_t ld, const floa
 
 // ---------------------------------------------------------------- select
 __global__ __launch_bounds__(256) void rescore_select_kernel(const int64_t* tokens, const int32_t* out_len, const float* ctc, const int32_t* n_rows,
-                                                             const float* att, const float* lm, int W, int T, int nbest, float lam, float mu,
-                                                             float penalty, float lamda, float* total, int32_t* perm, int64_t* nb_tokens,
+                                                             const float* att, const float* lm, const float* add, int W, int T, int nbest,
+                                                             float lam, float mu, float penalty, float lamda, float* total, int32_t* perm, int64_t* nb_tokens,
                                                              int32_t* nb_len, float* nb_score) {
   __shared__ float s_tot[RS_MAXW];
   __shared__ int s_src[RS_MAXW];                      // rank -> CTC slot
@@ -149,6 +149,7 @@ __global__ __launch_bounds__(256) void rescore_select_kernel(const int64_t* toke
     if (n_rows[h] > 0) {
       t = (1.f - lam) * att[h] + lam * ctc[h];
       if (lm) t += mu * lm[h];
+      if (add) t += add[h];                           // otr_rescore_select_add: a further term, inside the penalty's division
       if (penalty != 0.f) t /= powf((lamda + (float)(n_rows[h] - 1)) / (lamda + 1.f), penalty);
       if (!(t == t)) t = NEG_INF;                     // NaN ranks as -inf
     }
@@ -174,10 +175,11 @@ __global__ __launch_bounds__(256) void rescore_select_kernel(const int64_t* toke
   }
 }
 
-extern "C" int32_t otr_rescore_select(const int64_t* tokens, const int32_t* out_len, const float* ctc_score, const int32_t* n_rows,
-                                      const float* att_score, const float* lm_score, int32_t B, int32_t W, int32_t T, int32_t nbest,
-                                      float ctc_weight, float lm_weight, float penalty, float lamda, float* total, int32_t* perm,
-                                      int64_t* nbest_tokens, int32_t* nbest_len, float* nbest_score, void* stream) {
+extern "C" int32_t otr_rescore_select_add(const int64_t* tokens, const int32_t* out_len, const float* ctc_score, const int32_t* n_rows,
+                                          const float* att_score, const float* lm_score, const float* add_score, int32_t B, int32_t W,
+                                          int32_t T, int32_t nbest, float ctc_weight, float lm_weight, float penalty, float lamda,
+                                          float* total, int32_t* perm, int64_t* nbest_tokens, int32_t* nbest_len, float* nbest_score,
+                                          void* stream) {
   OTR_REQUIRE(tokens && out_len && ctc_score && n_rows && att_score && total && perm && nbest_tokens && nbest_len && nbest_score,
               "rescore_select: null pointer");
   OTR_REQUIRE(B > 0 && T > 0, "rescore_select: bad shape B=%d T=%d", B, T);
@@ -186,6 +188,14 @@ extern "C" int32_t otr_rescore_select(const int64_t* tokens, const int32_t* out_
   OTR_REQUIRE(ctc_weight >= 0.f && ctc_weight <= 1.f, "rescore_select: ctc_weight=%g must be in [0, 1]", (double)ctc_weight);
   OTR_REQUIRE(lm_weight == lm_weight && penalty == penalty && lamda + 1.f > 0.f, "rescore_select: bad lm_weight / penalty / lamda");
   hipLaunchKernelGGL(rescore_select_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, tokens, out_len, ctc_score, n_rows, att_score,
-                     lm_score, W, T, nbest, ctc_weight, lm_weight, penalty, lamda, total, perm, nbest_tokens, nbest_len, nbest_score);
+                     lm_score, add_score, W, T, nbest, ctc_weight, lm_weight, penalty, lamda, total, perm, nbest_tokens, nbest_len, nbest_score);
   return otr_check_launch("rescore_select");
+}
+
+extern "C" int32_t otr_rescore_select(const int64_t* tokens, const int32_t* out_len, const float* ctc_score, const int32_t* n_rows,
+                                      const float* att_score, const float* lm_score, int32_t B, int32_t W, int32_t T, int32_t nbest,
+                                      float ctc_weight, float lm_weight, float penalty, float lamda, float* total, int32_t* perm,
+                                      int64_t* nbest_tokens, int32_t* nbest_len, float* nbest_score, void* stream) {
+  return otr_rescore_select_add(tokens, out_len, ctc_score, n_rows, att_score, lm_score, nullptr, B, W, T, nbest, ctc_weight, lm_weight,
+                                penalty, lamda, total, perm, nbest_tokens, nbest_len, nbest_score, stream);
 }

@@ -296,3 +296,10 @@ class NGramLM:
         ctx, ln, tok = self._queries(contexts, tokens)
         return ops.ngram_lookup(self, torch.from_numpy(ctx).to(device), torch.from_numpy(ln).to(device),
                                 torch.from_numpy(tok).to(device))
+
+    def score(self, tokens, lengths, alpha=1.0, beta=0.0):
+        """Sentence scores on the device (otr_ngram_score_seqs): tokens int64 [..., T] on a GPU (negative = padding), lengths [...]
+        -> f32 [...] = alpha * (sum_l ln P(h_l | <s> h_{<l}) + ln P(</s> | <s> h)) + beta * len(h); the empty sentence scores
+        alpha * ln P(</s> | <s>).  </s> is the EOS unit, as from_arpa maps it."""
+        from . import ops
+        return ops.ngram_score_sequences(self, tokens, lengths, alpha, beta, eos=EOS)

@@ -3719,6 +3719,62 @@ def ngram_lookup(ngram, ctx, ctx_len, tok):
     return out
 
 
+def _ngram_args(ngram, dev):
+    """the table arguments every n-gram entry takes, in the order of include/otrans_hip.h"""
+    return _p(ngram.device_table(dev)), ngram.capacity, ngram.max_probe, ngram.order, ngram.vocab_size
+
+
+def ngram_score_candidates(ngram, preds, cand_idx, cand_score, alpha, beta, eos, t=0, pos=None, flags=None, beam=0, cand_out=None,
+                           with_add=False, k_score=None, k_idx=None):
+    """The n-gram addend of the pre-beam candidates (include/otrans_hip.h otr_ngram_score_cands).  preds int64 [R, ldp]: row r's prefix
+    is preds[r, :t] (t = pos + 1 with pos a device int32 scalar, when given), column 0 standing for <s>; cand_idx int32 / cand_score f32
+    [R, K'] from joint_prebeam; flags u8 [R] marks finished rows (copied unchanged).  cand_out (default: a new tensor; may be
+    cand_score itself) = cand_score + alpha * ln P(c | context) + (c == eos ? 0 : beta).  beam > 0: also the top-`beam` of each row in
+    the prune's layout (k_score f32 / k_idx int64 [R, beam]).  Returns (cand_out, cand_add or None, k_score, k_idx).  One launch on the
+    current stream, no host synchronisation: capturable (call ngram.to(device) before a capture)."""
+    _cuda(preds, cand_idx, cand_score, pos, flags)
+    if preds.dtype != torch.int64 or cand_idx.dtype != torch.int32 or cand_score.dtype != torch.float32:
+        raise L.OtransHipError('ngram_score_candidates: preds int64, cand_idx int32, cand_score f32 expected')
+    if preds.dim() != 2 or preds.stride(1) != 1 or cand_idx.shape != cand_score.shape or not cand_idx.is_contiguous() \
+            or not cand_score.is_contiguous() or cand_idx.shape[0] != preds.shape[0]:
+        raise L.OtransHipError('ngram_score_candidates: preds [R, ldp] and contiguous cand_idx / cand_score [R, K] expected, got %s %s %s'
+                               % (tuple(preds.shape), tuple(cand_idx.shape), tuple(cand_score.shape)))
+    R, K = cand_idx.shape
+    dev = preds.device
+    if cand_out is None:
+        cand_out = torch.empty_like(cand_score)
+    add = torch.empty_like(cand_score) if with_add else None
+    beam = int(beam)
+    if beam > 0 and k_score is None:
+        k_score = torch.empty((R, beam), dtype=torch.float32, device=dev)
+        k_idx = torch.empty((R, beam), dtype=torch.int64, device=dev)
+    L.check(L.load().otr_ngram_score_cands(*_ngram_args(ngram, dev), _p(preds), preds.stride(0), int(t), _p(pos) if pos is not None else None,
+                                           _p(flags) if flags is not None else None, _p(cand_idx), _p(cand_score), R, K, float(alpha),
+                                           float(beta), ngram.oov_score, int(eos), _p(cand_out), _p(add) if add is not None else None, beam,
+                                           _p(k_score) if beam > 0 else None, _p(k_idx) if beam > 0 else None, _stream()),
+            'otr_ngram_score_cands')
+    return cand_out, add, k_score, k_idx
+
+
+def ngram_score_sequences(ngram, tokens, out_len, alpha=1.0, beta=0.0, eos=1, with_logp=False):
+    """Sentence scores of an NGramLM on the device (include/otrans_hip.h otr_ngram_score_seqs).  tokens int64 [..., T] (negative =
+    padding), out_len int32 [...] lengths -> f32 [...] = alpha * (sum of ln P over the tokens and </s>) + beta * length; with_logp: also
+    the bare sum.  One launch on the current stream, the same bits on every run, capturable."""
+    _cuda(tokens, out_len)
+    if tokens.dtype != torch.int64 or tokens.shape[:-1] != out_len.shape:
+        raise L.OtransHipError('ngram_score_sequences: tokens int64 [..., T] and out_len [...] expected, got %s %s %s'
+                               % (tokens.dtype, tuple(tokens.shape), tuple(out_len.shape)))
+    T = tokens.shape[-1]
+    tok, ln = tokens.contiguous(), out_len.to(torch.int32).contiguous()
+    dev = tokens.device
+    out = torch.empty(out_len.shape, dtype=torch.float32, device=dev)
+    logp = torch.empty_like(out) if with_logp else None
+    L.check(L.load().otr_ngram_score_seqs(*_ngram_args(ngram, dev), _p(tok) if T else None, _p(ln), ln.numel(), T, float(alpha), float(beta),
+                                          ngram.oov_score, int(eos), _p(out), _p(logp) if logp is not None else None, _stream()),
+            'otr_ngram_score_seqs')
+    return (out, logp) if with_logp else out
+
+
 CTC_ALIGN_MAX_TGT = 127
 
 
@@ -3896,12 +3952,13 @@ def rescore_pack(tokens, out_len, scores, max_len, V, bos=1, eos=1):
 
 
 def attention_rescore(logits, tokens, out_len, scores, max_len, V, ctc_weight, lm_logits=None, lm_weight=0.0, nbest=1, penalty=0.0,
-                      lamda=5.0, packed=None, bos=1, eos=1):
+                      lamda=5.0, packed=None, bos=1, eos=1, add_score=None):
     """The second pass of two-pass decoding after the decoder (include/otrans_hip.h otr_rescore_*).  logits f32 [B*W * max_len, >= V]
     (any leading shape; unit stride along the vocabulary): the teacher-forced decoder output on rescore_pack's ys_in; lm_logits the same
     from the language model, or None.  tokens / out_len / scores: the search's outputs.  total = (1 - ctc_weight) att + ctc_weight ctc
     + lm_weight lm (/ the length penalty), sorted descending, ties to the lower CTC rank, dead and too long slots (-inf) last.
     `packed`: rescore_pack's result for these hypotheses (else it is formed here: one more launch).
+    `add_score`: f32 [B, W] in CTC order, added to total before the penalty's division (otr_rescore_select_add; the n-gram term).
     Returns a dict: tokens int64 [B, nbest, T] (-1 padded), len int32 [B, nbest], scores f32 [B, nbest], perm int32 [B, W] (rank -> CTC
     slot), total / att / lm f32 [B, W] in CTC order (lm None without lm_logits).  Two launches, no host synchronisation: capturable."""
     B, W, T = tokens.shape
@@ -3930,7 +3987,14 @@ def attention_rescore(logits, tokens, out_len, scores, max_len, V, ctc_weight, l
     L.check(lib.otr_rescore_score(_p(lg), lg.stride(0), _p(lmg) if lmg is not None else None, lmg.stride(0) if lmg is not None else 0,
                                   _p(ys_out), ys_out.stride(0), _p(n_rows), nh, int(max_len), int(V), _p(att),
                                   _p(lm) if lm is not None else None, _stream()), 'otr_rescore_score')
-    L.check(lib.otr_rescore_select(_p(tokens), _p(out_len), _p(scores), _p(n_rows), _p(att), _p(lm) if lm is not None else None, B, W, T,
-                                   int(nbest), float(ctc_weight), float(lm_weight or 0.0), float(penalty or 0.0), float(lamda), _p(total),
-                                   _p(perm), _p(nb_tok), _p(nb_len), _p(nb_score), _stream()), 'otr_rescore_select')
+    sel = (_p(tokens), _p(out_len), _p(scores), _p(n_rows), _p(att), _p(lm) if lm is not None else None)
+    tail = (B, W, T, int(nbest), float(ctc_weight), float(lm_weight or 0.0), float(penalty or 0.0), float(lamda), _p(total), _p(perm),
+            _p(nb_tok), _p(nb_len), _p(nb_score), _stream())
+    if add_score is None:
+        L.check(lib.otr_rescore_select(*sel, *tail), 'otr_rescore_select')
+    else:
+        _cuda(add_score)
+        if add_score.dtype != torch.float32 or add_score.numel() != nh:
+            raise L.OtransHipError('attention_rescore: add_score must be f32 [B, W], got %s %s' % (add_score.dtype, tuple(add_score.shape)))
+        L.check(lib.otr_rescore_select_add(*sel, _p(add_score.contiguous()), *tail), 'otr_rescore_select_add')
     return {'tokens': nb_tok, 'len': nb_len, 'scores': nb_score, 'perm': perm, 'total': total, 'att': att, 'lm': lm}

@@ -367,9 +367,13 @@ class _JointCTC:
         self.lengths.copy_(lengths.reshape(-1))
 
     def score(self, rec, logits, lm_logits, preds, cur, flags, k_score, k_idx, t=0, pos=None):
-        """pre-beam top-K' + CTC prefix scores + the joint top-beam of one step, reading phase cur, writing phase cur ^ 1's states"""
+        """pre-beam top-K' (+ the n-gram's addend) + CTC prefix scores + the joint top-beam of one step, reading phase cur, writing
+        phase cur ^ 1's states"""
         lam = float(rec.ctc_weight)
         ops.joint_prebeam(logits, lm_logits, 1.0 - lam, float(rec.lm_weight or 0.0), self.K, self.V, self.cand_s, self.cand_i)
+        if rec.ngram_lm is not None:                      # the n-gram's addend, in place; the prefix score ranks by counting, in any order
+            ops.ngram_score_candidates(rec.ngram_lm, preds, self.cand_i, self.cand_s, rec.alpha, rec.beta, EOS, t=t, pos=pos, flags=flags,
+                                       cand_out=self.cand_s)
         ops.ctc_prefix_score(self.lp, self.lengths, self.cand_i, preds, t, self.beam, rec.model.assistor.blank, EOS, self.jsrc[cur],
                              self.state[cur], self.state[cur ^ 1], pos=pos, cand_score=self.cand_s, ctc_weight=lam, beam=self.beam,
                              flags=flags, k_score=k_score, k_idx=k_idx, k_src=self.k_src)
@@ -389,12 +393,23 @@ class SpeechToTextRecognizer(Recognizer):
     per frame, ops.ctc_prefix_beam_search) are scored by the attention decoder -- and the LM -- in ONE teacher-forced pass each and
     re-ranked by (1 - ctc_weight) att + ctc_weight ctc + lm_weight lm, ctc being the beam's own score (include/otrans_hip.h
     otr_rescore_*, csrc/rescore.hip).  A hypothesis longer than max_len - 1 tokens is not rescored and sorts last.  Limits:
-    nbest <= beam_width <= 32, V <= 8192; not together with joint_ctc or apply_cache."""
+    nbest <= beam_width <= 32, V <= 8192; not together with joint_ctc or apply_cache.
+    ngram_lm: None, or an ngram.NGramLM over the decoder's V units (NGramLM.from_arpa).  In the step loops every pre-beam candidate c of
+    hypothesis g then gains alpha * ln P_ng(c | <s> g) + beta (EOS: scored as </s>, no beta) before it is ranked (include/otrans_hip.h
+    otr_ngram_score_cands): in the joint search the ctc_beam candidates, in the plain search the ngram_beam tokens of highest att + lm
+    (ngram_beam defaults to min(V, int(1.5 * beam_width)); limits beam_width <= 16, beam_width <= ngram_beam <= min(V, 32), V <= 8192),
+    which replace otr_beam_topk's full-vocabulary top-k.  With rescore=True the n-gram is fused into the first pass
+    (ops.ctc_prefix_beam_search_lm) and the second pass adds the hypothesis's n-gram score, computed afresh with its </s> term
+    (otr_ngram_score_seqs), to the total.  alpha / beta default as in CTCRecognizer.  A path is not loaded here (build_recognizer does)."""
 
     def __init__(self, model, lm=None, lm_weight=0.1, ctc_weight=0.0, beam_width=5, nbest=1, max_len=50,
                  idx2unit=None, penalty=0, lamda=5, ngpu=1, apply_cache=False, joint_ctc=False, ctc_beam=None, rescore=False,
-                 cutoff_top_n=40):
+                 cutoff_top_n=40, ngram_lm=None, alpha=0.1, beta=0.0, ngram_beam=None):
         super().__init__(model, idx2unit, lm, lm_weight, ngpu)
+        if ngram_lm is not None and not isinstance(ngram_lm, NGramLM):
+            raise NotImplementedError('SpeechToTextRecognizer: ngram_lm must be an NGramLM, not %s: load the ARPA file with '
+                                      'NGramLM.from_arpa(path, idx2unit) (KenLM binaries are not read)' % type(ngram_lm).__name__)
+        self.ngram_lm, self.alpha, self.beta, self.ngram_beam = ngram_lm, float(alpha), float(beta), None
         self.rescore, self.cutoff_top_n = bool(rescore), int(cutoff_top_n)
         if self.rescore:
             if joint_ctc or apply_cache:
@@ -425,6 +440,19 @@ class SpeechToTextRecognizer(Recognizer):
             if not beam_width <= self.ctc_beam <= min(V, ops.JOINT_MAX_K):
                 raise ValueError('joint_ctc=True: ctc_beam=%d must be in [beam_width=%d, min(V=%d, %d)]'
                                  % (self.ctc_beam, beam_width, V, ops.JOINT_MAX_K))
+        if ngram_lm is not None:
+            V = model.decoder.output_layer.weight.shape[0]
+            if ngram_lm.vocab_size != V:
+                raise ValueError('ngram_lm: the n-gram LM was loaded for %d units, the decoder has V=%d' % (ngram_lm.vocab_size, V))
+            if V > ops.JOINT_MAX_V:
+                raise ValueError('ngram_lm: vocabulary %d > %d' % (V, ops.JOINT_MAX_V))
+            if not self.rescore and not self.joint_ctc:       # the plain search: the pre-beam's limits (the joint search checked its own)
+                if not 1 <= beam_width <= ops.JOINT_MAX_BEAM:
+                    raise ValueError('ngram_lm: beam_width=%d must be in [1, %d]' % (beam_width, ops.JOINT_MAX_BEAM))
+                self.ngram_beam = int(ngram_beam) if ngram_beam is not None else min(V, int(1.5 * beam_width))
+                if not beam_width <= self.ngram_beam <= min(V, ops.JOINT_MAX_K):
+                    raise ValueError('ngram_lm: ngram_beam=%d must be in [beam_width=%d, min(V=%d, %d)]'
+                                     % (self.ngram_beam, beam_width, V, ops.JOINT_MAX_K))
         self.attn_weights = {}
         self.apply_cache = bool(apply_cache)
         self.use_hipgraph = True
@@ -512,6 +540,8 @@ class SpeechToTextRecognizer(Recognizer):
         key = (b, t, self.beam_width, self.max_len, ops.get_compute_dtype(), str(memory.device),
                self.lm is not None, bool(self.use_hipgraph), fp, self.joint_ctc, float(self.ctc_weight) if self.joint_ctc else None,
                self.ctc_beam)
+        if self.ngram_lm is not None:                        # a changed n-gram LM never replays a stale graph (the state pins its table)
+            key += (self.ngram_lm.device_table(memory.device).data_ptr(), self.ngram_lm.capacity, self.alpha, self.beta, self.ngram_beam)
         st = self._cached_states.get(key)
         if st is None:
             if len(self._cached_states) >= 4:                # a few shapes; each holds caches + two graphs
@@ -541,8 +571,16 @@ class SpeechToTextRecognizer(Recognizer):
         dict plus 'beam' = the search's own (tokens, out_len, scores)).  No host synchronisation: capturable into one graph once the weight packs exist (after one eager call)."""
         dec, lm, W = self.model.decoder, self.lm, self.beam_width
         V = dec.output_layer.weight.shape[0]
-        tokens, out_len, scores = ops.ctc_prefix_beam_search(log_probs, lengths, beam_width=W, cutoff_top_n=self.cutoff_top_n,
-                                                             blank=self.model.assistor.blank)
+        kw = dict(beam_width=W, cutoff_top_n=self.cutoff_top_n, blank=self.model.assistor.blank)
+        ng, ctc, ng_score = self.ngram_lm, None, None
+        if ng is None:
+            tokens, out_len, scores = ops.ctc_prefix_beam_search(log_probs, lengths, **kw)
+            ctc = scores
+        else:
+            # the n-gram shapes the n-best; the second pass takes the search's acoustic part and scores the strings afresh (with </s>)
+            tokens, out_len, scores, lm_scores = ops.ctc_prefix_beam_search_lm(log_probs, lengths, ng, self.alpha, self.beta, **kw)
+            ctc = scores - lm_scores
+            ng_score = ops.ngram_score_sequences(ng, tokens, out_len, self.alpha, self.beta, eos=EOS)
         packed = ops.rescore_pack(tokens, out_len, scores, self.max_len, V, BOS, EOS)
         ys_in = packed[0]
         out_dec, out_lm = self._rescore_outputs()
@@ -554,10 +592,11 @@ class SpeechToTextRecognizer(Recognizer):
             lm_logits = lm.logits_last(ys_in.reshape(-1, 1), out=out_lm)
         elif lm is not None:
             lm_logits = _output(out_lm, lm.output_project, lm.hidden(ys_in))
-        res = ops.attention_rescore(logits, tokens, out_len, scores, self.max_len, V, self.ctc_weight, lm_logits=lm_logits,
+        res = ops.attention_rescore(logits, tokens, out_len, ctc, self.max_len, V, self.ctc_weight, lm_logits=lm_logits,
                                     lm_weight=float(self.lm_weight or 0.0) if lm is not None else 0.0, nbest=self.nbest,
-                                    penalty=self.penalty, lamda=self.lamda, packed=packed, bos=BOS, eos=EOS)
+                                    penalty=self.penalty, lamda=self.lamda, packed=packed, bos=BOS, eos=EOS, add_score=ng_score)
         res['beam'] = (tokens, out_len, scores)           # the first pass, in CTC order
+        res['ctc'], res['ng'] = ctc, ng_score             # the terms of total beside att / lm (ng: None without an n-gram LM)
         return res
 
     @torch.no_grad()
@@ -603,6 +642,10 @@ class SpeechToTextRecognizer(Recognizer):
             log_probs, length = self._ctc_head(memory, memory_mask)
             joint = _JointCTC(b, t, self.model.decoder.output_layer.weight.shape[0], self.ctc_beam, beam, dev)
             joint.load(log_probs, length)
+        cand = None
+        if self.ngram_lm is not None and joint is None:      # the plain search with an n-gram: pre-beam + addend + select, no full top-k
+            cand = (torch.empty((R, self.ngram_beam), dtype=torch.float32, device=dev),
+                    torch.empty((R, self.ngram_beam), dtype=torch.int32, device=dev))
         cur, steps = 0, 0
         stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)    # noqa: E731
         for step in range(1, self.max_len + 1):
@@ -621,10 +664,16 @@ class SpeechToTextRecognizer(Recognizer):
                                                  beam, step, EOS, _ptr(scores[cur ^ 1]), _ptr(flags[cur ^ 1]), _ptr(preds[cur ^ 1]),
                                                  _ptr(n_fin), _ptr(joint.k_src), _ptr(joint.jsrc[cur ^ 1]), stream()), 'otr_beam_prune_joint')
             else:
-                L.check(lib.otr_beam_topk(_ptr(logits, (step - 1) * V), step * V,
-                                          _ptr(lm_logits, lm_off) if lm_logits is not None else None, lm_ld,
-                                          float(self.lm_weight or 0.0), R, V, beam, _ptr(k_score), _ptr(k_idx), stream()),
-                        'otr_beam_topk')
+                if cand is not None:
+                    ops.joint_prebeam(logits[:, step - 1], None if lm_logits is None else lm_logits.reshape(R, -1, V)[:, -1], 1.0,
+                                      float(self.lm_weight or 0.0), self.ngram_beam, V, *cand)
+                    ops.ngram_score_candidates(self.ngram_lm, preds[cur], cand[1], cand[0], self.alpha, self.beta, EOS, t=step,
+                                               flags=flags[cur], beam=beam, cand_out=cand[0], k_score=k_score, k_idx=k_idx)
+                else:
+                    L.check(lib.otr_beam_topk(_ptr(logits, (step - 1) * V), step * V,
+                                              _ptr(lm_logits, lm_off) if lm_logits is not None else None, lm_ld,
+                                              float(self.lm_weight or 0.0), R, V, beam, _ptr(k_score), _ptr(k_idx), stream()),
+                            'otr_beam_topk')
                 L.check(lib.otr_beam_prune(_ptr(k_score), _ptr(k_idx), _ptr(scores[cur]), _ptr(flags[cur]), _ptr(preds[cur]),
                                            ldp, b, beam, step, EOS, _ptr(scores[cur ^ 1]), _ptr(flags[cur ^ 1]),
                                            _ptr(preds[cur ^ 1]), _ptr(n_fin), stream()), 'otr_beam_prune')
@@ -696,6 +745,10 @@ class CachedBeamState:
         self.side = torch.cuda.Stream(device=dev) if (lm is not None and not self.paired) else None
         self.side_ws = ops.new_workspace(dev) if self.side is not None else None
         self.joint = _JointCTC(b, Tm, dec.output_layer.weight.shape[0], rec.ctc_beam, beam, dev) if rec.joint_ctc else None
+        self.ngram = rec.ngram_lm.to(dev) if rec.ngram_lm is not None else None     # pinned: the state's key holds its table's address
+        self.cand = None
+        if self.ngram is not None and self.joint is None:
+            self.cand = (new((R, rec.ngram_beam), torch.float32), new((R, rec.ngram_beam), torch.int32))
 
     def load_memory(self, memory, memory_mask):
         """Project the encoder memory to cross-attention K|V once per utterance and layer
@@ -886,8 +939,13 @@ class CachedBeamState:
                                                     _ptr(self.flags[nxt]), _ptr(self.preds[nxt]), _ptr(self.n_fin[nxt]), _ptr(j.k_src),
                                                     _ptr(j.jsrc[nxt]), stream), 'otr_beam_prune_cached_joint')
             return
-        L.check(lib.otr_beam_topk(_ptr(logits), ld, _ptr(lm_logits), ld_lm, float(rec.lm_weight or 0.0), self.R, V, beam,
-                                  _ptr(self.k_score), _ptr(self.k_idx), stream), 'otr_beam_topk')
+        if self.cand is not None:                         # the n-gram: pre-beam + addend + select in otr_beam_topk's place, one chain
+            ops.joint_prebeam(logits, lm_logits, 1.0, float(rec.lm_weight or 0.0), rec.ngram_beam, V, *self.cand)
+            ops.ngram_score_candidates(self.ngram, self.preds[cur], self.cand[1], self.cand[0], rec.alpha, rec.beta, EOS, pos=self.pos[cur],
+                                       flags=self.flags[cur], beam=beam, cand_out=self.cand[0], k_score=self.k_score, k_idx=self.k_idx)
+        else:
+            L.check(lib.otr_beam_topk(_ptr(logits), ld, _ptr(lm_logits), ld_lm, float(rec.lm_weight or 0.0), self.R, V, beam,
+                                      _ptr(self.k_score), _ptr(self.k_idx), stream), 'otr_beam_topk')
         L.check(lib.otr_beam_prune_cached(_ptr(self.k_score), _ptr(self.k_idx), _ptr(self.scores[cur]),
                                           _ptr(self.flags[cur]), _ptr(self.preds[cur]), self.ldp, self.b, beam, EOS,
                                           _ptr(self.pos[cur]), _ptr(self.pos[nxt]), _ptr(self.anc[cur]),
@@ -1103,11 +1161,16 @@ def frames_to_seconds(frame, subsample=4, frame_shift_ms=10.0):
 def build_recognizer(model_type, model, lm, args, idx2unit):
     """recognize/__init__.py:5-16."""
     if model_type == 'speech2text':
+        ngram_lm = getattr(args, 'ngram_lm', None)
+        if isinstance(ngram_lm, str):
+            ngram_lm = NGramLM.from_arpa(ngram_lm, idx2unit)
+        kw = {k: getattr(args, k) for k in ('alpha', 'beta') if hasattr(args, k)}
         return SpeechToTextRecognizer(model=model, lm=lm, lm_weight=args.lm_weight, ctc_weight=args.ctc_weight,
                                       beam_width=args.beam_width, nbest=args.nbest, max_len=args.max_len,
                                       idx2unit=idx2unit, penalty=args.penalty, lamda=args.lamda, ngpu=args.ngpu,
                                       joint_ctc=getattr(args, 'joint_ctc', False), ctc_beam=getattr(args, 'ctc_beam', None),
-                                      rescore=getattr(args, 'rescore', False))
+                                      rescore=getattr(args, 'rescore', False), ngram_lm=ngram_lm,
+                                      ngram_beam=getattr(args, 'ngram_beam', None), **kw)
     if model_type == 'ctc':
         ngram_lm = args.ngram_lm
         if isinstance(ngram_lm, str):                                           # the reference passes the path on to ctcdecode
