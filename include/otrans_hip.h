@@ -295,7 +295,13 @@ int32_t otr_colsum_grouped(const otr_colsum_item_t* items, int32_t n, void* stre
  *      (module/attention.py:23-46 compute_context, :76-82 self, :137-143 cross).
  * q/k/v/o are [B, T, H*dk] slices addressed by (batch stride, time stride) in elements; head h
  * occupies columns [h*dk, (h+1)*dk).  key_mask: uint8 [B, Tk] (1 = valid) or NULL; causal != 0
- * additionally masks key > query (decoder/utils.py:7-11).  lse: f32 [B,H,Tq] (saved for bwd). */
+ * additionally masks key > query (decoder/utils.py:7-11).  lse: f32 [B,H,Tq] (saved for bwd), the natural-log sum of exp(S) over
+ * the keys a query may see.
+ * A query row that may see NO key (every key of its utterance masked; torch's softmax gives NaN there): o = 0 and lse = -inf, and in
+ * the backward pass the row contributes nothing -- its dq row is 0, delta is 0, and it adds nothing to dk, dv or dbias.  A masked key
+ * gets dk = dv = 0 and every masked in-range (query, key) pair dbias = 0, written, not skipped.  Operands need no alignment: base
+ * pointers off a 16-byte boundary or strides that are no multiple of 16 bytes take scalar loads and stores.  Batch strides may exceed
+ * T * (time stride); nothing outside the [B, T, H*dk] elements of o / dq / dk / dv is written. */
 typedef struct {
   int32_t B, H, Tq, Tk, dk;
   int32_t dtype;                /* element type of q,k,v,o and their grads; also the MFMA type */
@@ -305,7 +311,11 @@ typedef struct {
 } otr_attn_desc_t;
 int32_t otr_attention_fwd(const otr_attn_desc_t* d, const void* q, const void* k, const void* v,
                           const uint8_t* key_mask, void* o, float* lse, void* stream);
-/* do_/dq/dk/dv use the strides of o/q/k/v.  delta: f32 [B,H,Tq] workspace. */
+/* do_/dq/dk/dv use the strides of o/q/k/v.  delta: f32 [B,H,Tq] workspace: the streamed kernels leave rowsum(dO * O) in all of it.
+ * The whole-utterance kernels keep that sum in LDS and need not write the workspace; a caller must not read it after a launch they
+ * may have served: 16-bit operands on 16-byte boundaries, Tq == Tk <= 512 and no causal mask, at head dim 64 without a bias
+ * (csrc/encattn.hip; otr_debug_set(21, 0) turns it off) and, in otr_attention_bias_bwd, at head dim 96 with rel_shift and bias rows long
+ * enough for 16-byte loads (csrc/encattn96.hip; otr_debug_set(33, 0)).  Every other launch writes all of delta. */
 int32_t otr_attention_bwd(const otr_attn_desc_t* d, const void* q, const void* k, const void* v,
                           const uint8_t* key_mask, const void* o, const void* do_, const float* lse,
                           float* delta, void* dq, void* dk, void* dv, void* stream);
