@@ -38,9 +38,9 @@ extern "C" {
 /* ABI version of THIS header: bumped whenever a signature, a descriptor struct or the meaning of an argument changes (600: round 6;
  * 300 was rounds 3-5, during which otr_optimizer_step, otr_ln_desc_t, otr_wgrad_item_t and otr_beam_prune_cached changed without a
  * bump; 602: the rescoring entries, additions only; 603: otr_ctc_align, additions only; 604: otr_ngram_lookup and otr_ctc_beam_search_lm, additions only; 605:
- * otr_edit_distance, additions only; 606: otr_ngram_score_cands, otr_ngram_score_seqs and otr_rescore_select_add, additions only).  A binding compares otr_version() with the OTR_ABI_VERSION it was written against BEFORE its first call and refuses a
+ * otr_edit_distance, additions only; 606: otr_ngram_score_cands, otr_ngram_score_seqs and otr_rescore_select_add, additions only; 607: otr_ngram_count, otr_ngram_stats and otr_ngram_estimate, additions only).  A binding compares otr_version() with the OTR_ABI_VERSION it was written against BEFORE its first call and refuses a
  * library that answers anything else: descriptors are passed by pointer and read at the library's idea of their size. */
-#define OTR_ABI_VERSION 606
+#define OTR_ABI_VERSION 607
 int32_t otr_version(void);
 /* OTR_BF16 or OTR_F16: the 16-bit type this library was built for */
 int32_t otr_half_type(void);
@@ -907,6 +907,50 @@ int32_t otr_rescore_select_add(const int64_t* tokens, const int32_t* out_len, co
                                const float* att_score, const float* lm_score, const float* add_score, int32_t B, int32_t W, int32_t T,
                                int32_t nbest, float ctc_weight, float lm_weight, float penalty, float lamda, float* total, int32_t* perm,
                                int64_t* nbest_tokens, int32_t* nbest_len, float* nbest_score, void* stream);
+
+/* ---- n-gram LM estimation (NGramLM.train: interpolated modified Kneser-Ney from unit-id sentences, the ARPA file the entries above
+ *      start from), csrc/ngramtrain.hip.  Integers, f32 and f64 only: the same code in every build.  Order N in [1, 4], V in [1, 8192].
+ * Corpus: tokens int64 [n_sent, ld] (row b at tokens + b * ld), lengths int32 [n_sent] with 0 <= lengths[b] <= max_len <= ld; columns
+ *   at or past lengths[b] are never read.  Every id inside a length lies in [1, V) and differs from eos (1 <= eos < V).  Sentence b is
+ *   read as x = <s> w_1 .. w_n </s> with <s> = V and </s> = eos.
+ * Count table: `capacity` entries of 32 bytes (capacity a power of two >= 2, the base 8-byte aligned), all zero before otr_ngram_count:
+ *   { u64 key, u32 raw, u32 cont, u32 sum, u32 n1, u32 n2, u32 n3p }.  key: the gram's ids, 16 bits each, newest id in bits 0-15 (the
+ *   `lo` word of the scoring table's key; ids are >= 1, so key != 0, 0 marks an empty entry, and the gram's order m is the number of
+ *   non-zero fields).  Open addressing with linear probing from ng_hash(key, m << 16) & (capacity - 1): the scoring table's hash of the
+ *   same gram.  raw = c(g); cont = the number of distinct (m+1)-grams of the corpus that end in g; sum / n1 / n2 / n3p = the context
+ *   statistics of g below.  Counters are 32-bit: a corpus holds fewer than 2^32 tokens.
+ * Estimator.  Raw counts: for every end position i of x and every m in 1 .. min(N, i+1) the m-gram x[i-m+1 .. i] is counted.
+ *   Adjusted count a(g) = c(g) if |g| == N or g starts with <s>, else cont(g) (Kneser-Ney continuation counts, KenLM's <s> rule).  The
+ *   unigram <s> takes part in no statistic.  Context h (the empty one included), over all grams h.w of order |h|+1: sum(h) = the sum
+ *   of a, n1 / n2 / n3p(h) = the number of them with a = 1, a = 2, a >= 3.  nn[m][k], k = 1 .. 4 = the number of order-m grams with
+ *   a = k.  Discounts of order m (Chen & Goodman): Y = nn1 / (nn1 + 2 nn2), D_k = k - (k+1) Y nn_{k+1} / nn_k for k = 1, 2, 3; the
+ *   order falls back to (0.5, 1, 1.5) if one of nn1 .. nn4 is 0 or a D_k leaves [0, k].  (The discounts are formed by the caller from
+ *   otr_ngram_stats' integers and handed to otr_ngram_estimate.)  With U the predictable units (|U| = n_units; </s> is one of them):
+ *     p_m(w | h) = (a(hw) - D_m[min(a, 3)]) / sum(h) + gamma(h) p_{m-1}(w | h'),   h' = h without its oldest id,
+ *     gamma(h)   = (D_m[1] n1(h) + D_m[2] n2(h) + D_m[3] n3p(h)) / sum(h),          p_0 = 1 / n_units,
+ *   in f64 from the integers.  Entry of a gram g: log-prob = ln p (the unigram <s>: -99 ln 10), backoff = ln gamma(g) with the
+ *   discounts of order |g|+1 if sum(g) > 0, else 0; both rounded to f32 once.
+ * err int32 [1] on the device, zero before the first pass; the passes OR bits into it and leave the rest to the caller, who reads it
+ *   after a pass: 1 = the count table is full (a probe loop ran `capacity` entries), 2 = an id inside a length is outside [1, V) or
+ *   equals eos, 4 = a length outside [0, max_len], 8 = a gram's context or suffix is missing from the table (a table that
+ *   otr_ngram_count did not fill).  A sentence with a bad length and an end position whose window holds a bad id count nothing.
+ * No pass takes a lock or waits for another thread: an insertion is one 64-bit compare-and-swap on the key followed by integer
+ *   atomic adds, and every probe loop is bounded by `capacity`.  Every statistic is an integer sum, so the results do not depend on the
+ *   order of threads, entries or sentences.
+ * otr_ngram_count: one thread per (sentence, end position of x).  Inserts the m = 1 .. N grams in that order and adds 1 to raw; the
+ *   thread whose compare-and-swap created an (m+1)-gram adds 1 to cont of its m-gram suffix (which it inserted one step earlier).
+ *   n_sent = 0: nothing to do.
+ * otr_ngram_stats: one thread per entry; fills sum / n1 / n2 / n3p of every context and glob u64 [20] on the device (zero before):
+ *   glob[0..3] = sum, n1, n2, n3p of the empty context, glob[4 + 4 (m-1) + (k-1)] = nn[m][k].  The additions to glob are summed per
+ *   workgroup first.
+ * otr_ngram_estimate: one launch per order m = 1 .. N, one thread per entry; order m reads prob of its suffix.  discounts f64 [N, 3]
+ *   on the HOST (row m-1 = D_m[1..3], each in [0, k]); glob as otr_ngram_stats left it.  Outputs per entry of the count table:
+ *   prob f64 = p, logp f32, backoff f32 (entries with key == 0 are not written). */
+int32_t otr_ngram_count(const int64_t* tokens, int64_t ld, const int32_t* lengths, int64_t n_sent, int32_t max_len, int32_t order,
+                        int32_t V, int32_t eos, void* table, int64_t capacity, int32_t* err, void* stream);
+int32_t otr_ngram_stats(void* table, int64_t capacity, int32_t order, int32_t V, uint64_t* glob, int32_t* err, void* stream);
+int32_t otr_ngram_estimate(const void* table, int64_t capacity, int32_t order, int32_t V, int32_t n_units, const double* discounts,
+                           const uint64_t* glob, double* prob, float* logp, float* backoff, int32_t* err, void* stream);
 
 /* ---- transposed copies of many matrices in ONE launch (the W^T bf16 shadows that turn dx = dy.W into a
  *      forward-type GEMM; refreshed after every optimizer step).  table: DEVICE int64 [n_mats,4] rows of

@@ -14,7 +14,7 @@ LIB_PATHS = {'bf16': os.path.join(_LIB_DIR, 'libotrans_hip.so'), 'fp16': os.path
 LIB_PATH = LIB_PATHS['bf16']
 
 OTR_F32, OTR_BF16, OTR_F16 = 0, 1, 2
-OTR_ABI_VERSION = 606           # include/otrans_hip.h: the header this binding's structures and SIGNATURES were written against
+OTR_ABI_VERSION = 607           # include/otrans_hip.h: the header this binding's structures and SIGNATURES were written against
 OTR_OPT_STATE_FLOATS = 528      # include/otrans_hip.h: floats of otr_optimizer_step's device state block
 ACT_NONE, ACT_RELU = 0, 1
 
@@ -222,6 +222,9 @@ SIGNATURES = {
     'otr_ngram_score_cands': [_P, _I64, _I32, _I32, _I32, _P, _I64, _I32, _P, _P, _P, _P, _I64, _I32, _F32, _F32, _F32, _I32, _P, _P, _I32,
                               _P, _P, _P],
     'otr_ngram_score_seqs': [_P, _I64, _I32, _I32, _I32, _P, _P, _I64, _I32, _F32, _F32, _F32, _I32, _P, _P, _P],
+    'otr_ngram_count': [_P, _I64, _P, _I64, _I32, _I32, _I32, _I32, _P, _I64, _P, _P],
+    'otr_ngram_stats': [_P, _I64, _I32, _I32, _P, _P, _P],
+    'otr_ngram_estimate': [_P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],
     'otr_decode_embed': [_P, _I64, _P, _P, _P, _P, _I64, _I32, _I32, _F32, _P],
     'otr_decode_lookup': [_P, _I64, _P, _P, _P, _P, _I64, _I32, _I32, _P],
     'otr_lstm_cell': [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P],

@@ -4,7 +4,11 @@
 NGramLM.from_arpa reads an ARPA text file (plain or .gz) into a hash table laid out for the device: include/otrans_hip.h states the
 entry layout and the scoring rule, csrc/ngram.h is the device side of this file.  The table is built with numpy; lookup_host walks
 the very table the kernels probe, lookup does the same on the device (otr_ngram_lookup), and ops.ctc_prefix_beam_search_lm fuses
-the model into the search."""
+the model into the search.
+
+NGramLM.train estimates such a model from unit-id sentences on the device (csrc/ngramtrain.hip: interpolated modified Kneser-Ney,
+the estimator include/otrans_hip.h states) and NGramLM.to_arpa writes any model back as ARPA text, so the file from_arpa starts
+from can be produced here."""
 import gzip
 import io
 import math
@@ -14,6 +18,8 @@ import numpy as np
 from .data import EOS
 
 MAX_ORDER = 5
+TRAIN_MAX_ORDER = 4               # the estimator's key is the one `lo` word: four 16-bit ids (NT_MAXN of csrc/ngramtrain.hip)
+FALLBACK_DISCOUNTS = (0.5, 1.0, 1.5)
 MAX_VOCAB = 8192                  # ids 0 .. V (V = <s>) in 16 bits: CB_MAXV of csrc/ctcbeam.hip
 OOV_SCORE = -1000.0               # ctcdecode's OOV_SCORE
 _KENLM_MAGIC = b'mmap lm http://kheafield.com/code'
@@ -53,6 +59,129 @@ def min_capacity(n):
     while cap < 2 * n:
         cap *= 2
     return cap
+
+
+def unpack_keys(lo, hi=None):
+    """the inverse of pack_keys: (ids int64 [n, 5] left aligned, oldest id first, lens [n]); without hi the order of a key is the
+    number of its non-zero 16-bit fields (the count table of the estimator, whose ids are >= 1)"""
+    lo = np.asarray(lo, _U)
+    f = np.stack([(lo >> _U(16 * j)) & _U(0xffff) for j in range(4)], 1).astype(np.int64)
+    if hi is None:
+        f = np.concatenate([f, np.zeros((len(lo), 1), np.int64)], 1)
+        lens = (f != 0).sum(1)
+    else:
+        hi = np.asarray(hi, _U)
+        f = np.concatenate([f, (hi & _U(0xffff)).astype(np.int64)[:, None]], 1)
+        lens = (hi >> _U(16)).astype(np.int64)
+    ids = np.zeros((len(lo), MAX_ORDER), np.int64)
+    for j in range(MAX_ORDER):                             # column m-1-j <- position j of the key
+        has = lens > j
+        ids[np.flatnonzero(has), (lens - 1 - j)[has]] = f[has, j]
+    return ids, lens
+
+
+def count_bound(lengths, order):
+    """sum_b sum_i min(order, i + 1) over the len_b + 2 positions of <s> w_1 .. w_n </s>: no corpus holds more distinct n-grams"""
+    P = np.asarray(lengths, np.int64) + 2
+    return int(np.where(P >= order, order * P - order * (order - 1) // 2, P * (P + 1) // 2).sum())
+
+
+def kn_discounts(nn):
+    """modified Kneser-Ney discounts (Chen & Goodman) of one order from its count-of-counts nn[0..3] = n1 .. n4: (D1, D2, D3), or
+    None where the order falls back (one of n1 .. n4 is 0, or a D_k leaves [0, k])"""
+    n1, n2, n3, n4 = (int(v) for v in nn)
+    if min(n1, n2, n3, n4) <= 0:
+        return None
+    Y = n1 / (n1 + 2.0 * n2)
+    d = (1.0 - 2.0 * Y * n2 / n1, 2.0 - 3.0 * Y * n3 / n2, 3.0 - 4.0 * Y * n4 / n3)
+    return d if all(0.0 <= d[k] <= k + 1 for k in range(3)) else None
+
+
+def _train_corpus(tokens, lengths, V, eos, device):
+    """-> (tokens int64 [n, L] on the device, lengths int32 [n] on the device, lengths on the host).  Lists are checked on the host,
+    padded and uploaded once; a tensor is taken as it is (its ids are checked by the count kernel)."""
+    import torch
+    from ._lib import OtransHipError
+    if torch.is_tensor(tokens):
+        if tokens.dim() != 2 or tokens.dtype != torch.int64:
+            raise ValueError('NGramLM.train: tokens must be an int64 [n, L] tensor or a list of id lists, got %s %s'
+                             % (tokens.dtype, tuple(tokens.shape)))
+        n, T = tokens.shape
+        if lengths is None:
+            len_h = np.full(n, T, np.int64)
+        else:
+            len_h = (lengths.detach().cpu().numpy() if torch.is_tensor(lengths) else np.asarray(lengths)).astype(np.int64).reshape(-1)
+        if len(len_h) != n:
+            raise ValueError('NGramLM.train: %d lengths for %d sentences' % (len(len_h), n))
+    else:
+        sents = [np.asarray(s, np.int64).reshape(-1) for s in tokens]
+        n = len(sents)
+        len_h = np.array([len(s) for s in sents], np.int64)
+        T = int(len_h.max()) if n else 0
+        flat = np.concatenate(sents) if n else np.zeros(0, np.int64)
+        if len(flat) and (flat.min() < 1 or flat.max() >= V or (flat == eos).any()):
+            raise ValueError('NGramLM.train: ids inside a sentence must be in [1, V = %d) and differ from the </s> unit %d' % (V, eos))
+        pad = np.zeros((n, T), np.int64)
+        pad[np.arange(T)[None, :] < len_h[:, None]] = flat
+        tokens = torch.from_numpy(pad)
+    if n == 0:
+        raise ValueError('NGramLM.train: an empty corpus')
+    if len_h.min() < 0 or len_h.max() > T:
+        raise ValueError('NGramLM.train: lengths must be in [0, L = %d]' % T)
+    if not tokens.is_cuda and not torch.cuda.is_available():
+        raise OtransHipError('NGramLM.train counts on the device and no GPU is available; there is no CPU path')
+    dev = tokens.device if tokens.is_cuda else torch.device(device)
+    return tokens.to(dev), torch.from_numpy(len_h.astype(np.int32)).to(dev), len_h
+
+
+def _train_check(err, what):
+    """read the estimator's error word (one synchronisation) and raise what it says"""
+    from . import ops
+    from ._lib import OtransHipError
+    e = int(err.item())
+    if e:
+        msg = 'NGramLM.train: %s: %s' % (what, '; '.join(t for b, t in ops.NGRAM_TRAIN_ERRORS.items() if e & b))
+        raise OtransHipError(msg) if e & 9 else ValueError(msg)
+
+
+def _train_args(order, V, eos, table_capacity):
+    if not 1 <= order <= TRAIN_MAX_ORDER:
+        raise ValueError('NGramLM.train: order %d, orders 1 .. %d are estimated (from_arpa reads up to %d)'
+                         % (order, TRAIN_MAX_ORDER, MAX_ORDER))
+    if not 2 <= V <= MAX_VOCAB:
+        raise ValueError('NGramLM.train: %d units, 2 .. %d fit' % (V, MAX_VOCAB))
+    if not 1 <= eos < V:
+        raise ValueError('NGramLM.train: the </s> unit %d must be in [1, V = %d)' % (eos, V))
+    if table_capacity is not None and (table_capacity < 2 or table_capacity & (table_capacity - 1) or table_capacity > 1 << 31):
+        raise ValueError('NGramLM.train: table_capacity %d must be a power of two in [2, 2^31]' % table_capacity)
+
+
+def _sorted_grams(table):
+    """the filled entries of a device count table: (index into the table, int64 on the device, in (order, key) order; keys uint64 on
+    the host in that order)"""
+    import torch
+    idx = torch.nonzero(table[:, 0]).reshape(-1)
+    keys = table[idx, 0].cpu().numpy().view(_U)
+    order = (np.stack([(keys >> _U(16 * j)) & _U(0xffff) for j in range(4)], 1) != 0).sum(1)
+    perm = np.lexsort((keys, order))
+    return idx[torch.from_numpy(perm).to(idx.device)], keys[perm]
+
+
+def count_ngrams(tokens, lengths=None, *, order=3, vocab_size, eos_unit=EOS, table_capacity=None, device='cuda'):
+    """The raw and continuation counts NGramLM.train estimates from (otr_ngram_count alone), for inspection and tests: every m-gram,
+    m = 1 .. order, of <s> w_1 .. w_n </s> per sentence.  Returns (ids int64 [n, order] left aligned, oldest first, lens [n],
+    raw [n], cont [n]: the number of distinct (m+1)-grams that end in the gram) in (order, key) order."""
+    from . import ops
+    order, V, eos = int(order), int(vocab_size), int(eos_unit)
+    _train_args(order, V, eos, table_capacity)
+    tok, ln, len_h = _train_corpus(tokens, lengths, V, eos, device)
+    cap = min_capacity(count_bound(len_h, order)) if table_capacity is None else int(table_capacity)
+    table, err = ops.ngram_train_count(tok, ln, order, V, eos, cap)
+    _train_check(err, 'counting')
+    idx, keys = _sorted_grams(table)
+    cnt = table[idx, 1].cpu().numpy().view(_U)
+    ids, lens = unpack_keys(keys)
+    return ids[:, :order], lens, (cnt & _U(0xffffffff)).astype(np.int64), (cnt >> _U(32)).astype(np.int64)
 
 
 class NGramLM:
@@ -202,6 +331,116 @@ class NGramLM:
             if f.peek(64)[:len(_KENLM_MAGIC)] == _KENLM_MAGIC:
                 raise ValueError('NGramLM.from_arpa: this is a gzipped KenLM binary file; only ARPA text is read')
         return io.TextIOWrapper(f, encoding='utf-8')
+
+    # ------------------------------------------------------------------ estimation
+    @classmethod
+    def train(cls, tokens, lengths=None, *, order=3, vocab_size, units=None, eos_unit=EOS, discounts=None, oov_score=OOV_SCORE,
+              capacity=None, table_capacity=None, device='cuda'):
+        """Estimate an interpolated modified Kneser-Ney model on the device (csrc/ngramtrain.hip; include/otrans_hip.h states the
+        estimator).  tokens: an int64 [n, L] tensor (on a GPU or not, rows strided freely, anything beyond `lengths`) or a list of id
+        lists; every id inside a sentence lies in [1, vocab_size) and differs from eos_unit.  A sentence is read as <s> w </s> with
+        <s> = vocab_size, </s> = eos_unit; order 1 .. 4.  units: the predictable ids (default: all of [1, vocab_size)); each has a
+        unigram afterwards, so none scores oov_score.  discounts [order][3] overrides the computed ones.  table_capacity: the count
+        table's size (a power of two; default: load <= 0.5 at the upper bound of the number of n-grams); capacity: the scoring
+        table's, as in the constructor.  stats gains sentences, tokens, ngrams (per order), discounts and fallback_orders (the orders
+        on (0.5, 1, 1.5)).  There is no CPU path."""
+        from . import ops
+        order, V, eos = int(order), int(vocab_size), int(eos_unit)
+        _train_args(order, V, eos, table_capacity)
+        U = np.arange(1, V) if units is None else np.unique(np.asarray(list(units), np.int64))
+        if len(U) == 0 or U.min() < 1 or U.max() >= V or eos not in U:
+            raise ValueError('NGramLM.train: units must be ids in [1, V = %d) and hold the </s> unit %d' % (V, eos))
+        if discounts is not None:
+            discounts = [[float(v) for v in row] for row in discounts]
+            if len(discounts) != order or any(len(r) != 3 or not all(0.0 <= r[k] <= k + 1 for k in range(3)) for r in discounts):
+                raise ValueError('NGramLM.train: discounts must be [order = %d][3] with D_k in [0, k]' % order)
+        tok, ln, len_h = _train_corpus(tokens, lengths, V, eos, device)
+        cap = min_capacity(count_bound(len_h, order)) if table_capacity is None else int(table_capacity)
+        table, err = ops.ngram_train_count(tok, ln, order, V, eos, cap)
+        _train_check(err, 'counting')
+        glob = ops.ngram_train_stats(table, order, V, err)
+        g = glob.cpu().numpy()
+        _train_check(err, 'statistics')
+        fallback = []
+        if discounts is None:
+            discounts = [kn_discounts(g[4 + 4 * m:8 + 4 * m]) for m in range(order)]
+            fallback = [m + 1 for m in range(order) if discounts[m] is None]
+            discounts = [list(d or FALLBACK_DISCOUNTS) for d in discounts]
+        logp_d, bo_d = ops.ngram_train_estimate(table, order, V, len(U), discounts, glob, err)
+        _train_check(err, 'probabilities')
+        idx, keys = _sorted_grams(table)
+        ids, lens = unpack_keys(keys)
+        logp, backoff = logp_d[idx].cpu().numpy(), bo_d[idx].cpu().numpy()
+        seen = ids[lens == 1, 0]
+        if not np.isin(seen[seen != V], U).all():
+            raise ValueError('NGramLM.train: the corpus holds ids that `units` leaves out')
+        new = np.setdiff1d(U, seen)                          # units without a count: ln(gamma(empty) / |U|)
+        if len(new):
+            D1 = discounts[0]
+            gamma = (D1[0] * float(g[1]) + D1[1] * float(g[2]) + D1[2] * float(g[3])) / float(g[0])
+            with np.errstate(divide='ignore'):
+                lp_new = np.float32(np.log(np.float64(gamma / len(U))))
+            keys = np.concatenate([keys, new.astype(_U)])
+            ids = np.concatenate([ids, np.pad(new[:, None], ((0, 0), (0, MAX_ORDER - 1)))])
+            lens = np.concatenate([lens, np.ones(len(new), np.int64)])
+            logp = np.concatenate([logp, np.full(len(new), lp_new, np.float32)])
+            backoff = np.concatenate([backoff, np.zeros(len(new), np.float32)])
+            perm = np.lexsort((keys, lens))
+            ids, lens, logp, backoff = ids[perm], lens[perm], logp[perm], backoff[perm]
+        stats = {'order': order, 'ngrams': [int((lens == m).sum()) for m in range(1, order + 1)], 'sentences': len(len_h),
+                 'tokens': int(len_h.sum()), 'discounts': [tuple(d) for d in discounts], 'fallback_orders': fallback,
+                 'count_capacity': cap, 'count_load': float(len(idx)) / cap}
+        return cls(order, V, ids[:, :order], lens, logp, backoff, oov_score=oov_score, capacity=capacity, stats=stats)
+
+    def entries(self):
+        """the stored n-grams decoded from the table: (ids int64 [n, 5] left aligned, oldest first, lens, logp f32, backoff f32),
+        sorted by order, then by key"""
+        t = self.table[self.table[:, 1] != 0]
+        t = t[np.lexsort((t[:, 0], t[:, 1]))]
+        ids, lens = unpack_keys(t[:, 0], t[:, 1])
+        return (ids, lens, (t[:, 2] & _U(0xffffffff)).astype(np.uint32).view(np.float32),
+                (t[:, 2] >> _U(32)).astype(np.uint32).view(np.float32))
+
+    def to_arpa(self, path_or_file, idx2unit, eos_unit=EOS):
+        """Write the model as ARPA text: to a path (gzip if it ends in .gz) or an open text file.  Works for any NGramLM, one read by
+        from_arpa included: the n-grams are decoded from the table.  Id V is written <s>, eos_unit </s>, every other id as
+        idx2unit[id].  log10 values carry 17 digits, so from_arpa of the file gives back the same f32 bits (the same table at the same
+        capacity); the unigram <s> at ARPA's -99 is written as -99."""
+        V = self.vocab_size
+        if max(idx2unit) + 1 != V:
+            raise ValueError('NGramLM.to_arpa: idx2unit names ids up to %d, the model has V = %d' % (max(idx2unit), V))
+        ids, lens, logp, backoff = self.entries()
+        word = {int(i): str(u) for i, u in idx2unit.items()}
+        word[V] = '<s>'
+        if eos_unit is not None:
+            word[int(eos_unit)] = '</s>'
+        missing = sorted(set(int(v) for r, m in zip(ids, lens) for v in r[:m]) - set(word))
+        if missing:
+            raise ValueError('NGramLM.to_arpa: idx2unit has no unit for the ids %s' % missing[:8])
+        ln10 = math.log(10.0)
+        minus99 = np.float32(-99.0 * ln10)
+        if isinstance(path_or_file, (str, bytes)) or hasattr(path_or_file, '__fspath__'):
+            name = path_or_file.decode() if isinstance(path_or_file, bytes) else str(path_or_file)
+            f = gzip.open(name, 'wt', encoding='utf-8') if name.endswith('.gz') else open(name, 'w', encoding='utf-8')
+            own = True
+        else:
+            f, own = path_or_file, False
+        try:
+            f.write('\n\\data\\\n')
+            for m in range(1, self.order + 1):
+                f.write('ngram %d=%d\n' % (m, int((lens == m).sum())))
+            for m in range(1, self.order + 1):
+                f.write('\n\\%d-grams:\n' % m)
+                for r in np.flatnonzero(lens == m):
+                    lp = '-99' if m == 1 and ids[r, 0] == V and logp[r] == minus99 else '%.17g' % (float(logp[r]) / ln10)
+                    line = lp + '\t' + ' '.join(word[int(v)] for v in ids[r, :m])
+                    if m < self.order or backoff[r] != 0:
+                        line += '\t%.17g' % (float(backoff[r]) / ln10)
+                    f.write(line + '\n')
+            f.write('\n\\end\\\n')
+        finally:
+            if own:
+                f.close()
 
     # ------------------------------------------------------------------ scoring
     def context(self, prefix):

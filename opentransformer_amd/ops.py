@@ -3775,6 +3775,52 @@ def ngram_score_sequences(ngram, tokens, out_len, alpha=1.0, beta=0.0, eos=1, wi
     return (out, logp) if with_logp else out
 
 
+NGRAM_TRAIN_ERRORS = {1: 'the count table is full', 2: 'an id inside a sentence is outside [1, V) or is the </s> unit',
+                      4: 'a sentence length is outside [0, L]', 8: 'a context or a suffix is missing from the count table'}
+
+
+def ngram_train_count(tokens, lengths, order, V, eos, table_capacity):
+    """The count pass of the n-gram estimator (include/otrans_hip.h otr_ngram_count).  tokens int64 [n, L] on a GPU, rows strided
+    freely, lengths int32 [n]; nothing at or beyond a length is read.  Returns (table int64 [table_capacity, 4]: the count entries
+    { key, raw | cont << 32, sum | n1 << 32, n2 | n3p << 32 }, err int32 [1]: the error bits, to be read by the caller)."""
+    _cuda(tokens, lengths)
+    if tokens.dtype != torch.int64 or tokens.dim() != 2 or lengths.dtype != torch.int32 or lengths.shape != tokens.shape[:1]:
+        raise L.OtransHipError('ngram_train_count: tokens int64 [n, L] and lengths int32 [n] expected, got %s %s %s %s'
+                               % (tokens.dtype, tuple(tokens.shape), lengths.dtype, tuple(lengths.shape)))
+    n, T = tokens.shape
+    if T and tokens.stride(1) != 1:
+        tokens = tokens.contiguous()
+    dev = tokens.device
+    table = torch.zeros((int(table_capacity), 4), dtype=torch.int64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    L.check(L.load().otr_ngram_count(_p(tokens) if n and T else None, tokens.stride(0) if n > 1 and T else T, _p(lengths.contiguous()), n, T,
+                                     int(order), int(V), int(eos), _p(table), int(table_capacity), _p(err), _stream()), 'otr_ngram_count')
+    return table, err
+
+
+def ngram_train_stats(table, order, V, err):
+    """The statistics pass (otr_ngram_stats): fills the context statistics of `table` in place; returns glob int64 [20] on the device:
+    sum, n1, n2, n3p of the empty context, then the count-of-counts nn[m][k] at 4 + 4 (m-1) + (k-1)."""
+    _cuda(table, err)
+    glob = torch.zeros(20, dtype=torch.int64, device=table.device)
+    L.check(L.load().otr_ngram_stats(_p(table), table.shape[0], int(order), int(V), _p(glob), _p(err), _stream()), 'otr_ngram_stats')
+    return glob
+
+
+def ngram_train_estimate(table, order, V, n_units, discounts, glob, err):
+    """The probability passes (otr_ngram_estimate, one launch per order): discounts [order][3] host floats.  Returns (logp f32,
+    backoff f32) per count entry; the entries of empty slots are not written."""
+    _cuda(table, glob, err)
+    cap, dev = table.shape[0], table.device
+    prob = torch.empty(cap, dtype=torch.float64, device=dev)
+    logp = torch.empty(cap, dtype=torch.float32, device=dev)
+    backoff = torch.empty(cap, dtype=torch.float32, device=dev)
+    d = (C.c_double * (3 * int(order)))(*[float(v) for row in discounts for v in row])
+    L.check(L.load().otr_ngram_estimate(_p(table), cap, int(order), int(V), int(n_units), d, _p(glob), _p(prob), _p(logp), _p(backoff),
+                                        _p(err), _stream()), 'otr_ngram_estimate')
+    return logp, backoff
+
+
 CTC_ALIGN_MAX_TGT = 127
 
 
