@@ -38,9 +38,10 @@ extern "C" {
 /* ABI version of THIS header: bumped whenever a signature, a descriptor struct or the meaning of an argument changes (600: round 6;
  * 300 was rounds 3-5, during which otr_optimizer_step, otr_ln_desc_t, otr_wgrad_item_t and otr_beam_prune_cached changed without a
  * bump; 602: the rescoring entries, additions only; 603: otr_ctc_align, additions only; 604: otr_ngram_lookup and otr_ctc_beam_search_lm, additions only; 605:
- * otr_edit_distance, additions only; 606: otr_ngram_score_cands, otr_ngram_score_seqs and otr_rescore_select_add, additions only; 607: otr_ngram_count, otr_ngram_stats and otr_ngram_estimate, additions only).  A binding compares otr_version() with the OTR_ABI_VERSION it was written against BEFORE its first call and refuses a
+ * otr_edit_distance, additions only; 606: otr_ngram_score_cands, otr_ngram_score_seqs and otr_rescore_select_add, additions only; 607: otr_ngram_count, otr_ngram_stats and otr_ngram_estimate, additions only;
+ * 608: otr_mwer_workspace_floats and otr_mwer_loss, additions only).  A binding compares otr_version() with the OTR_ABI_VERSION it was written against BEFORE its first call and refuses a
  * library that answers anything else: descriptors are passed by pointer and read at the library's idea of their size. */
-#define OTR_ABI_VERSION 607
+#define OTR_ABI_VERSION 608
 int32_t otr_version(void);
 /* OTR_BF16 or OTR_F16: the 16-bit type this library was built for */
 int32_t otr_half_type(void);
@@ -951,6 +952,39 @@ int32_t otr_ngram_count(const int64_t* tokens, int64_t ld, const int32_t* length
 int32_t otr_ngram_stats(void* table, int64_t capacity, int32_t order, int32_t V, uint64_t* glob, int32_t* err, void* stream);
 int32_t otr_ngram_estimate(const void* table, int64_t capacity, int32_t order, int32_t V, int32_t n_units, const double* discounts,
                            const uint64_t* glob, double* prob, float* logp, float* backoff, int32_t* err, void* stream);
+
+/* ---- minimum word error rate (MWER) training: the N-best approximation of the expected number of errors (Prabhavalkar et al. 2018)
+ *      with its gradient into the decoder's logits, csrc/mwer.hip.  f32 in every build.  B utterances with N hypothesis slots each,
+ *      n_hyp = B * N, slot h = b * N + n.  The inputs are what otr_rescore_pack and otr_edit_distance produce:
+ *   logits f32, row (h, l) at logits + (h*max_len + l)*ld, ld >= V (the teacher-forced decoder output on otr_rescore_pack's ys_in);
+ *   ys_out int64 [n_hyp, ld_ys] (the tokens, EOS, then -1); n_rows int32 [n_hyp] (len + 1, or 0 for a dead slot; a value above max_len
+ *   counts as max_len); errors int32 [B, N] (otr_edit_distance's dist; < 0: invalid).
+ *   s_h = sum over l < n_rows[h] of x[h, l, ys_out[h, l]] - logsumexp(x[h, l, :V])     (otr_rescore_score's att_score)
+ *   Slot h is LIVE iff n_rows[h] > 0, errors[h] >= 0 and every target inside n_rows lies in [0, V); a target outside that range makes
+ *   the slot dead (nothing is read out of bounds).  Rows of a slot with n_rows[h] <= 0 or errors[h] < 0 are not read at all.
+ *   Per utterance: P_n = softmax over the live n of s (max-subtracted), E_b = sum_n P_n W_n with W = errors.
+ *   loss = (1 / B_live) sum_b E_b, B_live = the number of utterances with at least one live slot; B_live = 0: loss 0, gradient all zero.
+ *   c_h = P_n (W_n - E_b) / B_live   (sum_n P_n (W_n - E_b) is identically zero: the value is E_b, the centring appears in the gradient only)
+ *   dlogits[h, l, v] = g c_h (1[v == ys_out[h, l]] - softmax(x[h, l, :V])_v) for l < n_rows[h] on live slots, g = *grad_scale (a device
+ *   scalar; NULL: 1).  EVERY other element of dlogits [n_hyp * max_len, ld_dlogits] is written as zero -- rows at or past n_rows, dead
+ *   slots, columns V .. ld_dlogits - 1 -- so the launch needs no memset (a live slot whose g c_h is exactly 0 gets zeros unread).
+ * Outputs: loss f32 [1]; seq_logp f32 [n_hyp] = s_h, -inf where the slot is not live; post f32 [B, N] = P, 0 where not live; utt_err f32
+ *   [B] = E_b (0 without a live slot); dlogits (NULL: forward only, two launches).  workspace: at least
+ *   otr_mwer_workspace_floats(B, N, max_len) floats (the rows' logsumexps and g c_h); that entry runs on the host and answers -1 for a
+ *   shape otr_mwer_loss refuses.
+ * Launches (at most three): a row pass as otr_rescore_score's -- one workgroup per slot, one wave per row, the row read once into an
+ *   online max / sum; wave w adds rows w, w + 4, ... in order and thread 0 adds the four partials in order; one workgroup that forms P,
+ *   E_b, c_h and the loss over the B * N scalars in a fixed order; a gradient pass, one wave per row, that reads each live row once
+ *   more.  No floating-point atomics: the same bits on every run.  Loads and stores are 16 bytes wide where the base is 16-byte aligned
+ *   and the row stride a multiple of 4 floats (logits and dlogits judged separately), scalar otherwise.
+ * Refused before any launch (< 0, outputs untouched): a null pointer (grad_scale and dlogits may be NULL), N outside [1, 32], V outside
+ *   [1, 8192], ld < V, ld_dlogits < V (with dlogits), ld_ys < max_len, max_len < 1, B < 0, B * N * max_len >= 2^30, a NULL or too small
+ *   workspace.  B = 0 returns 0 without a launch.  Caller-owned buffers, no allocation, memset or host synchronisation: capturable. */
+int64_t otr_mwer_workspace_floats(int32_t B, int32_t N, int32_t max_len);
+int32_t otr_mwer_loss(const float* logits, int64_t ld, const int64_t* ys_out, int64_t ld_ys, const int32_t* n_rows, const int32_t* errors,
+                      int32_t B, int32_t N, int32_t max_len, int32_t V, const float* grad_scale, float* loss, float* seq_logp,
+                      float* post, float* utt_err, float* dlogits, int64_t ld_dlogits, float* workspace, int64_t workspace_floats,
+                      void* stream);
 
 /* ---- transposed copies of many matrices in ONE launch (the W^T bf16 shadows that turn dx = dy.W into a
  *      forward-type GEMM; refreshed after every optimizer step).  table: DEVICE int64 [n_mats,4] rows of

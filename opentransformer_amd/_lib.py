@@ -14,7 +14,7 @@ LIB_PATHS = {'bf16': os.path.join(_LIB_DIR, 'libotrans_hip.so'), 'fp16': os.path
 LIB_PATH = LIB_PATHS['bf16']
 
 OTR_F32, OTR_BF16, OTR_F16 = 0, 1, 2
-OTR_ABI_VERSION = 607           # include/otrans_hip.h: the header this binding's structures and SIGNATURES were written against
+OTR_ABI_VERSION = 608           # include/otrans_hip.h: the header this binding's structures and SIGNATURES were written against
 OTR_OPT_STATE_FLOATS = 528      # include/otrans_hip.h: floats of otr_optimizer_step's device state block
 ACT_NONE, ACT_RELU = 0, 1
 
@@ -225,6 +225,8 @@ SIGNATURES = {
     'otr_ngram_count': [_P, _I64, _P, _I64, _I32, _I32, _I32, _I32, _P, _I64, _P, _P],
     'otr_ngram_stats': [_P, _I64, _I32, _I32, _P, _P, _P],
     'otr_ngram_estimate': [_P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],
+    'otr_mwer_workspace_floats': [_I32, _I32, _I32],
+    'otr_mwer_loss': [_P, _I64, _P, _I64, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P],
     'otr_decode_embed': [_P, _I64, _P, _P, _P, _P, _I64, _I32, _I32, _F32, _P],
     'otr_decode_lookup': [_P, _I64, _P, _P, _P, _P, _I64, _I32, _I32, _P],
     'otr_lstm_cell': [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P],
@@ -262,7 +264,7 @@ _RESTYPE = {'otr_last_error_string': C.c_char_p, 'otr_dec_ffn_hsave_bytes': C.c_
             'otr_ffn_split_padded_rows': C.c_int64, 'otr_add_layernorm_bwd_partial_rows': C.c_int64,
             'otr_ln_bwd_proj_partial_rows': C.c_int64, 'otr_dwconv_bwd_partial_rows': C.c_int64, 'otr_dwconv_fwd_partial_rows': C.c_int64,
             'otr_conv2_wide_scratch_bytes': C.c_int64, 'otr_add2_colsum_partial_rows': C.c_int64,
-            'otr_ctc_beam_workspace_bytes': C.c_int64, 'otr_ctc_align_workspace_bytes': C.c_int64}
+            'otr_ctc_beam_workspace_bytes': C.c_int64, 'otr_ctc_align_workspace_bytes': C.c_int64, 'otr_mwer_workspace_floats': C.c_int64}
 
 _libs = {}
 _kind = 'bf16'

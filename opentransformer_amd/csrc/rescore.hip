@@ -10,8 +10,7 @@
 //  * rescore_select:  one workgroup per utterance: total = (1 - lambda) att + lambda ctc + mu lm (+ add), the length penalty, the rank of each
 //                     of the W <= 32 entries by counting (ties -> lower CTC rank, -inf last in CTC order), then the n-best rows leave.
 #include "common.h"
-
-#define NEG_INF (-__builtin_huge_valf())
+#include "rowlse.h"      // NEG_INF, rs_row: one wave's online logsumexp of a row (shared with mwer.hip)
 
 constexpr int RS_MAXW = 32;       // the search's beam limit
 constexpr int RS_MAXV = 8192;     // the search's vocabulary limit
@@ -55,25 +54,6 @@ extern "C" int32_t otr_rescore_pack(const int64_t* tokens, const int32_t* out_le
 }
 
 // ---------------------------------------------------------------- score
-struct RsRun { float m, s; };      // running maximum and sum of exp(x - m) of what a lane has seen (m = -inf: nothing finite yet, s = 0)
-
-__device__ __forceinline__ void rs_take(RsRun& r, float x) {
-  if (x > r.m) {                                      // new maximum: rescale (exp(-inf - x) = 0 the first time)
-    r.s = r.s * __expf(r.m - x) + 1.f;
-    r.m = x;
-  } else if (x > NEG_INF) {
-    r.s += __expf(x - r.m);
-  }
-}
-__device__ __forceinline__ void rs_take4(RsRun& r, const float4& q) {
-  const float mq = fmaxf(fmaxf(q.x, q.y), fmaxf(q.z, q.w));
-  if (mq > r.m) {
-    r.s *= __expf(r.m - mq);
-    r.m = mq;
-  }
-  if (r.m > NEG_INF) r.s += __expf(q.x - r.m) + __expf(q.y - r.m) + __expf(q.z - r.m) + __expf(q.w - r.m);
-}
-
 __global__ __launch_bounds__(256) void rescore_score_kernel(const float* logits, int64_t ld, const float* lm_logits, int64_t ld_lm,
                                                             const int64_t* ys_out, int64_t ldt, const int32_t* n_rows, int64_t nh, int max_len,
                                                             int V, float* att, float* lm) {
@@ -94,24 +74,8 @@ __global__ __launch_bounds__(256) void rescore_score_kernel(const float* logits,
   float acc = 0.f;
   for (int l = wid; l < n; l += 4) {
     const float* x = base + (h * max_len + l) * ldx;
-    RsRun r{NEG_INF, 0.f};
-    if (vec) {
-      const int nq = V >> 2;
-      int q = lane;
-      for (; q + 192 < nq; q += 256) {                // four loads in flight per lane
-        const float4 a = *reinterpret_cast<const float4*>(x + 4 * q);
-        const float4 b = *reinterpret_cast<const float4*>(x + 4 * (q + 64));
-        const float4 c = *reinterpret_cast<const float4*>(x + 4 * (q + 128));
-        const float4 d = *reinterpret_cast<const float4*>(x + 4 * (q + 192));
-        rs_take4(r, a); rs_take4(r, b); rs_take4(r, c); rs_take4(r, d);
-      }
-      for (; q < nq; q += 64) rs_take4(r, *reinterpret_cast<const float4*>(x + 4 * q));
-      for (int v = 4 * nq + lane; v < V; v += 64) rs_take(r, x[v]);    // the row's last, partial quad
-    } else {
-      for (int v = lane; v < V; v += 64) rs_take(r, x[v]);
-    }
-    const float M = wave_max(r.m);
-    const float S = wave_sum(r.m > NEG_INF ? r.s * __expf(r.m - M) : 0.f);
+    float M, S;
+    rs_row(x, V, vec, lane, M, S);
     const int64_t t = ys_out[h * ldt + l];
     if (t >= 0 && t < V) acc += x[t] - (M + __logf(S));
   }

@@ -4044,3 +4044,88 @@ def attention_rescore(logits, tokens, out_len, scores, max_len, V, ctc_weight, l
             raise L.OtransHipError('attention_rescore: add_score must be f32 [B, W], got %s %s' % (add_score.dtype, tuple(add_score.shape)))
         L.check(lib.otr_rescore_select_add(*sel, _p(add_score.contiguous()), *tail), 'otr_rescore_select_add')
     return {'tokens': nb_tok, 'len': nb_len, 'scores': nb_score, 'perm': perm, 'total': total, 'att': att, 'lm': lm}
+
+
+# ------------------------------------------------------------------ minimum word error rate training (csrc/mwer.hip)
+MWER_MAX_NBEST, MWER_MAX_V = 32, 8192
+
+
+class MwerLossFn(torch.autograd.Function):
+    """The N-best expected number of errors (include/otrans_hip.h otr_mwer_loss) of teacher-forced logits [B*N*max_len, V] (any leading
+    shape) + its gradient in the same call when the logits need one, like LabelSmoothingLossFn.  The head of a row-padded product
+    (ops.padded_rows: rows of V8 = ceil8(V) floats) is read in place and the gradient leaves as the head of a zero-tailed [R, V8]
+    buffer.  `gscale` (a device scalar; None = 1) rides in the written gradient; backward multiplies by the incoming gradient unless
+    that is the cached unit seed of ops.backward.  Returns (loss, seq_logp [B*N], post [B, N], utt_err [B]); only loss is
+    differentiable.  The gradient is fp32: a 16-bit hand-over armed by the logits' Linear (_Grad16Link) is left unused."""
+
+    @staticmethod
+    def forward(ctx, logits, ys_out, n_rows, errors, gscale):
+        V = logits.shape[-1]
+        B, N = errors.shape
+        max_len = ys_out.shape[1]
+        lg = logits.reshape(-1, V)
+        ok = lg.stride(1) == 1 and (lg.shape[0] <= 1 or lg.stride(0) >= V)
+        if not ok:
+            lg = lg.contiguous()
+        ld = lg.stride(0) if lg.shape[0] > 1 else V
+        R = lg.shape[0]
+        need = ctx.needs_input_grad[0]
+        ldd = ld if (V < ld < V + 8 and ld % 8 == 0) else V          # the padded width goes back to LinearFn.backward with a zero tail
+        dev = lg.device
+        f32 = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)    # noqa: E731
+        loss, seq_logp, post, utt_err = f32(), f32(B * N), f32(B, N), f32(B)
+        dlogits = f32(R, ldd) if need else None
+        lib = L.load()
+        nws = lib.otr_mwer_workspace_floats(B, N, max_len)
+        ws = f32(max(nws, 1))
+        L.check(_timed('mwer_loss %dx%dx%dx%d' % (B, N, max_len, V), {'bytes': R * (2 * V + ldd) * 4},
+                       lambda: lib.otr_mwer_loss(_p(lg), ld, _p(ys_out), ys_out.stride(0), _p(n_rows), _p(errors), B, N, max_len, V,
+                                                 _p(gscale), _p(loss), _p(seq_logp), _p(post), _p(utt_err), _p(dlogits), ldd, _p(ws),
+                                                 ws.numel(), _stream())), 'otr_mwer_loss')
+        ctx.save_for_backward(dlogits)
+        ctx.shape, ctx.V = logits.shape, V
+        ctx.mark_non_differentiable(seq_logp, post, utt_err)
+        return loss, seq_logp, post, utt_err
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        (dlogits,) = ctx.saved_tensors
+        seed = _state.get(('unit_grad', g.device, g.dtype))
+        if seed is not None and g.data_ptr() == seed.data_ptr():
+            out = dlogits                                          # g == 1: the saved buffer IS the gradient
+        else:
+            out = torch.empty_like(dlogits)
+            g = g.contiguous().float()
+            L.check(L.load().otr_scale(_p(dlogits), _p(out), dlogits.numel(), _p(g), 1.0, _stream()), 'otr_scale')
+        if out.shape[1] != ctx.V:
+            out._otr_zero_tail = tuple(out.shape)                  # LinearFn.backward may read it at its full width (_zero_tail_of)
+            out = out[:, :ctx.V]
+        return out.view(ctx.shape), None, None, None, None
+
+
+def mwer_loss(logits, ys_out, n_rows, errors, grad_scale=None):
+    """Minimum word error rate loss over an n-best list (include/otrans_hip.h otr_mwer_loss).  logits f32 [B*N, max_len, >= V] or
+    [B*N*max_len, V] with unit stride along the vocabulary (a view with a longer row stride is read in place): the teacher-forced
+    decoder output on rescore_pack's ys_in; ys_out int64 [B*N, max_len] and n_rows int32 [B*N] from rescore_pack; errors int32 [B, N]
+    from edit_distance (< 0: the slot is left out).  grad_scale: a device scalar the gradient into the logits is multiplied by (the
+    loss scale), None = 1.  Returns (loss, {'seq_logp' [B, N] (-inf: not live), 'post' [B, N], 'utt_err' [B]}), the dict detached.
+    At most three launches on the current stream, no host synchronisation, the same bits on every run: capturable."""
+    if errors.dim() != 2 or ys_out.dim() != 2 or ys_out.shape[0] != errors.numel() or n_rows.numel() != errors.numel():
+        raise ValueError('mwer_loss: errors must be [B, N], ys_out [B*N, max_len] and n_rows [B*N], got %s, %s and %s'
+                         % (tuple(errors.shape), tuple(ys_out.shape), tuple(n_rows.shape)))
+    B, N = errors.shape
+    V, max_len = logits.shape[-1], ys_out.shape[1]
+    if not 1 <= N <= MWER_MAX_NBEST:
+        raise ValueError('mwer_loss: N=%d hypotheses per utterance must be in [1, %d]' % (N, MWER_MAX_NBEST))
+    if not 1 <= V <= MWER_MAX_V:
+        raise ValueError('mwer_loss: vocabulary V=%d must be in [1, %d]' % (V, MWER_MAX_V))
+    if max_len < 1 or B * N * max_len >= 1 << 30:
+        raise ValueError('mwer_loss: B*N*max_len = %d*%d*%d must be in [1, 2^30)' % (B, N, max_len))
+    if logits.numel() != B * N * max_len * V:
+        raise ValueError('mwer_loss: logits %s do not hold B*N*max_len = %d rows of V = %d' % (tuple(logits.shape), B * N * max_len, V))
+    _cuda(logits, ys_out, n_rows, errors, grad_scale)
+    if (logits.dtype != torch.float32 or ys_out.dtype != torch.int64 or n_rows.dtype != torch.int32 or errors.dtype != torch.int32
+            or ys_out.stride(1) != 1 or ys_out.stride(0) < max_len):
+        raise L.OtransHipError('mwer_loss: logits f32, ys_out int64 (rows contiguous), n_rows int32, errors int32 expected')
+    loss, seq_logp, post, utt_err = MwerLossFn.apply(logits, ys_out, n_rows.contiguous(), errors.contiguous(), grad_scale)
+    return loss, {'seq_logp': seq_logp.view(B, N), 'post': post, 'utt_err': utt_err}
