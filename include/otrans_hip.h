@@ -39,7 +39,9 @@ extern "C" {
  * 300 was rounds 3-5, during which otr_optimizer_step, otr_ln_desc_t, otr_wgrad_item_t and otr_beam_prune_cached changed without a
  * bump; 602: the rescoring entries, additions only; 603: otr_ctc_align, additions only; 604: otr_ngram_lookup and otr_ctc_beam_search_lm, additions only; 605:
  * otr_edit_distance, additions only; 606: otr_ngram_score_cands, otr_ngram_score_seqs and otr_rescore_select_add, additions only; 607: otr_ngram_count, otr_ngram_stats and otr_ngram_estimate, additions only;
- * 608: otr_mwer_workspace_floats and otr_mwer_loss, additions only).  A binding compares otr_version() with the OTR_ABI_VERSION it was written against BEFORE its first call and refuses a
+ * 608: otr_mwer_workspace_floats and otr_mwer_loss, additions only; still 608: otr_feature_prepare_workspace_bytes, otr_feature_prepare and
+ * otr_cmvn_accumulate were added without a bump -- no existing signature, structure or meaning changed, and a binding that needs them
+ * fails on the missing symbol of an older library when it loads it).  A binding compares otr_version() with the OTR_ABI_VERSION it was written against BEFORE its first call and refuses a
  * library that answers anything else: descriptors are passed by pointer and read at the library's idea of their size. */
 #define OTR_ABI_VERSION 608
 int32_t otr_version(void);
@@ -997,6 +999,42 @@ int32_t otr_transpose_batched(const void* src, void* dst, const int64_t* table, 
  *      rectangles per utterance, ranges int32 [B,NR,4] = {t0,t1,f0,f1} half-open.  The rectangles are drawn on the host
  *      with the reference's own random calls (opentransformer_amd/data.py), so the masks are bit-identical. */
 int32_t otr_spec_mask(float* x, const int32_t* ranges, int32_t B, int32_t NR, int32_t T, int32_t F, void* stream);
+
+/* ---- feature preparation for device batch assembly (otrans/data/audio.py:125-136: normalisation -> gaussian noise -> SpecAugment, run
+ *      per utterance after the fbank) while a packed ragged upload is spread into the padded batch, and the sums of a global CMVN;
+ *      csrc/featprep.hip.  fp32 / fp64 in every build.
+ * otr_feature_prepare: utterance b is the contiguous span of lengths[b] * F floats at src + row_off[b] * F (row_off int64 [B] in FRAMES,
+ *   lengths int32 [B], both on the device; lengths[b] is clamped to [0, Tmax]): one [sum T, F] buffer.  src == dst with row_off[b] ==
+ *   b * Tmax is the in-place padded form; every other overlap of src and dst is undefined.
+ *   dst f32 [B, Tmax, F]: EVERY cell is written (it may be uninitialised).  Rows t >= lengths[b] are exactly 0.0f.  A live cell is
+ *   y = norm(x) + noise[b, f] (noise f32 [B, F] or NULL: one vector per utterance added to every frame, the reference's quirk), then
+ *   exactly 0.0f inside any of the NR rectangles of utterance b, ranges int32 [B, NR, 4] = {t0, t1, f0, f1} half-open as otr_spec_mask
+ *   takes them (NULL: none; NR <= 64; an empty rectangle changes nothing).
+ *   norm_mode 0: norm(x) = x.  1: (x - mean_b) / std_b with the utterance's scalar mean and UNBIASED std over its lengths[b] * F values,
+ *   both rounded to fp32 before use as torch.std_mean gives them (audio.py:22-24); a zero std or fewer than two values gives what IEEE
+ *   gives, there is no epsilon.  2: (x - gmean[f]) / gstd[f], f32 [F] each.
+ *   mask uint8 [B, Tmax] (or NULL) = 1 where t < lengths[b]; stats f32 [B, 2] (or NULL) = the mean and std used in mode 1 (untouched in
+ *   the other modes).  An utterance of length 0 gives zero rows and a zero mask; its row_off is not read from and its stats are
+ *   unspecified.
+ *   Launches: one (modes 0 and 2) or two (mode 1: fp64 sums of d = x - x[0] and d * d per chunk of 4096 elements into the workspace; then
+ *   every workgroup of the second launch adds the utterance's partials in index order).  No floating-point atomics: the same call gives
+ *   the same bits.  Loads and stores are 16 bytes wide where the utterance's base allows (src span and dst row judged separately; a dst
+ *   row is aligned when dst is and Tmax * F is a multiple of 4 or b = 0), scalar otherwise.
+ *   workspace: at least otr_feature_prepare_workspace_bytes(B, Tmax, F) bytes, 8-byte aligned, in every mode; that entry runs on the host
+ *   and answers -1 for a shape otr_feature_prepare refuses.
+ *   Refused before any launch (< 0, outputs untouched): a NULL src, row_off, lengths or dst; B outside [0, 65535], Tmax <= 0, F <= 0,
+ *   Tmax * F >= 2^31; NR outside [0, 64]; NR > 0 with NULL ranges; norm_mode outside 0 .. 2; mode 2 with a NULL gmean or gstd; a
+ *   workspace that is too small.  B = 0 returns 0 without a launch.  Caller-owned buffers, no allocation or host synchronisation: capturable.
+ * otr_cmvn_accumulate: adds into acc f64 [2F + 1] the per-dimension sums [F], the per-dimension sums of squares [F] and the frame count
+ *   over all live frames (lengths[b] <= 0: none) of the call, src / row_off / lengths as above.  One launch; a workgroup owns 16
+ *   dimensions and is the only writer of their entries, and adds in a fixed order: a given sequence of calls on one stream gives the
+ *   same bits.  Mean and std are formed on the host from acc. */
+int64_t otr_feature_prepare_workspace_bytes(int32_t B, int32_t Tmax, int32_t F);
+int32_t otr_feature_prepare(const float* src, const int64_t* row_off, const int32_t* lengths, int32_t B, int32_t Tmax, int32_t F,
+                            int32_t norm_mode, const float* gmean, const float* gstd, const float* noise, const int32_t* ranges, int32_t NR,
+                            float* dst, uint8_t* mask, float* stats, void* workspace, int64_t workspace_bytes, void* stream);
+int32_t otr_cmvn_accumulate(const float* src, const int64_t* row_off, const int32_t* lengths, int32_t B, int32_t F, double* acc,
+                            void* stream);
 
 /* ---- incremental (KV-cached) decoding, SURVEY.md 8f rank 1.  The reference threads a `cache` argument through
  *      decoder.inference / attention.inference but never fills it (decoder/transformer.py:185-208,

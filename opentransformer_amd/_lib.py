@@ -140,6 +140,9 @@ SIGNATURES = {
     'otr_debug_wgrad256_errors': [_P],
     'otr_debug_trread': [_P, _P, _P, _P],
     'otr_spec_mask': [_P, _P, _I32, _I32, _I32, _I32, _P],
+    'otr_feature_prepare_workspace_bytes': [_I32, _I32, _I32],
+    'otr_feature_prepare': [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _I64, _P],
+    'otr_cmvn_accumulate': [_P, _P, _P, _I32, _I32, _P, _P],
     'otr_transpose_batched': [_P, _P, _P, _I32, _I64, _I32, _P],
     'otr_glu_fwd': [_P, _P, _I32, _I64, _I64, _P, _P],
     'otr_glu_bwd': [_P, _P, _P, _P, _I32, _I64, _I64, _P, _I32, _P],
@@ -264,7 +267,8 @@ _RESTYPE = {'otr_last_error_string': C.c_char_p, 'otr_dec_ffn_hsave_bytes': C.c_
             'otr_ffn_split_padded_rows': C.c_int64, 'otr_add_layernorm_bwd_partial_rows': C.c_int64,
             'otr_ln_bwd_proj_partial_rows': C.c_int64, 'otr_dwconv_bwd_partial_rows': C.c_int64, 'otr_dwconv_fwd_partial_rows': C.c_int64,
             'otr_conv2_wide_scratch_bytes': C.c_int64, 'otr_add2_colsum_partial_rows': C.c_int64,
-            'otr_ctc_beam_workspace_bytes': C.c_int64, 'otr_ctc_align_workspace_bytes': C.c_int64, 'otr_mwer_workspace_floats': C.c_int64}
+            'otr_ctc_beam_workspace_bytes': C.c_int64, 'otr_ctc_align_workspace_bytes': C.c_int64, 'otr_mwer_workspace_floats': C.c_int64,
+            'otr_feature_prepare_workspace_bytes': C.c_int64}
 
 _libs = {}
 _kind = 'bf16'
