@@ -12,6 +12,9 @@ Same constructor arguments and return values as the reference recognizers.  Two 
   self-attention K/V live in write-once caches addressed through a beam-tree ancestor table; the position,
   prefix length and ping-pong state are device-resident, so each step is ONE hipGraph replay
   (decoder + LM + scoring + pruning).  Hypotheses are identical to the re-forward loop.
+
+Both loops keep their beams in a _BeamState and end every step in its `advance` (scoring + prune); a loop only produces the step's
+logits.  CachedBeamState is a _BeamState plus what the cache needs.
 """
 import ctypes as C
 import weakref
@@ -353,7 +356,7 @@ class _JointCTC:
 
     def __init__(self, B, T, V, K, beam, dev):
         R = B * beam
-        self.B, self.T, self.V, self.K, self.beam = B, T, V, K, beam
+        self.K = K
         new = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)    # noqa: E731
         self.lp = new((B, T, V), torch.float32)
         self.lengths = new((B,), torch.int32)
@@ -366,17 +369,121 @@ class _JointCTC:
         self.lp.copy_(log_probs)
         self.lengths.copy_(lengths.reshape(-1))
 
-    def score(self, rec, logits, lm_logits, preds, cur, flags, k_score, k_idx, t=0, pos=None):
-        """pre-beam top-K' (+ the n-gram's addend) + CTC prefix scores + the joint top-beam of one step, reading phase cur, writing
-        phase cur ^ 1's states"""
-        lam = float(rec.ctc_weight)
-        ops.joint_prebeam(logits, lm_logits, 1.0 - lam, float(rec.lm_weight or 0.0), self.K, self.V, self.cand_s, self.cand_i)
-        if rec.ngram_lm is not None:                      # the n-gram's addend, in place; the prefix score ranks by counting, in any order
-            ops.ngram_score_candidates(rec.ngram_lm, preds, self.cand_i, self.cand_s, rec.alpha, rec.beta, EOS, t=t, pos=pos, flags=flags,
-                                       cand_out=self.cand_s)
-        ops.ctc_prefix_score(self.lp, self.lengths, self.cand_i, preds, t, self.beam, rec.model.assistor.blank, EOS, self.jsrc[cur],
-                             self.state[cur], self.state[cur ^ 1], pos=pos, cand_score=self.cand_s, ctc_weight=lam, beam=self.beam,
-                             flags=flags, k_score=k_score, k_idx=k_idx, k_src=self.k_src)
+
+class _BeamState:
+    """The beams of one search over R = B * beam hypotheses, for both decode loops: ping-pong prefixes / scores / finished flags (a
+    step reads phase cur and writes phase cur ^ 1 only), the per-row top-beam the scoring hands to the prune, the finished counter and,
+    where the recognizer asks for them, the joint search's state and the pinned n-gram LM with the plain search's pre-beam candidates.
+    cached: the counter is [finished hypotheses, the prune kernel's arrival word] per phase, as otr_beam_prune_cached takes it -- the
+    count of a step stays readable while the next step runs (CachedBeamState.run) --, else the one count of otr_beam_prune."""
+
+    def __init__(self, rec, b, Tm, dev, cached):
+        beam = rec.beam_width
+        R = b * beam
+        self.rec, self.b, self.Tm, self.dev, self.beam, self.R = rec, b, Tm, dev, beam, R
+        self.V = rec.model.decoder.output_layer.weight.shape[0]
+        self.ldp = rec.max_len + 2
+        new = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)    # noqa: E731
+        self.preds = [new((R, self.ldp), torch.long) for _ in range(2)]
+        self.scores = [new((R,), torch.float32) for _ in range(2)]
+        self.flags = [new((R,), torch.uint8) for _ in range(2)]
+        self.k_score = new((R, beam), torch.float32)
+        self.k_idx = new((R, beam), torch.long)
+        self.n_fin = new((2, 2) if cached else (1,), torch.int32)
+        self.score0 = torch.tensor([0.0] + [-float('inf')] * (beam - 1), device=dev).repeat([b]).contiguous()
+        self.joint = _JointCTC(b, Tm, self.V, rec.ctc_beam, beam, dev) if rec.joint_ctc else None
+        self.ngram = rec.ngram_lm.to(dev) if rec.ngram_lm is not None else None     # pinned: a cached state's key holds its table's address
+        self.cand = None
+        if self.ngram is not None and self.joint is None:      # the plain search with an n-gram: pre-beam + addend + select, no full top-k
+            self.cand = (new((R, rec.ngram_beam), torch.float32), new((R, rec.ngram_beam), torch.int32))
+
+    def reset(self):
+        """the start of a search in phase 0: BOS alone in every prefix, one live hypothesis per utterance, nothing finished"""
+        self.preds[0].fill_(EOS)
+        self.preds[0][:, 0] = BOS
+        self.scores[0].copy_(self.score0)
+        self.flags[0].zero_()
+        self.n_fin.zero_()       # incl. the prune kernel's arrival word: a launch aborted mid-step would leave it poisoned for every later batch (ADVICE r05)
+
+    def advance(self, logits, lm_logits, cur, t=0, pos=None, anc=None, maxlen=0):
+        """The scoring tail of one step (recognize/speech2text.py:102-146), reading phase cur, writing phase cur ^ 1.  logits and
+        lm_logits (or None): the next-token scores as 2-D views [R, >= V] of any row stride.  The prefixes have t columns (the
+        re-forward loop's host step), or pos[cur] + 1 where the cached loop gives its per-phase device positions `pos` with the
+        ancestor tables `anc` of width maxlen."""
+        rec, lib, nxt, j = self.rec, L.load(), cur ^ 1, self.joint
+        V, beam, lm_weight = self.V, self.beam, float(rec.lm_weight or 0.0)
+        preds, scores, flags = self.preds, self.scores, self.flags
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        p_cur = pos[cur] if pos is not None else None
+        if j is not None:                                 # pre-beam top-K' (+ the n-gram's addend, in place) + CTC prefix scores + joint top-beam
+            lam = float(rec.ctc_weight)
+            ops.joint_prebeam(logits, lm_logits, 1.0 - lam, lm_weight, j.K, V, j.cand_s, j.cand_i)
+            if self.ngram is not None:                    # the prefix score ranks by counting, in any order
+                ops.ngram_score_candidates(self.ngram, preds[cur], j.cand_i, j.cand_s, rec.alpha, rec.beta, EOS, t=t, pos=p_cur,
+                                           flags=flags[cur], cand_out=j.cand_s)
+            ops.ctc_prefix_score(j.lp, j.lengths, j.cand_i, preds[cur], t, beam, rec.model.assistor.blank, EOS, j.jsrc[cur], j.state[cur],
+                                 j.state[nxt], pos=p_cur, cand_score=j.cand_s, ctc_weight=lam, beam=beam, flags=flags[cur],
+                                 k_score=self.k_score, k_idx=self.k_idx, k_src=j.k_src)
+        elif self.cand is not None:                       # the n-gram alone: pre-beam + addend + select in otr_beam_topk's place
+            ops.joint_prebeam(logits, lm_logits, 1.0, lm_weight, rec.ngram_beam, V, *self.cand)
+            ops.ngram_score_candidates(self.ngram, preds[cur], self.cand[1], self.cand[0], rec.alpha, rec.beta, EOS, t=t, pos=p_cur,
+                                       flags=flags[cur], beam=beam, cand_out=self.cand[0], k_score=self.k_score, k_idx=self.k_idx)
+        else:
+            L.check(lib.otr_beam_topk(_ptr(logits), logits.stride(0), _ptr(lm_logits), lm_logits.stride(0) if lm_logits is not None else V,
+                                      lm_weight, self.R, V, beam, _ptr(self.k_score), _ptr(self.k_idx), stream), 'otr_beam_topk')
+        # the prune: {host t, device pos} x {plain, joint}
+        args = [_ptr(self.k_score), _ptr(self.k_idx), _ptr(scores[cur]), _ptr(flags[cur]), _ptr(preds[cur]), self.ldp, self.b, beam]
+        out = [_ptr(scores[nxt]), _ptr(flags[nxt]), _ptr(preds[nxt])]
+        if pos is None:
+            args += [t, EOS] + out + [_ptr(self.n_fin)]
+        else:
+            args += [EOS, _ptr(pos[cur]), _ptr(pos[nxt]), _ptr(anc[cur]), _ptr(anc[nxt]), maxlen] + out + [_ptr(self.n_fin[nxt])]
+        if j is not None:
+            args += [_ptr(j.k_src), _ptr(j.jsrc[nxt])]
+        if pos is None and j is None:
+            L.check(lib.otr_beam_prune(*args, stream), 'otr_beam_prune')
+        elif pos is None:
+            L.check(lib.otr_beam_prune_joint(*args, stream), 'otr_beam_prune_joint')
+        elif j is None:
+            L.check(lib.otr_beam_prune_cached(*args, stream), 'otr_beam_prune_cached')
+        else:
+            L.check(lib.otr_beam_prune_cached_joint(*args, stream), 'otr_beam_prune_cached_joint')
+
+
+def _lm_recurrent(lm):
+    """True for the RecurrentLanguageModel, False for the Transformer LM, None for any other model_type (the step loops run such an LM
+    like the Transformer LM, rescore=True refuses it).  The one reader of model_type."""
+    return {'recurrent_lm': True, 'transformer_lm': False}.get(getattr(lm, 'model_type', ''))
+
+
+def _lm_logits(lm, tokens, pos=None, out=None, hidden=None, every=False):
+    """The LM's un-normalised scores of the next token (None without an LM) after the last column of the prefixes `tokens` [R, t] -- a
+    2-D view [R, >= V] of any row stride -- or, with `every`, after each column (the rescore pass over ys_in).  The cached loop
+    passes preds with its device position `pos`, the _PaddedOutput `out` and `hidden`, which gives the Transformer LM's rows of that
+    position from its K/V caches.  The recurrent LM scores the last token alone from the ZERO state (recognize/base.py:35-36)."""
+    if lm is None:
+        return None
+    if _lm_recurrent(lm):
+        return lm.logits_last(tokens.reshape(-1, 1) if every else tokens, pos, out=out)
+    lg = _output(out, lm.output_project, hidden() if hidden is not None else lm.hidden(tokens))
+    return lg if every or hidden is not None else lg[:, -1]
+
+
+def _vocab_limit(who, V):
+    if V > ops.JOINT_MAX_V:
+        raise ValueError('%s: vocabulary %d > %d' % (who, V, ops.JOINT_MAX_V))
+
+
+def _prebeam_limits(who, name, beam_width, K, V):
+    """the pre-beam's limits (include/otrans_hip.h), refused in the constructor; returns the pre-beam width `name` (K, or ESPnet's
+    default min(V, int(1.5 * beam_width)))"""
+    if not 1 <= beam_width <= ops.JOINT_MAX_BEAM:
+        raise ValueError('%s: beam_width=%d must be in [1, %d]' % (who, beam_width, ops.JOINT_MAX_BEAM))
+    _vocab_limit(who, V)
+    K = int(K) if K is not None else min(V, int(1.5 * beam_width))
+    if not beam_width <= K <= min(V, ops.JOINT_MAX_K):
+        raise ValueError('%s: %s=%d must be in [beam_width=%d, min(V=%d, %d)]' % (who, name, K, beam_width, V, ops.JOINT_MAX_K))
+    return K
 
 
 class SpeechToTextRecognizer(Recognizer):
@@ -419,40 +526,26 @@ class SpeechToTextRecognizer(Recognizer):
             ops._rescore_check('rescore=True', beam_width, model.decoder.output_layer.weight.shape[0], nbest, ctc_weight)
             if max_len < 1 or self.cutoff_top_n < 1:
                 raise ValueError('rescore=True: max_len=%d and cutoff_top_n=%d must be >= 1' % (max_len, self.cutoff_top_n))
-            if lm is not None and getattr(lm, 'model_type', '') not in ('transformer_lm', 'recurrent_lm'):
+            if lm is not None and _lm_recurrent(lm) is None:
                 raise ValueError('rescore=True: the language model %r cannot be scored teacher-forced here (TransformerLanguageModel and '
                                  'RecurrentLanguageModel can)' % type(lm).__name__)
             self._rescore_out = None
         self.beam_width, self.max_len, self.nbest = beam_width, max_len, nbest
         self.penalty, self.lamda, self.ctc_weight, self.lm_weight = penalty, lamda, ctc_weight, lm_weight
         self.joint_ctc, self.ctc_beam = bool(joint_ctc), None
+        V = model.decoder.output_layer.weight.shape[0] if self.joint_ctc or ngram_lm is not None else None
         if self.joint_ctc:
             if getattr(model, 'assistor', None) is None:
                 raise ValueError('joint_ctc=True needs the model\'s CTC head (model.assistor): build the model with ctc_weight > 0')
             if not 0.0 <= float(ctc_weight) <= 1.0:
                 raise ValueError('joint_ctc=True: ctc_weight=%r must be in [0, 1]' % (ctc_weight,))
-            V = model.decoder.output_layer.weight.shape[0]
-            if not 1 <= beam_width <= ops.JOINT_MAX_BEAM:
-                raise ValueError('joint_ctc=True: beam_width=%d must be in [1, %d]' % (beam_width, ops.JOINT_MAX_BEAM))
-            if V > ops.JOINT_MAX_V:
-                raise ValueError('joint_ctc=True: vocabulary %d > %d' % (V, ops.JOINT_MAX_V))
-            self.ctc_beam = int(ctc_beam) if ctc_beam is not None else min(V, int(1.5 * beam_width))
-            if not beam_width <= self.ctc_beam <= min(V, ops.JOINT_MAX_K):
-                raise ValueError('joint_ctc=True: ctc_beam=%d must be in [beam_width=%d, min(V=%d, %d)]'
-                                 % (self.ctc_beam, beam_width, V, ops.JOINT_MAX_K))
+            self.ctc_beam = _prebeam_limits('joint_ctc=True', 'ctc_beam', beam_width, ctc_beam, V)
         if ngram_lm is not None:
-            V = model.decoder.output_layer.weight.shape[0]
             if ngram_lm.vocab_size != V:
                 raise ValueError('ngram_lm: the n-gram LM was loaded for %d units, the decoder has V=%d' % (ngram_lm.vocab_size, V))
-            if V > ops.JOINT_MAX_V:
-                raise ValueError('ngram_lm: vocabulary %d > %d' % (V, ops.JOINT_MAX_V))
-            if not self.rescore and not self.joint_ctc:       # the plain search: the pre-beam's limits (the joint search checked its own)
-                if not 1 <= beam_width <= ops.JOINT_MAX_BEAM:
-                    raise ValueError('ngram_lm: beam_width=%d must be in [1, %d]' % (beam_width, ops.JOINT_MAX_BEAM))
-                self.ngram_beam = int(ngram_beam) if ngram_beam is not None else min(V, int(1.5 * beam_width))
-                if not beam_width <= self.ngram_beam <= min(V, ops.JOINT_MAX_K):
-                    raise ValueError('ngram_lm: ngram_beam=%d must be in [beam_width=%d, min(V=%d, %d)]'
-                                     % (self.ngram_beam, beam_width, V, ops.JOINT_MAX_K))
+            _vocab_limit('ngram_lm', V)
+            if not self.rescore and not self.joint_ctc:       # the plain search pre-beams too (the joint search's limits are checked above)
+                self.ngram_beam = _prebeam_limits('ngram_lm', 'ngram_beam', beam_width, ngram_beam, V)
         self.attn_weights = {}
         self.apply_cache = bool(apply_cache)
         self.use_hipgraph = True
@@ -510,9 +603,7 @@ class SpeechToTextRecognizer(Recognizer):
         recognize(): nbest_translate(tokens) gives its strings (it stops at the first EOS, which is where a length ends).  On the re-forward and cached
         paths a hypothesis ends before its first EOS; on the rescore path the search's < 0 padding marks the end."""
         if self.rescore:
-            memory, memory_mask, _, _ = self.encode(inputs, inputs_mask)
-            log_probs, length = self.model.assistor.inference(memory, memory_mask)
-            res = self.rescore_pass(memory, memory_mask, log_probs.float().contiguous(), length)
+            res = self._rescore(inputs, inputs_mask)
             tok = res['tokens']
             return tok.masked_fill(tok < 0, EOS), torch.sum(tok >= 0, dim=-1, dtype=torch.int32), res['scores']
         search = self._search_cached if self.apply_cache else self._search
@@ -527,8 +618,7 @@ class SpeechToTextRecognizer(Recognizer):
         """the cached beam search: (scores [B*beam], prefixes [B*beam, >= steps + 1] with BOS, steps, B) on the device"""
         memory, memory_mask, _, _ = self.encode(inputs, inputs_mask)
         b, t, _ = memory.size()
-        if self.joint_ctc and t > ops.JOINT_MAX_T:
-            raise ValueError('joint_ctc=True: T\'=%d encoder frames > %d' % (t, ops.JOINT_MAX_T))
+        head = self._ctc_head(memory, memory_mask) if self.joint_ctc else None
         # the captured graphs bake in the device pointers of the stand-alone 16-bit weight shadows (ops.weight_lp caches a
         # cast per parameter version): a checkpoint loaded into the same modules, averaging, ... re-allocates them, so the
         # weights' (version, pointer) fingerprint is part of the key -- stale graphs are dropped, never replayed
@@ -548,8 +638,8 @@ class SpeechToTextRecognizer(Recognizer):
                 self._cached_states.pop(next(iter(self._cached_states)))
             st = self._cached_states[key] = CachedBeamState(self, b, t, memory.device)
         st.load_memory(memory, memory_mask)
-        if st.joint is not None:
-            st.joint.load(*self._ctc_head(memory, memory_mask))
+        if head is not None:
+            st.joint.load(*head)
         cur, steps = st.run()
         return st.scores[cur], st.preds[cur], steps, b
 
@@ -585,13 +675,7 @@ class SpeechToTextRecognizer(Recognizer):
         ys_in = packed[0]
         out_dec, out_lm = self._rescore_outputs()
         logits = _output(out_dec, dec.output_layer, dec.hidden(ys_in, memory, memory_mask, share=W))
-        lm_logits = None
-        if lm is not None and lm.model_type == 'recurrent_lm':
-            # as in the beam search's shallow fusion (recognize/base.py:35-36): every token scored from the ZERO state -- one LSTM step
-            # over all positions at once
-            lm_logits = lm.logits_last(ys_in.reshape(-1, 1), out=out_lm)
-        elif lm is not None:
-            lm_logits = _output(out_lm, lm.output_project, lm.hidden(ys_in))
+        lm_logits = _lm_logits(lm, ys_in, out=out_lm, every=True)
         res = ops.attention_rescore(logits, tokens, out_len, ctc, self.max_len, V, self.ctc_weight, lm_logits=lm_logits,
                                     lm_weight=float(self.lm_weight or 0.0) if lm is not None else 0.0, nbest=self.nbest,
                                     penalty=self.penalty, lamda=self.lamda, packed=packed, bos=BOS, eos=EOS, add_score=ng_score)
@@ -599,11 +683,15 @@ class SpeechToTextRecognizer(Recognizer):
         res['ctc'], res['ng'] = ctc, ng_score             # the terms of total beside att / lm (ng: None without an n-gram LM)
         return res
 
-    @torch.no_grad()
-    def recognize_rescore(self, inputs, inputs_mask):
+    def _rescore(self, inputs, inputs_mask):
+        """the two-pass decode of a batch: encoder, CTC head, rescore_pass"""
         memory, memory_mask, _, _ = self.encode(inputs, inputs_mask)
         log_probs, length = self.model.assistor.inference(memory, memory_mask)
-        res = self.rescore_pass(memory, memory_mask, log_probs.float().contiguous(), length)
+        return self.rescore_pass(memory, memory_mask, log_probs.float().contiguous(), length)
+
+    @torch.no_grad()
+    def recognize_rescore(self, inputs, inputs_mask):
+        res = self._rescore(inputs, inputs_mask)
         tok = res['tokens'].cpu()
         preds = torch.cat((tok.masked_fill(tok < 0, EOS), torch.full_like(tok[:, :, :1], EOS)), dim=-1)      # EOS behind every hypothesis
         return self.nbest_translate(preds), res['scores'].cpu()
@@ -620,102 +708,50 @@ class SpeechToTextRecognizer(Recognizer):
     def _search(self, inputs, inputs_mask):
         """the re-forward beam search: (scores [B*beam], prefixes [B*beam, max_len + 2] with BOS, steps, B) on the device"""
         beam = self.beam_width
-        lib = L.load()
         memory, memory_mask, _, _ = self.encode(inputs, inputs_mask)
-        dev = memory.device
         b, t, v = memory.size()
         R = b * beam
+        head = self._ctc_head(memory, memory_mask) if self.joint_ctc else None
         # tile the encoder memory over the beam, like the reference (speech2text.py:51-52)
         beam_memory = memory.unsqueeze(1).repeat([1, beam, 1, 1]).view(R, t, v)
         beam_mask = memory_mask.unsqueeze(1).repeat([1, beam, 1]).view(R, t)
-        ldp = self.max_len + 2
-        preds = [torch.full((R, ldp), EOS, dtype=torch.long, device=dev) for _ in range(2)]
-        preds[0][:, 0] = BOS
-        scores = [torch.tensor([0.0] + [-float('inf')] * (beam - 1), device=dev).repeat([b]).contiguous(),
-                  torch.empty(R, device=dev)]
-        flags = [torch.zeros(R, dtype=torch.uint8, device=dev), torch.zeros(R, dtype=torch.uint8, device=dev)]
-        k_score = torch.empty((R, beam), dtype=torch.float32, device=dev)
-        k_idx = torch.empty((R, beam), dtype=torch.long, device=dev)
-        n_fin = torch.zeros(1, dtype=torch.int32, device=dev)
-        joint = None
-        if self.joint_ctc:
-            log_probs, length = self._ctc_head(memory, memory_mask)
-            joint = _JointCTC(b, t, self.model.decoder.output_layer.weight.shape[0], self.ctc_beam, beam, dev)
-            joint.load(log_probs, length)
-        cand = None
-        if self.ngram_lm is not None and joint is None:      # the plain search with an n-gram: pre-beam + addend + select, no full top-k
-            cand = (torch.empty((R, self.ngram_beam), dtype=torch.float32, device=dev),
-                    torch.empty((R, self.ngram_beam), dtype=torch.int32, device=dev))
+        bs = _BeamState(self, b, t, memory.device, cached=False)
+        bs.reset()
+        if head is not None:
+            bs.joint.load(*head)
         cur, steps = 0, 0
-        stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)    # noqa: E731
         for step in range(1, self.max_len + 1):
-            prefix = preds[cur][:, :step].contiguous()
+            prefix = bs.preds[cur][:, :step].contiguous()
             logits, _ = self.model.decoder(prefix, beam_memory, beam_mask)       # [R, step, V] fp32
-            V = logits.size(-1)
-            lm_logits, lm_off, lm_ld = None, 0, step * V
-            if self.lm is not None and getattr(self.lm, 'model_type', '') == 'recurrent_lm':
-                lm_logits, lm_off, lm_ld = self.lm.logits_last(prefix), 0, V        # the last token, no state (recognize/base.py:35-36)
-            elif self.lm is not None:
-                lm_logits, lm_off = self.lm.logits(prefix), (step - 1) * V
-            if joint is not None:
-                joint.score(self, logits[:, step - 1], None if lm_logits is None else lm_logits.reshape(R, -1, V)[:, -1], preds[cur], cur,
-                            flags[cur], k_score, k_idx, t=step)
-                L.check(lib.otr_beam_prune_joint(_ptr(k_score), _ptr(k_idx), _ptr(scores[cur]), _ptr(flags[cur]), _ptr(preds[cur]), ldp, b,
-                                                 beam, step, EOS, _ptr(scores[cur ^ 1]), _ptr(flags[cur ^ 1]), _ptr(preds[cur ^ 1]),
-                                                 _ptr(n_fin), _ptr(joint.k_src), _ptr(joint.jsrc[cur ^ 1]), stream()), 'otr_beam_prune_joint')
-            else:
-                if cand is not None:
-                    ops.joint_prebeam(logits[:, step - 1], None if lm_logits is None else lm_logits.reshape(R, -1, V)[:, -1], 1.0,
-                                      float(self.lm_weight or 0.0), self.ngram_beam, V, *cand)
-                    ops.ngram_score_candidates(self.ngram_lm, preds[cur], cand[1], cand[0], self.alpha, self.beta, EOS, t=step,
-                                               flags=flags[cur], beam=beam, cand_out=cand[0], k_score=k_score, k_idx=k_idx)
-                else:
-                    L.check(lib.otr_beam_topk(_ptr(logits, (step - 1) * V), step * V,
-                                              _ptr(lm_logits, lm_off) if lm_logits is not None else None, lm_ld,
-                                              float(self.lm_weight or 0.0), R, V, beam, _ptr(k_score), _ptr(k_idx), stream()),
-                            'otr_beam_topk')
-                L.check(lib.otr_beam_prune(_ptr(k_score), _ptr(k_idx), _ptr(scores[cur]), _ptr(flags[cur]), _ptr(preds[cur]),
-                                           ldp, b, beam, step, EOS, _ptr(scores[cur ^ 1]), _ptr(flags[cur ^ 1]),
-                                           _ptr(preds[cur ^ 1]), _ptr(n_fin), stream()), 'otr_beam_prune')
+            bs.advance(logits[:, step - 1], _lm_logits(self.lm, prefix), cur, t=step)
             cur ^= 1
             steps = step
             if self.trace is not None:
-                self.trace.append((preds[cur][:, :step + 1].clone(), scores[cur].clone()))
-            if int(n_fin.item()) == R:           # the reference syncs here every step too (speech2text.py:67)
+                self.trace.append((bs.preds[cur][:, :step + 1].clone(), bs.scores[cur].clone()))
+            if int(bs.n_fin.item()) == R:           # the reference syncs here every step too (speech2text.py:67)
                 break
-        return scores[cur], preds[cur], steps, b
+        return bs.scores[cur], bs.preds[cur], steps, b
 
 
-class CachedBeamState:
-    """Static device state of the cached beam search for one (batch, T', beam, max_len) shape: ping-pong beam
-    buffers, ancestor tables, write-once self-attention caches for the decoder and the LM, per-utterance
-    cross-attention K/V, and the two captured step graphs (even / odd ping-pong phase)."""
+class CachedBeamState(_BeamState):
+    """Static device state of the cached beam search for one (batch, T', beam, max_len) shape: the beams (_BeamState) and what the
+    cache adds to them -- the device position and ancestor tables per phase, write-once self-attention caches for the decoder and the
+    LM, per-utterance cross-attention K/V, and the two captured step graphs (even / odd ping-pong phase)."""
 
     def __init__(self, rec, b, Tm, dev):
-        self.rec, self.b, self.Tm, self.dev = weakref.proxy(rec), b, Tm, dev     # no rec <-> state cycle: graphs die with rec
-        dec, lm = rec.model.decoder, rec.lm
-        beam = rec.beam_width
-        R = self.R = b * beam
+        super().__init__(weakref.proxy(rec), b, Tm, dev, cached=True)     # no rec <-> state cycle: graphs die with rec
+        dec, lm, R = rec.model.decoder, rec.lm, self.R
         self.maxlen = rec.max_len + 1
-        self.ldp = rec.max_len + 2
         adt = ops.act_dtype()
         new = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)    # noqa: E731
-        self.preds = [new((R, self.ldp), torch.long) for _ in range(2)]
-        self.scores = [new((R,), torch.float32) for _ in range(2)]
-        self.flags = [new((R,), torch.uint8) for _ in range(2)]
         self.pos = [new((1,), torch.int32) for _ in range(2)]
         self.anc = [new((R, self.maxlen), torch.int32) for _ in range(2)]
-        self.k_score = new((R, beam), torch.float32)
-        self.k_idx = new((R, beam), torch.long)
-        self.n_fin = new((2, 2), torch.int32)         # per phase: [finished hypotheses, the prune kernel's arrival word]; the count of a step
-                                                      # stays readable while the next step runs (run: the lagged all-finished test)
-        self.score0 = torch.tensor([0.0] + [-float('inf')] * (beam - 1), device=dev).repeat([b]).contiguous()
         d = dec.d_model
         self.mem_kv = [new((b, Tm, 2 * d), adt) for _ in dec.blocks]
         self.mem_mask = new((b, Tm), torch.uint8)
         self.dec_cache = [(new((R, self.maxlen, d), adt), new((R, self.maxlen, d), adt)) for _ in dec.blocks]
         self.lm_cache = None
-        self.lm_recurrent = lm is not None and getattr(lm, 'model_type', '') == 'recurrent_lm'
+        self.lm_recurrent = bool(_lm_recurrent(lm))
         if lm is not None and not self.lm_recurrent:
             dl = lm.embedding.weight.shape[1]
             self.lm_cache = [(new((R, self.maxlen, dl), adt), new((R, self.maxlen, dl), adt)) for _ in lm.blocks]
@@ -744,11 +780,6 @@ class CachedBeamState:
         self.paired = bool(_DECODE_PAIR and self.fused_dec and self.fused_lm and not self.lm_recurrent)
         self.side = torch.cuda.Stream(device=dev) if (lm is not None and not self.paired) else None
         self.side_ws = ops.new_workspace(dev) if self.side is not None else None
-        self.joint = _JointCTC(b, Tm, dec.output_layer.weight.shape[0], rec.ctc_beam, beam, dev) if rec.joint_ctc else None
-        self.ngram = rec.ngram_lm.to(dev) if rec.ngram_lm is not None else None     # pinned: the state's key holds its table's address
-        self.cand = None
-        if self.ngram is not None and self.joint is None:
-            self.cand = (new((R, rec.ngram_beam), torch.float32), new((R, rec.ngram_beam), torch.int32))
 
     def load_memory(self, memory, memory_mask):
         """Project the encoder memory to cross-attention K|V once per utterance and layer
@@ -759,12 +790,8 @@ class CachedBeamState:
             m_kv = ops.linear(memory, a.vk_proj.weight, a.vk_proj.bias, out_dtype=adt)
             kv.copy_(torch.cat((m_kv, m_kv), dim=-1) if a.share_vk_proj else m_kv)
         self.mem_mask.copy_(memory_mask.reshape(self.b, self.Tm))
-        self.preds[0].fill_(EOS)
-        self.preds[0][:, 0] = BOS
-        self.scores[0].copy_(self.score0)
-        self.flags[0].zero_()
+        self.reset()
         self.pos[0].zero_()
-        self.n_fin.zero_()       # incl. the prune kernel's arrival word: a launch aborted mid-step would leave it poisoned for every later batch
 
     @staticmethod
     def _close(blk, concat_linear, norm, x, a, ctx):
@@ -884,26 +911,21 @@ class CachedBeamState:
             L.check(lib.otr_dec_ln(C.byref(chains[0].ln), self.R, st), 'otr_dec_ln')
         return [c.out() for c in chains]
 
-    def _lm_logits(self, cur):
-        """the LM's scores of the next token for every hypothesis, [R, V or V padded to 8] (speech2text.py:108-113)"""
+    def _lm_hidden(self, cur):
+        """the Transformer LM's rows of the new position for every hypothesis, before its output layer (speech2text.py:108-113)"""
         lm = self.rec.lm
-        if self.lm_recurrent:
-            return lm.logits_last(self.preds[cur], self.pos[cur], out=self.out_lm)     # one LSTM step from zeros on the last token (base.py:35-36)
         y = ops.decode_embed(self.preds[cur], self.pos[cur], lm.embedding.weight)
         if self.fused_lm:
-            y = self._walk([self._lm_chain(y, cur)])[0]
-        else:
-            for blk, cache, tail in zip(lm.blocks, self.lm_cache, self.tail_lm):
-                y = self._layer(y, blk, cache, cur, tail, getattr(blk, 'concat_linear', None), blk.norm2)
-        return _output(self.out_lm, lm.output_project, y)
+            return self._walk([self._lm_chain(y, cur)])[0]
+        for blk, cache, tail in zip(lm.blocks, self.lm_cache, self.tail_lm):
+            y = self._layer(y, blk, cache, cur, tail, getattr(blk, 'concat_linear', None), blk.norm2)
+        return y
 
     def step(self, cur):
         """One beam-search step (recognize/speech2text.py:95-146) reading phase `cur`, writing phase cur^1.  Three routes: paired (the
         LM's layers ride in the decoder's fused launches), forked (the LM on the side stream), no LM."""
-        rec, lib = self.rec, L.load()
-        dec, lm, beam = rec.model.decoder, rec.lm, rec.beam_width
-        main = torch.cuda.current_stream()
-        stream = C.c_void_p(main.cuda_stream)
+        dec, lm = self.rec.model.decoder, self.rec.lm
+        main = torch.cuda.current_stream() if self.side is not None else None      # the forked route's own stream; advance asks for its own
         embed = lambda m: ops.decode_embed(self.preds[cur], self.pos[cur], m.embedding.weight)    # noqa: E731
         lm_logits = None
         if self.paired:
@@ -913,7 +935,7 @@ class CachedBeamState:
             if self.side is not None:
                 self.side.wait_stream(main)                   # fork
                 with torch.cuda.stream(self.side), ops.workspace_lane(self.side_ws):
-                    lm_logits = self._lm_logits(cur)
+                    lm_logits = _lm_logits(lm, self.preds[cur], self.pos[cur], self.out_lm, hidden=lambda: self._lm_hidden(cur))
             x = embed(dec)                                    # after the fork: queued before it, the LM branch would wait for it
             if self.fused_dec:
                 x = self._walk([self._dec_chain(x, cur)])[0]
@@ -923,34 +945,10 @@ class CachedBeamState:
                                     getattr(blk, 'concat_linear2', None))
         if dec.normalize_before:
             x = ops.add_layernorm(x, None, dec.after_norm.weight, dec.after_norm.bias, 0.0, dec.after_norm.eps)
-        V = dec.output_layer.weight.shape[0]
-        logits = _output(self.out_dec, dec.output_layer, x)
-        ld = logits.size(-1)                             # V, or V padded to a multiple of 8 (_PaddedOutput)
+        logits = _output(self.out_dec, dec.output_layer, x)       # [R, V], or V padded to a multiple of 8 (_PaddedOutput)
         if self.side is not None:
             main.wait_stream(self.side)                   # join: the LM's logits are ready
-        ld_lm = lm_logits.size(-1) if lm_logits is not None else V
-        nxt = cur ^ 1
-        if self.joint is not None:
-            j = self.joint
-            j.score(rec, logits, lm_logits, self.preds[cur], cur, self.flags[cur], self.k_score, self.k_idx, pos=self.pos[cur])
-            L.check(lib.otr_beam_prune_cached_joint(_ptr(self.k_score), _ptr(self.k_idx), _ptr(self.scores[cur]), _ptr(self.flags[cur]),
-                                                    _ptr(self.preds[cur]), self.ldp, self.b, beam, EOS, _ptr(self.pos[cur]), _ptr(self.pos[nxt]),
-                                                    _ptr(self.anc[cur]), _ptr(self.anc[nxt]), self.maxlen, _ptr(self.scores[nxt]),
-                                                    _ptr(self.flags[nxt]), _ptr(self.preds[nxt]), _ptr(self.n_fin[nxt]), _ptr(j.k_src),
-                                                    _ptr(j.jsrc[nxt]), stream), 'otr_beam_prune_cached_joint')
-            return
-        if self.cand is not None:                         # the n-gram: pre-beam + addend + select in otr_beam_topk's place, one chain
-            ops.joint_prebeam(logits, lm_logits, 1.0, float(rec.lm_weight or 0.0), rec.ngram_beam, V, *self.cand)
-            ops.ngram_score_candidates(self.ngram, self.preds[cur], self.cand[1], self.cand[0], rec.alpha, rec.beta, EOS, pos=self.pos[cur],
-                                       flags=self.flags[cur], beam=beam, cand_out=self.cand[0], k_score=self.k_score, k_idx=self.k_idx)
-        else:
-            L.check(lib.otr_beam_topk(_ptr(logits), ld, _ptr(lm_logits), ld_lm, float(rec.lm_weight or 0.0), self.R, V, beam,
-                                      _ptr(self.k_score), _ptr(self.k_idx), stream), 'otr_beam_topk')
-        L.check(lib.otr_beam_prune_cached(_ptr(self.k_score), _ptr(self.k_idx), _ptr(self.scores[cur]),
-                                          _ptr(self.flags[cur]), _ptr(self.preds[cur]), self.ldp, self.b, beam, EOS,
-                                          _ptr(self.pos[cur]), _ptr(self.pos[nxt]), _ptr(self.anc[cur]),
-                                          _ptr(self.anc[nxt]), self.maxlen, _ptr(self.scores[nxt]), _ptr(self.flags[nxt]),
-                                          _ptr(self.preds[nxt]), _ptr(self.n_fin[nxt]), stream), 'otr_beam_prune_cached')
+        self.advance(logits, lm_logits, cur, pos=self.pos, anc=self.anc, maxlen=self.maxlen)
 
     def _launch(self, cur):
         if not self.rec.use_hipgraph:
@@ -1022,37 +1020,54 @@ class CTCRecognizer(Recognizer):
         self.beam_width, self.mode, self.ngram_lm = beam_width, mode, ngram_lm
         self.alpha, self.beta, self.cutoff_top_n = alpha, beta, cutoff_top_n
 
-    @torch.no_grad()
-    def recognize_greedy(self, inputs, inputs_mask):
+    def _encode(self, inputs, inputs_mask):
         x, mask, _ = self.model.frontend.inference(inputs, inputs_mask, None)
         memory, memory_mask, _ = self.model.encoder(x, mask)
-        logits = self.model.assistor.compute_logits(memory)                 # [B,T',V]; argmax(log_softmax) == argmax
+        return memory, memory_mask
+
+    def _greedy(self, memory, memory_mask):
+        """the greedy decode of the CTC head's logits (no look-ahead; argmax(log_softmax) == argmax): the per-frame arg-max on the
+        device, repeats and PAD collapsed on the host.  Returns (lists, logits [B, T', V], frames [B])"""
+        logits = self.model.assistor.compute_logits(memory)
         B, T, V = logits.shape
         best_s = torch.empty((B * T, 1), dtype=torch.float32, device=logits.device)
         best_i = torch.empty((B * T, 1), dtype=torch.long, device=logits.device)
         L.check(L.load().otr_beam_topk(_ptr(logits), V, None, 0, 0.0, B * T, V, 1, _ptr(best_s), _ptr(best_i),
                                        C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'otr_beam_topk')
-        best = best_i.view(B, T).cpu()
-        length = memory_mask.sum(-1).cpu()
-        results = []
+        length = memory_mask.sum(-1)
+        best, n = best_i.view(B, T).cpu(), length.cpu()
+        lists = []
         for b in range(B):
             pred, last_k = [], PAD
-            for i in range(int(length[b])):
-                k = int(best[b, i])
+            for k in best[b, :int(n[b])].tolist():
                 if k != last_k and k != PAD:
                     pred.append(k)
                 last_k = k
-            results.append(pred)
-        return results
+            lists.append(pred)
+        return lists, logits, length
+
+    @staticmethod
+    def _best_lists(tokens, out_len):
+        """the 1-best of the beam as host lists"""
+        best, n = tokens[:, 0].cpu(), out_len[:, 0].cpu()
+        return [best[b, :int(n[b])].tolist() for b in range(best.size(0))]
+
+    @staticmethod
+    def _padded(lists, dev):
+        """host lists -> (tokens int64 [B, width >= 1] padded with PAD, lengths int32 [B]) on `dev`"""
+        width = max([len(p) for p in lists] + [1])
+        tokens = torch.tensor([p + [PAD] * (width - len(p)) for p in lists], dtype=torch.long)
+        return tokens.to(dev), torch.tensor([len(p) for p in lists], dtype=torch.int32).to(dev)
+
+    @torch.no_grad()
+    def recognize_greedy(self, inputs, inputs_mask):
+        return self._greedy(*self._encode(inputs, inputs_mask))[0]
 
     @torch.no_grad()
     def recognize_beam(self, inputs, inputs_mask):
-        x, mask, _ = self.model.frontend.inference(inputs, inputs_mask, None)
-        memory, memory_mask, _ = self.model.encoder(x, mask)
+        memory, memory_mask = self._encode(inputs, inputs_mask)
         log_probs, length = self.model.assistor.inference(memory, memory_mask)      # look-ahead conv + log_softmax, f32
-        tokens, out_len = self._beam(log_probs, length)
-        best, n = tokens[:, 0].cpu(), out_len[:, 0].cpu()
-        return [best[b, :int(n[b])].tolist() for b in range(best.size(0))]
+        return self._best_lists(*self._beam(log_probs, length))
 
     def _beam(self, log_probs, length, with_scores=False):
         """the beam of the CTC head's log-probs, with the n-gram LM fused in where one was given: (tokens, out_len[, scores])"""
@@ -1065,20 +1080,15 @@ class CTCRecognizer(Recognizer):
     def recognize_tokens(self, inputs, inputs_mask):
         """recognize() as device tensors (tokens int64 [B, 1, L], lengths int32 [B, 1], scores f32 [B, 1]) for ops.edit_distance /
         evaluate.ErrorRateMeter; translate(tokens[b, 0, :lengths[b, 0]]) gives recognize()'s strings.  Beam mode: the search's own
-        outputs narrowed to the 1-best, nothing goes through the host.  Greedy mode: the collapse of repeats and blanks is the existing
-        host loop of recognize_greedy, its lists padded with PAD and uploaded (one host round trip per batch); the score is 0."""
+        outputs narrowed to the 1-best, nothing goes through the host.  Greedy mode: the collapse of repeats and blanks is the host
+        loop of _greedy, its lists padded with PAD and uploaded (one host round trip per batch); the score is 0."""
+        memory, memory_mask = self._encode(inputs, inputs_mask)
         if self.mode == 'beam':
-            x, mask, _ = self.model.frontend.inference(inputs, inputs_mask, None)
-            memory, memory_mask, _ = self.model.encoder(x, mask)
             log_probs, length = self.model.assistor.inference(memory, memory_mask)
             tokens, out_len, scores = self._beam(log_probs, length, with_scores=True)
             return tokens[:, :1], out_len[:, :1].to(torch.int32), scores[:, :1].float()
-        lists = self.recognize_greedy(inputs, inputs_mask)
-        B, width = len(lists), max([len(p) for p in lists] + [1])
-        tokens = torch.tensor([p + [PAD] * (width - len(p)) for p in lists], dtype=torch.long).view(B, 1, width)
-        lengths = torch.tensor([len(p) for p in lists], dtype=torch.int32).view(B, 1)
-        dev = inputs.device
-        return tokens.to(dev), lengths.to(dev), torch.zeros((B, 1), dtype=torch.float32, device=dev)
+        tokens, lengths = self._padded(self._greedy(memory, memory_mask)[0], inputs.device)
+        return tokens.unsqueeze(1), lengths.unsqueeze(1), torch.zeros((tokens.size(0), 1), dtype=torch.float32, device=inputs.device)
 
     def recognize(self, inputs, inputs_mask):
         if self.mode == 'beam':
@@ -1107,8 +1117,7 @@ class CTCRecognizer(Recognizer):
         """CTC forced alignment of known transcripts: `labels` [B, max_tgt] unit ids without BOS / EOS, `labels_length` [B] their counts
         (at most 127).  Per utterance a list of (unit, start_frame, end_frame, logp): the encoder frames [start, end) the most probable
         CTC path gives the unit, and the unit's log-probs summed over them; frames_to_seconds() turns a frame into a time."""
-        x, mask, _ = self.model.frontend.inference(inputs, inputs_mask, None)
-        memory, memory_mask, _ = self.model.encoder(x, mask)
+        memory, memory_mask = self._encode(inputs, inputs_mask)
         _, spans, label_logp, score = self.model.assistor.align(memory, memory_mask, labels, labels_length)
         return self._span_lists(labels, labels_length, spans, label_logp, score)
 
@@ -1117,37 +1126,18 @@ class CTCRecognizer(Recognizer):
         """recognize() with time stamps (what ctcdecode's `timesteps` give the reference's users): one encoder pass, greedy or beam
         decoding as `mode` says, then the 1-best aligned on the log-probs it was decoded from.  Returns (texts, per-utterance lists of
         (unit, start_frame, end_frame, logp)); the units of a list, read in order, are the words of its text."""
-        x, mask, _ = self.model.frontend.inference(inputs, inputs_mask, None)
-        memory, memory_mask, _ = self.model.encoder(x, mask)
-        blank = self.model.assistor.blank
+        memory, memory_mask = self._encode(inputs, inputs_mask)
         if self.mode == 'beam':
             log_probs, length = self.model.assistor.inference(memory, memory_mask)
-            tokens, out_len = self._beam(log_probs, length)       # the alignment below runs on the acoustic log-probs alone
-            best, n = tokens[:, 0].cpu(), out_len[:, 0].cpu()
-            preds = [best[b, :int(n[b])].tolist() for b in range(best.size(0))]
-        else:                                                                   # recognize_greedy's logits: no look-ahead
-            logits = self.model.assistor.compute_logits(memory)
-            B, T, V = logits.shape
-            best_s = torch.empty((B * T, 1), dtype=torch.float32, device=logits.device)
-            best_i = torch.empty((B * T, 1), dtype=torch.long, device=logits.device)
-            L.check(L.load().otr_beam_topk(_ptr(logits), V, None, 0, 0.0, B * T, V, 1, _ptr(best_s), _ptr(best_i),
-                                           C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'otr_beam_topk')
-            log_probs, length = ops.log_softmax(logits), memory_mask.sum(-1)
-            best, n = best_i.view(B, T).cpu(), length.cpu()
-            preds = []
-            for b in range(best.size(0)):
-                pred, last_k = [], PAD
-                for k in best[b, :int(n[b])].tolist():
-                    if k != last_k and k != PAD:
-                        pred.append(k)
-                    last_k = k
-                preds.append(pred)
-        width = max(1, max(len(p) for p in preds))
-        if width > ops.CTC_ALIGN_MAX_TGT:
-            raise ValueError('recognize_with_times: a 1-best of %d units, the alignment takes at most %d' % (width, ops.CTC_ALIGN_MAX_TGT))
-        labels = torch.tensor([p + [PAD] * (width - len(p)) for p in preds], dtype=torch.int64, device=log_probs.device)
-        labels_length = torch.tensor([len(p) for p in preds], dtype=torch.int32, device=log_probs.device)
-        _, spans, label_logp, score = ops.ctc_forced_align(log_probs, length, labels, labels_length, blank=blank)
+            preds = self._best_lists(*self._beam(log_probs, length))       # the alignment below runs on the acoustic log-probs alone
+        else:
+            preds, logits, length = self._greedy(memory, memory_mask)
+            log_probs = ops.log_softmax(logits)
+        labels, labels_length = self._padded(preds, log_probs.device)
+        if labels.size(1) > ops.CTC_ALIGN_MAX_TGT:
+            raise ValueError('recognize_with_times: a 1-best of %d units, the alignment takes at most %d'
+                             % (labels.size(1), ops.CTC_ALIGN_MAX_TGT))
+        _, spans, label_logp, score = ops.ctc_forced_align(log_probs, length, labels, labels_length, blank=self.model.assistor.blank)
         return self.translate(preds), self._span_lists(labels, labels_length, spans, label_logp, score)
 
 

@@ -474,3 +474,40 @@ def test_cached_search_with_the_lagged_stop_test_is_the_synchronous_search(mode)
         recognize._DECODE_LAGGED_STOP = True
         recognize.CachedBeamState.run = run0
         ops.set_compute_dtype('bf16')
+
+
+@pytest.mark.parametrize('joint,ngram', [(False, False), (True, False), (False, True), (True, True)])
+@pytest.mark.parametrize('lm_kind', ['none', 'transformer', 'recurrent'])
+def test_both_loops_take_the_same_steps_fp32(golden, lm_kind, joint, ngram):
+    """the re-forward loop and the cached loop (eager: with `trace` set its run syncs after every step) hand the shared scoring tail
+    the same state: after EVERY step the same prefixes and, to the file's fp32 bound of cached against reference, the same cumulative
+    scores, and both stop at the same step -- with and without each LM, the joint CTC scores and the n-gram's addend"""
+    from opentransformer_amd import ops
+    from opentransformer_amd.recognize import LanguageModel, SpeechToTextRecognizer
+    from tests import ngram_attn_cases as cs
+    g = golden('c1_decode.npz')
+    try:
+        model, lm = load_models(g, 'fp32')
+        if lm_kind == 'recurrent':
+            lm = LanguageModel['rnn_lm'](syn.rnn_lm_config(100, hidden_size=64, num_layers=2))
+            syn.fill_state_dict_(lm.state_dict(), 4321)
+            lm = lm.to(DEV).eval()
+        x, m = torch.from_numpy(g['inputs']).to(DEV), torch.from_numpy(g['mask']).to(DEV)
+        kw = dict(lm=lm if lm_kind != 'none' else None, lm_weight=0.3, ctc_weight=0.3, beam_width=4, nbest=4, max_len=8, joint_ctc=joint,
+                  idx2unit={i: str(i) for i in range(100)})
+        if ngram:
+            kw.update(ngram_lm=cs.ngram(5)[0], alpha=0.5, beta=1.0)
+        traces = {}
+        for cache in (False, True):
+            rec = SpeechToTextRecognizer(model, apply_cache=cache, **kw)
+            rec.use_hipgraph = False
+            rec.trace = traces[cache] = []
+            rec.recognize(x, m)
+        assert len(traces[False]) == len(traces[True]) >= 1, (len(traces[False]), len(traces[True]))
+        for step, ((p0, s0), (p1, s1)) in enumerate(zip(traces[False], traces[True]), 1):
+            assert p0.shape == (x.size(0) * 4, step + 1)
+            assert torch.equal(p0, p1), step
+            print(lm_kind, joint, ngram, 'step', step, 'max |d score| %.3g' % float((s0 - s1)[torch.isfinite(s0)].abs().max()))
+            torch.testing.assert_close(s1, s0, rtol=2e-4, atol=2e-4, msg=lambda t: 'step %d: %s' % (step, t))
+    finally:
+        ops.set_compute_dtype('bf16')
