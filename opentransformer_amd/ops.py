@@ -309,6 +309,51 @@ def grad_target(p):
     return None
 
 
+# A backward pass hands every parameter gradient to one of the three functions below and puts what they return into its autograd
+# tuple: the tensor when `ref` has no in-place buffer, None when the gradient was accumulated into the buffer -- now, or (with
+# _wq['on'], inside an autograd pass) by the grouped launches at the end of backward: linear_wgrad_raw / colsum_raw decide that.
+def sink_wgrad(dy2, x2, ref, w_like=None):
+    """the weight gradient dy2^T x2 of parameter `ref`"""
+    gt = grad_target(ref)
+    dw = linear_wgrad_raw(dy2, x2, w_like, out=gt)
+    return None if gt is not None else dw
+
+
+def sink_colsum(a2, ref, defer=True):
+    """the column sums of a2 [M, N] as the gradient of the N-element parameter `ref` (None: no such parameter, nothing is launched).
+    A buffer of more than one dimension is written as its flat view; a returned tensor is [N] whatever the shape of `ref`."""
+    if ref is None:
+        return None
+    gt = grad_target(ref)
+    if gt is not None and gt.dim() != 1:
+        gt = gt.view(-1)
+    db = colsum_raw(a2, out=gt, defer=defer)
+    return None if gt is not None else db
+
+
+def sink_colsum_blocks(part, width, blocks, refs, summed=False):
+    """part [rows, n * width]: a kernel's per-workgroup partial sums.  Columns [c * width, (c + 1) * width) with c = blocks[i] (or
+    [c0 * width, c1 * width) with (c0, c1) = blocks[i]) are the gradient of refs[i]; entries of refs that are None are skipped.
+    Returns the list for the autograd tuple.
+    summed=False: one sink_colsum per block.
+    summed=True (the kernels with five and seven sums per row): that only where every block would be queued for the grouped launch;
+    otherwise ONE part.sum(0), whose slices are added to the gradient buffers (every ref has one) or returned."""
+    cols = [(c, c + 1) if isinstance(c, int) else c for c in blocks]
+    if summed:
+        inplace = all(grad_target(r) is not None for r in refs if r is not None)
+        if not (inplace and _wq['on'] and _in_backward() and width % 4 == 0):
+            sums = part.sum(0)
+            out = []
+            for (c0, c1), r in zip(cols, refs):
+                s = sums[c0 * width:c1 * width] if r is not None else None
+                if s is not None and inplace:
+                    grad_target(r).add_(s)
+                    s = None
+                out.append(s)
+            return out
+    return [sink_colsum(part[:, c0 * width:c1 * width], r) if r is not None else None for (c0, c1), r in zip(cols, refs)]
+
+
 # ---------------------------------------------------------------------------------------- split-K workspace
 _WS_BYTES = 64 << 20
 
@@ -855,6 +900,8 @@ def colsum_raw(a2, out=None, defer=True):
         return out
     if out is None:
         out = torch.empty((N,), dtype=torch.float32, device=a2.device)
+    if a2.data_ptr() % 16 != 0:       # otr_colsum wants a 16-byte aligned base: a column block that starts elsewhere is copied out
+        a2 = a2.clone(memory_format=torch.contiguous_format)
     L.check(L.load().otr_colsum(_p(a2), _code(a2.dtype), M, N, a2.stride(0), _p(out), int(acc), _stream()), 'otr_colsum')
     return out
 
@@ -1078,10 +1125,9 @@ class LinearFn(torch.autograd.Function):
                 dx = linear_dgrad_raw(dy2, wc, ctx.xdtype, out=skip).view(ctx.xshape)
         dw = None
         if ctx.needs_input_grad[1]:
-            gt = grad_target(ctx.w_ref) if ctx.perm is None else None
-            if gt is not None:
-                linear_wgrad_raw(dy2, x2, wc, out=gt)
-            elif (ctx.perm is not None and dy2.dtype == half_dtype() and x2.dtype == half_dtype() and _wq['on'] and _in_backward()
+            if ctx.perm is None:
+                dw = sink_wgrad(dy2, x2, ctx.w_ref, wc)
+            elif (dy2.dtype == half_dtype() and x2.dtype == half_dtype() and _wq['on'] and _in_backward()
                   and getattr(ctx.w_ref, '_otr_regroup_grad', None) is not None and grad_target(ctx.w_ref) is not None):
                 # 16-bit operands: the product joins the grouped 256-wide launch, accumulating into the KERNEL-order staging image of
                 # this weight's gradient (zeroed with the gradient buffer); behind that launch one strided add regroups it into the
@@ -1095,23 +1141,17 @@ class LinearFn(torch.autograd.Function):
                 # replay of a graph captured without the clear), with no host-side state baked into anything
                 _wq['post'].append(lambda gt_w=gt_w, stage=stage, C_=C_, F_=F_: regroup_add(gt_w, stage, stage.shape[0], C_, F_, True))
             else:
-                dw = linear_wgrad_raw(dy2, x2, wc)
-                if ctx.perm is not None:
-                    C_, F_ = ctx.perm
-                    dw = dw.view(-1, F_, C_).permute(0, 2, 1)
-                    gt = grad_target(ctx.w_ref)
-                    if gt is not None:       # regrouped back while it is added to the gradient buffer: one launch, not copy + add
-                        gt.view(-1, C_, F_).add_(dw)
-                        dw = None
-                    else:
-                        dw = dw.reshape(dw.shape[0], C_ * F_)
+                C_, F_ = ctx.perm
+                dw = linear_wgrad_raw(dy2, x2, wc).view(-1, F_, C_).permute(0, 2, 1)
+                gt = grad_target(ctx.w_ref)
+                if gt is not None:       # regrouped back while it is added to the gradient buffer: one launch, not copy + add
+                    gt.view(-1, C_, F_).add_(dw)
+                    dw = None
+                else:
+                    dw = dw.reshape(dw.shape[0], C_ * F_)
         db = None
         if ctx.has_bias and ctx.needs_input_grad[2] and not ctx.defer_bias:
-            gt = grad_target(ctx.b_ref)
-            if gt is not None:
-                colsum_raw(dy2, out=gt)
-            else:
-                db = colsum_raw(dy2)
+            db = sink_colsum(dy2, ctx.b_ref)
         return dx, dw, db, None, None, None, None, None, None
 
 
@@ -1373,10 +1413,7 @@ class CrossKVAllFn(torch.autograd.Function):
         n2 = ws[0].shape[0]
         for i, (w, b) in enumerate(zip(ws, bs)):
             sl = d2[:, i * n2:(i + 1) * n2]
-            gw, gb = grad_target(w), grad_target(b)
-            dw = linear_wgrad_raw(sl, m2, None, out=gw)
-            db = colsum_raw(sl, out=gb)
-            grads += [None if gw is not None else dw, None if gb is not None else db]
+            grads += [sink_wgrad(sl, m2, w), sink_colsum(sl, b)]
         return (dmem.view(ctx.mshape), None, *grads)
 
 
@@ -1429,6 +1466,55 @@ class CrossAttentionSliceFn(torch.autograd.Function):
 
 
 # ---------------------------------------------------------------------------------------- add + LayerNorm
+def _layernorm_bwd(cfg, dy2, saved, skip, dx, da, refs, staged=False, more=None):
+    """The backward launch of y = LayerNorm(x + dropout(a)) with the delivery of its three parameter gradients.  cfg: the fields of
+    otr_ln_desc_t behind (M, d); saved = (z, mean, rstd, gamma, seed); dx [M, d] receives skip + the input gradient, da (or None) the
+    branch's; refs = (gamma, beta, the bias of the branch's last Linear or None).  Returns their three autograd entries.
+    In-place gradient buffers for every ref + deferred reductions: the kernel writes per-workgroup partial sums and the three column
+    sums join the grouped launch at the end of backward (no atomics, deterministic).  Otherwise the kernel adds into fp32 rows it is
+    handed: the gradient buffers themselves, or zero-filled rows that autograd receives.
+    staged (FfnLnFn: the entry without a skip operand, any d): those rows are always zero-filled temporaries, added to the buffers or
+    returned afterwards.  more: partial sums of the same three gradients left by another launch (LnOutLink), sunk ahead of these."""
+    z, mean, rstd, gamma, seed = saved
+    M, d = dx.shape
+    lib, dev = L.load(), dx.device
+    desc = L.LnDesc(M, d, *cfg)
+    targets = [grad_target(r) for r in refs]
+    inplace = all(t is not None for t, r in zip(targets, refs) if r is not None)
+    ret, dgb = [None, None, None], None
+    gg, gb, gab = targets
+    if not staged:
+        if gg is None or gb is None:
+            dgb = torch.zeros((2, d), dtype=torch.float32, device=dev)
+            gg, gb = ret[0], ret[1] = dgb[0], dgb[1]
+        if refs[2] is not None and gab is None:
+            gab = ret[2] = torch.zeros((d,), dtype=torch.float32, device=dev)
+    part = None
+    if inplace and _wq['on'] and _in_backward() and (staged or d % 4 == 0):
+        part = torch.empty((lib.otr_add_layernorm_bwd_partial_rows(M), 3 * d), dtype=torch.float32, device=dev)
+    elif staged:
+        dgb = torch.zeros((3, d), dtype=torch.float32, device=dev)
+    if staged:
+        assert skip is None
+        L.check(lib.otr_add_layernorm_bwd(C.byref(desc), _p(dy2), _p(z), _p(mean), _p(rstd), _p(gamma), _p(seed), _p(dx), _p(da),
+                                          _p(dgb[0]) if dgb is not None else None, _p(dgb[1]) if dgb is not None else None,
+                                          _p(dgb[2]) if dgb is not None else None, _p(part), _stream()), 'otr_add_layernorm_bwd')
+    else:
+        L.check(lib.otr_add_layernorm_bwd_skip(C.byref(desc), _p(dy2), _p(z), _p(mean), _p(rstd), _p(gamma), _p(seed), _p(skip), _p(dx),
+                                               _p(da), _p(gg), _p(gb), _p(gab), _p(part), _stream()), 'otr_add_layernorm_bwd_skip')
+    if more is not None:
+        sink_colsum_blocks(more, d, (0, 1, 2), refs)
+    if part is not None:
+        sink_colsum_blocks(part, d, (0, 1, 2), refs)
+    elif staged:
+        for i, t in enumerate(targets):
+            if t is not None:
+                t.add_(dgb[i])
+            else:
+                ret[i] = dgb[i]
+    return ret
+
+
 class AddLayerNormFn(torch.autograd.Function):
     """y = LayerNorm(x + dropout(a)) (post-norm residual: encoder/transformer.py:54-56,61-63)."""
 
@@ -1477,42 +1563,18 @@ class AddLayerNormFn(torch.autograd.Function):
         dy2 = dy.reshape(-1, d).contiguous()
         dx = torch.empty_like(dy2)
         da = torch.empty((M, d), dtype=adt, device=dy.device) if adt is not None else None
-        gg, gb = grad_target(ctx.g_ref), grad_target(ctx.b_ref)
-        inplace = gg is not None and gb is not None
-        if not inplace:
-            dgb = torch.zeros((2, d), dtype=torch.float32, device=dy.device)
-            gg, gb = dgb[0], dgb[1]
-        gab, dab = None, None
         want_ab = ctx.ab_ref is not None and da is not None and ctx.needs_input_grad[6]
-        if want_ab:
-            gab = grad_target(ctx.ab_ref)
-            if gab is None:
-                gab = dab = torch.zeros((d,), dtype=torch.float32, device=dy.device)
-        desc = L.LnDesc(M, d, _code(adt) if adt is not None else L.OTR_F32, eps, p_drop, off)
-        part = None
-        if inplace and dab is None and _wq['on'] and _in_backward() and d % 4 == 0:
-            # in-place gradient buffers + deferred reductions: the kernel writes per-workgroup partial sums and the
-            # three column sums join the grouped launch at the end of backward (no atomics, deterministic)
-            nrow = L.load().otr_add_layernorm_bwd_partial_rows(M)
-            part = torch.empty((nrow, 3 * d), dtype=torch.float32, device=dy.device)
         skip = None
         if isinstance(ctx.link, PreNormLink) and ctx.link.buf is not None:     # gradient through the skip connection of x + f(LN(x))
             skip, ctx.link.buf = ctx.link.buf, None
-        L.check(L.load().otr_add_layernorm_bwd_skip(C.byref(desc), _p(dy2), _p(z), _p(mean), _p(rstd), _p(gamma), _p(seed),
-                                                    _p(skip), _p(dx), _p(da), _p(gg), _p(gb), _p(gab), _p(part), _stream()),
-                'otr_add_layernorm_bwd')
-        if part is not None:
-            colsum_raw(part[:, :d], out=gg)
-            colsum_raw(part[:, d:2 * d], out=gb)
-            if want_ab:
-                colsum_raw(part[:, 2 * d:], out=gab)
+        dgamma, dbeta, dab = _layernorm_bwd((_code(adt) if adt is not None else L.OTR_F32, eps, p_drop, off), dy2, (z, mean, rstd, gamma, seed),
+                                            skip, dx, da, (ctx.g_ref, ctx.b_ref, ctx.ab_ref if want_ab else None))
         dx_ret = dx.view(xshape)
         if isinstance(ctx.link, ResidualLink) and ctx.link.armed and ctx.needs_input_grad[0]:
             ctx.link.buf = dx           # the branch's first Linear adds its input gradient into this and returns the sum
             _park(ctx.link)
             dx_ret = None
-        return (dx_ret, (da.view(ashape) if da is not None else None),
-                None if inplace else gg, None if inplace else gb, None, None, dab, None)
+        return dx_ret, (da.view(ashape) if da is not None else None), dgamma, dbeta, None, None, dab, None
 
 
 class ResidualLnFn(torch.autograd.Function):
@@ -1583,48 +1645,23 @@ class ResidualLnFn(torch.autograd.Function):
         skip = dz.reshape(-1, d).contiguous() if dz is not None else None
         dx = torch.empty((M, d), dtype=torch.float32, device=z.device)
         da = torch.empty((M, d), dtype=adt, device=z.device)
-        refs = (ctx.g_ref, ctx.b_ref) + ((ctx.g2_ref, ctx.b2_ref) if two else ())
-        targets = [grad_target(r) for r in refs]
-        inplace = all(t is not None for t in targets)
-        lib = L.load()
-        desc = L.LnDesc(M, d, _code(adt), eps, p_drop, off, scale, ctx.a_mask.data_ptr() if ctx.a_mask is not None else None, _code(dy2.dtype))
-        ret = [None] * len(refs)
+        cfg = (_code(adt), eps, p_drop, off, scale, ctx.a_mask.data_ptr() if ctx.a_mask is not None else None, _code(dy2.dtype))
         if two:
+            lib = L.load()
+            desc = L.LnDesc(M, d, *cfg)
             part = torch.empty((lib.otr_add_layernorm_bwd_partial_rows(M), 5 * d), dtype=torch.float32, device=z.device)
             L.check(lib.otr_add_layernorm2_bwd(C.byref(desc), _p(dy2), _p(z), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(mean2), _p(rstd2),
                                                _p(gamma2), _p(seed), _p(skip), _p(dx), _p(da), _p(part), _stream()), 'otr_add_layernorm2_bwd')
-            cols = (0, 1, 3, 4)                       # dgamma | dbeta | (da sums) | dgamma2 | dbeta2
-            if inplace and _wq['on'] and _in_backward() and d % 4 == 0:
-                for t, c in zip(targets, cols):
-                    colsum_raw(part[:, c * d:(c + 1) * d], out=t)
-            else:
-                sums = part.sum(0)
-                for i, (t, c) in enumerate(zip(targets, cols)):
-                    if inplace:
-                        t.add_(sums[c * d:(c + 1) * d])
-                    else:
-                        ret[i] = sums[c * d:(c + 1) * d]
+            # dgamma | dbeta | (da sums) | dgamma2 | dbeta2
+            ret = sink_colsum_blocks(part, d, (0, 1, 3, 4), (ctx.g_ref, ctx.b_ref, ctx.g2_ref, ctx.b2_ref), summed=True)
         else:
-            gg, gb = targets
-            if not inplace:
-                dgb = torch.zeros((2, d), dtype=torch.float32, device=z.device)
-                gg, gb = dgb[0], dgb[1]
-                ret = [gg, gb]
-            part = None
-            if inplace and _wq['on'] and _in_backward() and d % 4 == 0:
-                part = torch.empty((lib.otr_add_layernorm_bwd_partial_rows(M), 3 * d), dtype=torch.float32, device=z.device)
-            L.check(lib.otr_add_layernorm_bwd_skip(C.byref(desc), _p(dy2), _p(z), _p(mean), _p(rstd), _p(gamma), _p(seed), _p(skip),
-                                                   _p(dx), _p(da), _p(gg), _p(gb), None, _p(part), _stream()), 'otr_add_layernorm_bwd')
-            if part is not None:
-                colsum_raw(part[:, :d], out=gg)
-                colsum_raw(part[:, d:2 * d], out=gb)
+            ret = _layernorm_bwd(cfg, dy2, (z, mean, rstd, gamma, seed), skip, dx, da, (ctx.g_ref, ctx.b_ref, None))[:2] + [None, None]
         dx_ret = dx.view(xshape)
         if ctx.link is not None:
             ctx.link.buf = dx
             _park(ctx.link)
             dx_ret = None
-        g2 = (ret[2], ret[3]) if two else (None, None)
-        return dx_ret, da.view(ashape), None, None, ret[0], ret[1], None, None, g2[0], g2[1], None, None
+        return dx_ret, da.view(ashape), None, None, ret[0], ret[1], None, None, ret[2], ret[3], None, None
 
 
 class ResidualLn3Fn(torch.autograd.Function):
@@ -1689,20 +1726,8 @@ class ResidualLn3Fn(torch.autograd.Function):
         L.check(lib.otr_add_layernorm3_bwd(C.byref(desc), _p(g2), _p(g3), _code(g3.dtype), _p(z), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(mean2), _p(rstd2),
                                            _p(gamma2), _p(beta2), _p(mean3), _p(rstd3), _p(gamma3), _p(seed), _p(skip), _p(dx), _p(da), _p(part),
                                            _stream()), 'otr_add_layernorm3_bwd')
-        targets = [grad_target(r) for r in ctx.refs]
-        inplace = all(t is not None for t in targets)
-        cols = (0, 1, 3, 4, 5, 6)                     # dgamma | dbeta | (da sums) | dgamma2 | dbeta2 | dgamma3 | dbeta3
-        ret = [None] * 6
-        if inplace and _wq['on'] and _in_backward() and d % 4 == 0:
-            for t, c in zip(targets, cols):
-                colsum_raw(part[:, c * d:(c + 1) * d], out=t)
-        else:
-            sums = part.sum(0)
-            for i, (t, c) in enumerate(zip(targets, cols)):
-                if inplace:
-                    t.add_(sums[c * d:(c + 1) * d])
-                else:
-                    ret[i] = sums[c * d:(c + 1) * d]
+        # dgamma | dbeta | (da sums) | dgamma2 | dbeta2 | dgamma3 | dbeta3
+        ret = sink_colsum_blocks(part, d, (0, 1, 3, 4, 5, 6), ctx.refs, summed=True)
         return dx.view(xshape), da.view(ashape), None, None, ret[0], ret[1], None, ret[2], ret[3], ret[4], ret[5], None
 
 
@@ -1798,27 +1823,14 @@ class ProjLnFn(torch.autograd.Function):
                            lambda: L.load().otr_ln_bwd_proj(_p(dy2), _p(z), _p(mean), _p(rstd), _p(gamma), _p(seed), _p(packs[1]), _p(dx),
                                                             _p(da), _p(dc), dc.stride(0), _p(part), M, d, p_drop, off, _stream())),
                     'otr_ln_bwd_proj')
-        outs = []
-        for k, ref in ((0, g_ref), (1, b_ref), (2, b)):
-            if ref is None:
-                outs.append(None)
-                continue
-            gt = grad_target(ref)
-            sl = part[:, k * d:(k + 1) * d]
-            if gt is not None:
-                colsum_raw(sl, out=gt)
-                outs.append(None)
-            else:
-                outs.append(colsum_raw(sl))
-        dgamma, dbeta, dbias = outs
-        gw = grad_target(w)
-        dw = linear_wgrad_raw(da, c2, w, out=gw)
+        dgamma, dbeta, dbias = sink_colsum_blocks(part, d, (0, 1, 2), (g_ref, b_ref, b))
+        dw = sink_wgrad(da, c2, w, w)
         dx_ret = dx.view(xshape)
         if isinstance(ctx.link, ResidualLink) and ctx.link.armed and ctx.needs_input_grad[0]:
             ctx.link.buf = dx           # the branch's first Linear adds its input gradient into this and returns the sum
             _park(ctx.link)
             dx_ret = None
-        return (dx_ret, dc.view(cshape), None if gw is not None else dw, dbias, dgamma, dbeta, None, None, None, None, None)
+        return dx_ret, dc.view(cshape), dw, dbias, dgamma, dbeta, None, None, None, None, None
 
 
 def proj_ln_packs(x, c, w, gamma):
@@ -1896,9 +1908,8 @@ class FeedForwardGLUFn(torch.autograd.Function):
         w1p, b1p, w2p, b2p = ctx.refs
         dy2 = _rows(dy)
         M, F = u.shape
-        gw2, gb2, gw1, gb1 = grad_target(w2p), grad_target(b2p), grad_target(w1p), grad_target(b1p)
-        dw2 = linear_wgrad_raw(dy2, u, w2, out=gw2)
-        db2 = None if ctx.defer_b2 else colsum_raw(dy2, out=gb2)
+        dw2 = sink_wgrad(dy2, u, w2p, w2)
+        db2 = None if ctx.defer_b2 else sink_colsum(dy2, b2p)
         dh = torch.empty_like(h)
         part = None
         if ctx.w2t is not None and dy2.dtype == half_dtype() and h.dtype == dy2.dtype and is_half():
@@ -1919,7 +1930,7 @@ class FeedForwardGLUFn(torch.autograd.Function):
             part = torch.empty((nblk, 2 * F), dtype=torch.float32, device=dy.device)
             L.check(L.load().otr_glu_bwd(_p(h), _p(du), _p(dh), _p(part), _code(h.dtype), M, F, None, int(ctx.h_sig), _stream()),
                     'otr_glu_bwd')
-        db1 = colsum_raw(part, out=gb1)
+        db1 = sink_colsum(part, b1p)
         skip = None
         if ctx.link is not None and ctx.link.buf is not None:
             skip, ctx.link.buf = ctx.link.buf, None
@@ -1927,9 +1938,8 @@ class FeedForwardGLUFn(torch.autograd.Function):
             dx = linear_fwd_raw(dh, ctx.w1t, None, ctx.xdtype, out=skip).view(ctx.xshape)
         else:
             dx = linear_dgrad_raw(dh, w1, ctx.xdtype, out=skip).view(ctx.xshape)
-        dw1 = linear_wgrad_raw(dh, x2, w1, out=gw1)
-        return (dx, None if gw1 is not None else dw1, None if gb1 is not None else db1,
-                None if gw2 is not None else dw2, None if (gb2 is not None or ctx.defer_b2) else db2, None, None, None)
+        dw1 = sink_wgrad(dh, x2, w1p, w1)
+        return dx, dw1, db1, dw2, db2, None, None, None
 
 
 # ---------------------------------------------------------------------------------------- row-block fused FFN sub-layer
@@ -2117,54 +2127,25 @@ class FfnLnFn(torch.autograd.Function):
         w1p, b1p, w2p, b2p, gp, bp = ctx.refs
         P1, _, P3, P4 = ctx.packs
         lib = L.load()
-        gg, gb, gb2 = grad_target(gp), grad_target(bp), grad_target(b2p)
+        refs = (gp, bp, b2p)
         stash = None
         if ctx.olink is not None:
             # `saved` stays: a second backward through a retained graph reaches the linked Linear again (ops.LinearFn.backward)
             stash, ctx.olink.result = ctx.olink.result, None
-        part, dgb = None, None
         if stash is not None and _is_zero_placeholder(dy):
             # the LayerNorm backward already ran in the epilogue of the next layer's q|k|v input-gradient launch (LnOutLink)
             dx, da, part = stash
-            stash = None
+            ret_g, ret_b, ret_b2 = sink_colsum_blocks(part, d, (0, 1, 2), refs)
         else:
             dy2 = dy.reshape(-1, d).contiguous()
             dx = torch.empty_like(dy2)
             da = torch.empty((M, d), dtype=x16.dtype, device=dy.device)
             # LayerNorm backward: dx = skip-connection gradient, da = gradient of the FFN output (dropout mask regenerated)
-            inplace = gg is not None and gb is not None and gb2 is not None
-            desc = L.LnDesc(M, d, _code(da.dtype), eps, p_drop, off)
-            if inplace and _wq['on'] and _in_backward():
-                part = torch.empty((lib.otr_add_layernorm_bwd_partial_rows(M), 3 * d), dtype=torch.float32, device=dy.device)
-            else:
-                dgb = torch.zeros((3, d), dtype=torch.float32, device=dy.device)
-            L.check(lib.otr_add_layernorm_bwd(C.byref(desc), _p(dy2), _p(z), _p(mean), _p(rstd), _p(gamma), _p(seed), _p(dx), _p(da),
-                                              _p(dgb[0]) if dgb is not None else None, _p(dgb[1]) if dgb is not None else None,
-                                              _p(dgb[2]) if dgb is not None else None, _p(part), _stream()), 'otr_add_layernorm_bwd')
+            ret_g, ret_b, ret_b2 = _layernorm_bwd((_code(da.dtype), eps, p_drop, off), dy2, (z, mean, rstd, gamma, seed), None, dx, da, refs,
+                                                  staged=True, more=stash[2] if stash is not None else None)
             if stash is not None:       # y had another consumer besides the linked Linear: add the part that Linear's launch produced
                 dx.add_(stash[0])
                 da = (da.float() + stash[1].float()).to(da.dtype)
-                colsum_raw(stash[2][:, :d], out=gg)
-                colsum_raw(stash[2][:, d:2 * d], out=gb)
-                colsum_raw(stash[2][:, 2 * d:], out=gb2)
-        ret_g = ret_b = ret_b2 = None
-        if part is not None:
-            colsum_raw(part[:, :d], out=gg)
-            colsum_raw(part[:, d:2 * d], out=gb)
-            colsum_raw(part[:, 2 * d:], out=gb2)
-        else:
-            if gg is not None:
-                gg.add_(dgb[0])
-            else:
-                ret_g = dgb[0]
-            if gb is not None:
-                gb.add_(dgb[1])
-            else:
-                ret_b = dgb[1]
-            if gb2 is not None:
-                gb2.add_(dgb[2])
-            else:
-                ret_b2 = dgb[2]
         if ctx.split and hsave is not None:
             # 128-row workgroups, the hidden read back from the forward pass's tiles: dh for the w_1 weight gradient; dx += dh . w_1
             dh = torch.empty((usave.shape[0], 2 * F), dtype=x16.dtype, device=dy.device)[:M]
@@ -2189,25 +2170,19 @@ class FfnLnFn(torch.autograd.Function):
                 L.check(_timed('ffn_bwd_split', {'flops': 6.0 * M * F * d, 'bytes': M * d * (2 + 4 + 4) + M * F * 8 + 6 * F * d},
                                lambda: lib.otr_ffn_bwd_split(_p(da), _p(hsave), _p(P3), _p(P4), _p(dh), _p(dx), _p(dx), _p(scratch), nb,
                                                              _p(sync), sync.numel(), M, F, d, _stream())), 'otr_ffn_bwd_split')
-            gw1, gb1, gw2 = grad_target(w1p), grad_target(b1p), grad_target(w2p)
-            dw1 = linear_wgrad_raw(dh, x16, None, out=gw1)
-            dw2 = linear_wgrad_raw(da, usave[:M], None, out=gw2)
-            db1 = colsum_raw(dh, out=gb1)               # rides along with the w_1 weight-gradient launch (same matrix)
-            return (dx.view(xshape), None if gw1 is not None else dw1, None if gb1 is not None else db1,
-                    None if gw2 is not None else dw2, ret_b2, ret_g, ret_b, None, None, None, None, None, None)
-        # FFN backward with recompute: dh, u for the weight gradients; dx += dh . w_1
-        dh = torch.empty((M, 2 * F), dtype=x16.dtype, device=dy.device)
-        u = torch.empty((M, F), dtype=x16.dtype, device=dy.device)
-        bpart = torch.empty(((M + 31) // 32, 2 * F), dtype=torch.float32, device=dy.device)    # d b_1 per 32-row block
-        L.check(_timed('ffn_bwd', {'flops': 10.0 * M * F * d, 'bytes': M * d * (2 + 2 + 4 + 4) + M * F * 6 + 10 * F * d},
-                       lambda: lib.otr_ffn_bwd(_p(x16), _p(da), _p(P1), _p(b1), _p(P3), _p(P4), _p(dh), _p(u), _p(bpart), _p(dx),
-                                               _p(dx), M, F, d, _stream())), 'otr_ffn_bwd')
-        gw1, gb1, gw2 = grad_target(w1p), grad_target(b1p), grad_target(w2p)
-        dw1 = linear_wgrad_raw(dh, x16, None, out=gw1)
-        dw2 = linear_wgrad_raw(da, u, None, out=gw2)
-        db1 = colsum_raw(bpart, out=gb1)             # per-workgroup column sums of dh, written by the backward kernel
-        return (dx.view(xshape), None if gw1 is not None else dw1, None if gb1 is not None else db1,
-                None if gw2 is not None else dw2, ret_b2, ret_g, ret_b, None, None, None, None, None, None)
+            u, b1_sums = None, dh                      # d b_1 rides along with the w_1 weight-gradient launch (same matrix)
+        else:
+            # FFN backward with recompute: dh, u for the weight gradients; dx += dh . w_1
+            dh = torch.empty((M, 2 * F), dtype=x16.dtype, device=dy.device)
+            u = torch.empty((M, F), dtype=x16.dtype, device=dy.device)
+            b1_sums = torch.empty(((M + 31) // 32, 2 * F), dtype=torch.float32, device=dy.device)    # d b_1 per 32-row block
+            L.check(_timed('ffn_bwd', {'flops': 10.0 * M * F * d, 'bytes': M * d * (2 + 2 + 4 + 4) + M * F * 6 + 10 * F * d},
+                           lambda: lib.otr_ffn_bwd(_p(x16), _p(da), _p(P1), _p(b1), _p(P3), _p(P4), _p(dh), _p(u), _p(b1_sums), _p(dx),
+                                                   _p(dx), M, F, d, _stream())), 'otr_ffn_bwd')
+        dw1 = sink_wgrad(dh, x16, w1p)
+        dw2 = sink_wgrad(da, u if u is not None else usave[:M], w2p)
+        db1 = sink_colsum(b1_sums, b1p)
+        return dx.view(xshape), dw1, db1, dw2, ret_b2, ret_g, ret_b, None, None, None, None, None, None
 
 
 def ffn_add_layernorm(x, w1, b1, w2, b2, gamma, beta, p_drop=0.0, eps=1e-5, defer_ln=False):
@@ -2287,18 +2262,6 @@ def _dec_lnb(dskip, slabs, nslab, saved, gamma, seed, p_drop, dz, da16, partial)
     z, mean, rstd, off = saved
     pv = lambda t: t.data_ptr() if t is not None else None
     return L.DecLnB(pv(dskip), pv(slabs), nslab, pv(z), pv(mean), pv(rstd), pv(gamma), pv(seed), p_drop, off, pv(dz), pv(da16), pv(partial))
-
-
-def _grad_w(dy2, x2, w):
-    gt = grad_target(w)
-    r = linear_wgrad_raw(dy2, x2, None, out=gt)
-    return None if gt is not None else r
-
-
-def _grad_b(a2, b):
-    gt = grad_target(b)
-    r = colsum_raw(a2, out=gt)
-    return None if gt is not None else r
 
 
 class DecoderStackFn(torch.autograd.Function):
@@ -2427,8 +2390,8 @@ class DecoderStackFn(torch.autograd.Function):
             L.check(_timed('dec_ffn_bwd', {'flops': 6.0 * R * F * d}, lambda lnb=lnb, rec=rec, P3=P3, P4=P4, dh=dh, u=u, bpart=bpart, slCb=slCb:
                            lib.otr_dec_ffn_bwd(C.byref(lnb), R, _p(rec['hsave']), _p(P3), _p(P4), F, S, _p(dh), _p(u), _p(bpart), _p(slCb), _stream())),
                     'otr_dec_ffn_bwd')
-            grads[o + 16], grads[o + 17], grads[o + 15] = _grad_b(part3[:, :d], g3), _grad_b(part3[:, d:2 * d], be3), _grad_b(part3[:, 2 * d:], b2)
-            grads[o + 12], grads[o + 13], grads[o + 14] = _grad_w(dh, rec['y216'], w1), _grad_b(bpart, b1), _grad_w(da3, u, w2)
+            grads[o + 16], grads[o + 17], grads[o + 15] = sink_colsum_blocks(part3, d, (0, 1, 2), (g3, be3, b2))
+            grads[o + 12], grads[o + 13], grads[o + 14] = sink_wgrad(dh, rec['y216'], w1), sink_colsum(bpart, b1), sink_wgrad(da3, u, w2)
             # ---- cross-attention sub-layer
             dz2, da2, part2, dq16, slBb = f32(R, d), h16(R, d), f32(ngrp, 3 * d), h16(R, d), h16(4, R, d)
             if dkv is None:
@@ -2438,8 +2401,8 @@ class DecoderStackFn(torch.autograd.Function):
                            lambda lnb=lnb, pk=pk, rec=rec, l=l, dq16=dq16, slBb=slBb: lib.otr_dec_cross_bwd(
                                C.byref(lnb), B, Lq, _p(pk[3][1]), _p(pk[2][1]), _p(rec['q16']), _p(rec['ctx2']), _p(rec['lse2']), _p(kv_all), _p(dkv),
                                T * W, W, l * 512, l * 512 + 256, _p(kmask), T, _p(dq16), _p(slBb), _stream())), 'otr_dec_cross_bwd')
-            grads[o + 10], grads[o + 11], grads[o + 9] = _grad_b(part2[:, :d], g2), _grad_b(part2[:, d:2 * d], be2), _grad_b(part2[:, 2 * d:], bo2)
-            grads[o + 8], grads[o + 6], grads[o + 7] = _grad_w(da2, rec['ctx2'], wo2), _grad_w(dq16, rec['y116'], wq), _grad_b(dq16, bq)
+            grads[o + 10], grads[o + 11], grads[o + 9] = sink_colsum_blocks(part2, d, (0, 1, 2), (g2, be2, bo2))
+            grads[o + 8], grads[o + 6], grads[o + 7] = sink_wgrad(da2, rec['ctx2'], wo2), sink_wgrad(dq16, rec['y116'], wq), sink_colsum(dq16, bq)
             # ---- self-attention sub-layer
             dz1, da1, part1, dqkv16, slAb = f32(R, d), h16(R, d), f32(ngrp, 3 * d), h16(R, 3 * d), h16(4, R, d)
             lnb = _dec_lnb(dz2, slBb, 4, rec['ln1'], g1, seed, p_drop, dz1, da1, part1)
@@ -2447,8 +2410,8 @@ class DecoderStackFn(torch.autograd.Function):
                            lambda lnb=lnb, pk=pk, rec=rec, dqkv16=dqkv16, slAb=slAb: lib.otr_dec_self_bwd(
                                C.byref(lnb), B, Lq, _p(pk[1][1]), _p(pk[0][1]), _p(rec['qkv16']), _p(rec['ctx1']), _p(rec['lse1']), _p(dqkv16),
                                _p(slAb), _stream())), 'otr_dec_self_bwd')
-            grads[o + 4], grads[o + 5], grads[o + 3] = _grad_b(part1[:, :d], g1), _grad_b(part1[:, d:2 * d], be1), _grad_b(part1[:, 2 * d:], bo)
-            grads[o + 2], grads[o + 0], grads[o + 1] = _grad_w(da1, rec['ctx1'], wo), _grad_w(dqkv16, rec['y016'], wqkv), _grad_b(dqkv16, bqkv)
+            grads[o + 4], grads[o + 5], grads[o + 3] = sink_colsum_blocks(part1, d, (0, 1, 2), (g1, be1, bo))
+            grads[o + 2], grads[o + 0], grads[o + 1] = sink_wgrad(da1, rec['ctx1'], wo), sink_wgrad(dqkv16, rec['y016'], wqkv), sink_colsum(dqkv16, bqkv)
             dskip, slabs, nslab = dz1, slAb, 4
         dx0 = None
         if ctx.needs_input_grad[0]:
@@ -2822,24 +2785,16 @@ class LstmLayerFn(torch.autograd.Function):
         dx = linear_dgrad_raw(dG2, wi, torch.float32).view(T, B, Hin) if ctx.needs_input_grad[0] else None
         dw_ih = dw_hh = db_ih = db_hh = None
         if ctx.needs_input_grad[1]:
-            gt = grad_target(w_ih_ref)
-            dw_ih = linear_wgrad_raw(dG2, x2, wi, out=gt)
-            dw_ih = None if gt is not None else dw_ih
+            dw_ih = sink_wgrad(dG2, x2, w_ih_ref, wi)
         if ctx.needs_input_grad[2]:
-            gt = grad_target(w_hh_ref)
             if T > 1:
-                dw_hh = linear_wgrad_raw(dG[1:].reshape((T - 1) * B, 4 * H), hop[:T - 1].reshape((T - 1) * B, H), w_hh, out=gt)
-            elif gt is None:
+                dw_hh = sink_wgrad(dG[1:].reshape((T - 1) * B, 4 * H), hop[:T - 1].reshape((T - 1) * B, H), w_hh_ref, w_hh)
+            elif grad_target(w_hh_ref) is None:       # one step from the zero state: h_{-1} = 0
                 dw_hh = torch.zeros_like(w_hh)
-            dw_hh = None if gt is not None else dw_hh
-        for i, ref in ((3, b_ih_ref), (4, b_hh_ref)):
-            if ctx.needs_input_grad[i]:
-                gt = grad_target(ref)
-                db = colsum_raw(dG2, out=gt) if gt is not None else colsum_raw(dG2)
-                if i == 3:
-                    db_ih = None if gt is not None else db
-                else:
-                    db_hh = None if gt is not None else db
+        if ctx.needs_input_grad[3]:
+            db_ih = sink_colsum(dG2, b_ih_ref)
+        if ctx.needs_input_grad[4]:
+            db_hh = sink_colsum(dG2, b_hh_ref)
         return dx, dw_ih, dw_hh, db_ih, db_hh
 
 
@@ -2942,13 +2897,12 @@ class ConvSubsampleFn(torch.autograd.Function):
             dact2 = gm
         M2 = B * T2 * F2
         w1p, b1p, b2p = ctx.refs
-        gw1, gb1, gb2 = grad_target(w1p), grad_target(b1p), grad_target(b2p)
         fused = relu_bwd_colsum_raw(act2.view(M2, C2), dact2.view(M2, C2))       # ReLU mask + the bias-gradient partial sums
         if fused is not None:
-            g2, db2 = fused[0].view(dact2.shape), colsum_raw(fused[1], out=gb2)
+            g2, db2 = fused[0].view(dact2.shape), sink_colsum(fused[1], b2p)
         else:
             g2 = relu_bwd_raw(act2, dact2)
-            db2 = colsum_raw(g2.view(M2, C2), out=gb2)
+            db2 = sink_colsum(g2.view(M2, C2), b2p)
         dw2r = torch.empty((C2, 3, 3, C1), dtype=torch.float32, device=x.device)
         dact1 = torch.empty_like(act1)
         # (r06, measured and removed: this weight gradient on a side stream -- a BRANCH of the captured step beside the input gradient
@@ -2970,24 +2924,25 @@ class ConvSubsampleFn(torch.autograd.Function):
             L.check(rc, 'otr_conv2_dgrad')
         if p_drop > 0:
             L.check(lib.otr_dropout(_p(dact1), _p(dact1), _code(adt), dact1.numel(), p_drop, _p(seed), offs[0], _stream()), 'otr_dropout')
-        if gw1 is not None and gb1 is not None:
-            dw1, db1 = gw1, gb1
-        else:
+        inpl = grad_target(w1p) is not None and grad_target(b1p) is not None
+        if not inpl:                         # the pair of sums lands in one zero-filled tensor that autograd receives
             dwb = torch.zeros((C1 * 10,), dtype=torch.float32, device=x.device)
             dw1, db1 = dwb[:C1 * 9], dwb[C1 * 9:]
         nrow = lib.otr_conv1_wgrad_partial_rows()
         part = torch.empty((nrow, C1 * 10), dtype=torch.float32, device=x.device)      # per-workgroup sums: no atomics
         L.check(lib.otr_conv1_wgrad(C.byref(desc), _p(x), _p(dact1), None, None, _p(part), _stream()), 'otr_conv1_wgrad')
-        inpl = gw1 is not None and gb1 is not None
-        colsum_raw(part[:, :C1 * 9], out=dw1.view(-1), defer=inpl)
-        colsum_raw(part[:, C1 * 9:], out=db1, defer=inpl)
+        if inpl:
+            dw1, db1 = sink_colsum_blocks(part, C1, ((0, 9), 9), (w1p, b1p))
+        else:
+            colsum_raw(part[:, :C1 * 9], out=dw1.view(-1), defer=False)
+            colsum_raw(part[:, C1 * 9:], out=db1, defer=False)
         gw2 = grad_target(ctx.w2_ref)
         if gw2 is not None and gw2.is_contiguous() and gw2.dtype == torch.float32:
             regroup_add(gw2, dw2r, C2, C1, 9, False)                 # [C2, 9, C1] -> += [C2, C1, 3, 3] in one launch (it was AccumulateGrad's strided add)
             dw2 = None
         else:
             dw2 = dw2r.permute(0, 3, 1, 2)
-        return (None, None if inpl else dw1.view(C1, 1, 3, 3), None if inpl else db1, dw2, None if gb2 is not None else db2, None)
+        return None, dw1 if inpl else dw1.view(C1, 1, 3, 3), db1, dw2, db2, None
 
 
 def conv_subsample_with_dropout(x, w1, b1, w2, b2, p_drop):
@@ -3295,9 +3250,7 @@ class RelPosAttentionFn(torch.autograd.Function):
             part = torch.empty((lib.otr_add2_colsum_partial_rows(M), 2 * d), dtype=torch.float32, device=qkv.device)
             L.check(lib.otr_add2_strided_colsum(_p(dquv), 2 * d, _p(dquv, d), 2 * d, _p(dqkv), d3, _code(adt), M, d, _p(part), _stream()),
                     'otr_add2_strided_colsum')
-            colsum_raw(part[:, :d], out=gu.view(-1))
-            colsum_raw(part[:, d:], out=gv.view(-1))
-            du = dv = None
+            du, dv = sink_colsum_blocks(part, d, (0, 1), (pu, pv))
         else:
             L.check(lib.otr_add2_strided(_p(dquv), 2 * d, _p(dquv, d), 2 * d, _p(dqkv), d3, _code(adt), M, d, _stream()),
                     'otr_add2_strided')
@@ -3306,8 +3259,8 @@ class RelPosAttentionFn(torch.autograd.Function):
             _wq['post'].append(lambda: linear_wgrad_raw(dp, pe, pos_w, out=gw))      # queued again: one more grouped launch for all blocks
             dw = None
         else:
-            dw = linear_wgrad_raw(dp, pe, pos_w, out=gw)     # contraction over the padded axis (zero rows): the fast grouped kernel takes it
-        return dqkv, None, None if gw is not None else dw, du, dv, None, None, None
+            dw = sink_wgrad(dp, pe, pos_w, pos_w)     # contraction over the padded axis (zero rows): the fast grouped kernel takes it
+        return dqkv, None, dw, du, dv, None, None, None
 
 
 class ConformerConvFn(torch.autograd.Function):
@@ -3382,10 +3335,9 @@ class ConformerConvFn(torch.autograd.Function):
             dm = torch.empty((M, Cc), dtype=adt, device=dout.device)
             L.check(lib.otr_row_mask_cast(_p(dout), _code(dout.dtype), _p(mask_u8), _p(dm), _code(adt), M, Cc, _stream()), 'otr_row_mask_cast')
         w1p, b1p, w2p, b2p = ctx.refs
-        gw1, gb1, gw2, gb2 = grad_target(w1p), grad_target(b1p), grad_target(w2p), grad_target(b2p)
         ds = linear_fwd_raw(dm, ctx.w2t, None, adt) if ctx.w2t is not None else linear_dgrad_raw(dm, w2c, adt)
-        dw2 = linear_wgrad_raw(dm, s, w2c, out=gw2)
-        db2 = colsum_raw(dm, out=gb2) if b2p is not None else None
+        dw2 = sink_wgrad(dm, s, w2p, w2c)
+        db2 = sink_colsum(dm, b2p)
         red = torch.empty((2 * Cc,), dtype=torch.float32, device=dout.device)
         bn_part = torch.empty((lib.otr_bn_swish_bwd_partial_rows(M), 2 * Cc), dtype=torch.float32, device=dout.device)
         gp, bp = ctx.bn_refs
@@ -3407,46 +3359,35 @@ class ConformerConvFn(torch.autograd.Function):
             L.check(lib.otr_conformer_conv_bwd_mid(_p(y), _p(ds), _p(saved), _p(gamma), _p(beta), _p(red), _p(g), _p(wk), _p(h), _p(mask_u8),
                                                    _p(dh), _p(dpart), _p(part), _code(adt), int(training), B, T, Cc, k, (k - 1) // 2, _stream()),
                     'otr_conformer_conv_bwd_mid')
-            colsum_raw(dpart[:, :Cc * k], out=gwd.view(-1))
-            if has_dwb:
-                colsum_raw(dpart[:, Cc * k:], out=gbd)
-            db1 = colsum_raw(part, out=gb1) if b1p is not None else None
-            dx = (linear_fwd_raw(dh, ctx.w1t, None, xdtype) if ctx.w1t is not None else linear_dgrad_raw(dh, w1c, xdtype)).view(xshape)
-            dw1 = linear_wgrad_raw(dh, x2, w1c, out=gw1)
-            return (dx, None, None if gw1 is not None else dw1, None if gb1 is not None else db1, None, None,
-                    None if bn_inplace else red[Cc:], None if bn_inplace else red[:Cc], None, None,
-                    None if gw2 is not None else dw2, None if gb2 is not None else db2, None, None, None, None)
-        dy = torch.empty((M, Cc), dtype=torch.float32, device=dout.device)
-        L.check(lib.otr_bn_swish_bwd(_p(y), _p(ds), _code(adt), _p(saved), _p(gamma), _p(beta), _p(red), _p(bn_part),
-                                     _p(gg) if bn_inplace else None, _p(gbt) if bn_inplace else None, _p(dy), M, Cc,
-                                     int(training), _stream()), 'otr_bn_swish_bwd')
-        dg = torch.empty((M, Cc), dtype=adt, device=dout.device)
-        dwk = None if dw_inplace else torch.zeros((Cc * k + Cc,), dtype=torch.float32, device=dout.device)
-        if dw_inplace and _DW_PART and _wq['on'] and _in_backward():
-            # the kernel leaves per-workgroup sums; the grouped column-sum launch at the end of backward adds them where the gradients
-            # live (otr_dwconv_bwd_part: no atomics)
-            dpart = torch.empty((lib.otr_dwconv_bwd_partial_rows(M), Cc * k + Cc), dtype=torch.float32, device=dout.device)
-            L.check(lib.otr_dwconv_bwd_part(_p(dy), _p(g), _code(adt), _p(wk), _p(dg), _p(dpart), B, T, Cc, k, (k - 1) // 2, _stream()),
-                    'otr_dwconv_bwd_part')
-            colsum_raw(dpart[:, :Cc * k], out=gwd.view(-1))
-            if has_dwb:
-                colsum_raw(dpart[:, Cc * k:], out=gbd)
+            sink_colsum_blocks(dpart, Cc, ((0, k), k), (wdwp, bdwp))
         else:
-            L.check(lib.otr_dwconv_bwd(_p(dy), _p(g), _code(adt), _p(wk), _p(dg), _p(gwd) if dw_inplace else _p(dwk),
-                                       (_p(gbd) if has_dwb else None) if dw_inplace else _p(dwk, Cc * k), B, T, Cc, k,
-                                       (k - 1) // 2, _stream()), 'otr_dwconv_bwd')
-        dh = torch.empty_like(h)
-        nblk = (M + GLU_RPB - 1) // GLU_RPB
-        part = torch.empty((nblk, 2 * Cc), dtype=torch.float32, device=dout.device)
-        L.check(lib.otr_glu_bwd(_p(h), _p(dg), _p(dh), _p(part), _code(adt), M, Cc, _p(mask_u8), 0, _stream()), 'otr_glu_bwd')
-        db1 = colsum_raw(part, out=gb1) if b1p is not None else None
+            dy = torch.empty((M, Cc), dtype=torch.float32, device=dout.device)
+            L.check(lib.otr_bn_swish_bwd(_p(y), _p(ds), _code(adt), _p(saved), _p(gamma), _p(beta), _p(red), _p(bn_part),
+                                         _p(gg) if bn_inplace else None, _p(gbt) if bn_inplace else None, _p(dy), M, Cc,
+                                         int(training), _stream()), 'otr_bn_swish_bwd')
+            dg = torch.empty((M, Cc), dtype=adt, device=dout.device)
+            dwk = None if dw_inplace else torch.zeros((Cc * k + Cc,), dtype=torch.float32, device=dout.device)
+            if dw_inplace and _DW_PART and _wq['on'] and _in_backward():
+                # the kernel leaves per-workgroup sums; the grouped column-sum launch at the end of backward adds them where the
+                # gradients live (otr_dwconv_bwd_part: no atomics)
+                dpart = torch.empty((lib.otr_dwconv_bwd_partial_rows(M), Cc * k + Cc), dtype=torch.float32, device=dout.device)
+                L.check(lib.otr_dwconv_bwd_part(_p(dy), _p(g), _code(adt), _p(wk), _p(dg), _p(dpart), B, T, Cc, k, (k - 1) // 2, _stream()),
+                        'otr_dwconv_bwd_part')
+                sink_colsum_blocks(dpart, Cc, ((0, k), k), (wdwp, bdwp))
+            else:
+                L.check(lib.otr_dwconv_bwd(_p(dy), _p(g), _code(adt), _p(wk), _p(dg), _p(gwd) if dw_inplace else _p(dwk),
+                                           (_p(gbd) if has_dwb else None) if dw_inplace else _p(dwk, Cc * k), B, T, Cc, k,
+                                           (k - 1) // 2, _stream()), 'otr_dwconv_bwd')
+            dh = torch.empty_like(h)
+            nblk = (M + GLU_RPB - 1) // GLU_RPB
+            part = torch.empty((nblk, 2 * Cc), dtype=torch.float32, device=dout.device)
+            L.check(lib.otr_glu_bwd(_p(h), _p(dg), _p(dh), _p(part), _code(adt), M, Cc, _p(mask_u8), 0, _stream()), 'otr_glu_bwd')
+        db1 = sink_colsum(part, b1p)
         dx = (linear_fwd_raw(dh, ctx.w1t, None, xdtype) if ctx.w1t is not None else linear_dgrad_raw(dh, w1c, xdtype)).view(xshape)
-        dw1 = linear_wgrad_raw(dh, x2, w1c, out=gw1)
-        return (dx, None, None if gw1 is not None else dw1, None if gb1 is not None else db1,
+        dw1 = sink_wgrad(dh, x2, w1p, w1c)
+        return (dx, None, dw1, db1,
                 None if dw_inplace else dwk[:Cc * k].view(wdw_shape), dwk[Cc * k:] if (has_dwb and not dw_inplace) else None,
-                None if bn_inplace else red[Cc:], None if bn_inplace else red[:Cc], None, None,
-                None if gw2 is not None else dw2,
-                None if gb2 is not None else db2, None, None, None, None)
+                None if bn_inplace else red[Cc:], None if bn_inplace else red[:Cc], None, None, dw2, db2, None, None, None, None)
 
 
 class LookaheadConvFn(torch.autograd.Function):
