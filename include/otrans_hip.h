@@ -40,7 +40,7 @@ extern "C" {
  * bump; 602: the rescoring entries, additions only; 603: otr_ctc_align, additions only; 604: otr_ngram_lookup and otr_ctc_beam_search_lm, additions only; 605:
  * otr_edit_distance, additions only; 606: otr_ngram_score_cands, otr_ngram_score_seqs and otr_rescore_select_add, additions only; 607: otr_ngram_count, otr_ngram_stats and otr_ngram_estimate, additions only;
  * 608: otr_mwer_workspace_floats and otr_mwer_loss, additions only; still 608: otr_feature_prepare_workspace_bytes, otr_feature_prepare and
- * otr_cmvn_accumulate were added without a bump -- no existing signature, structure or meaning changed, and a binding that needs them
+ * otr_cmvn_accumulate, and after them otr_ctc_segment_workspace_bytes and otr_ctc_segment, were added without a bump -- no existing signature, structure or meaning changed, and a binding that needs them
  * fails on the missing symbol of an older library when it loads it).  A binding compares otr_version() with the OTR_ABI_VERSION it was written against BEFORE its first call and refuses a
  * library that answers anything else: descriptors are passed by pointer and read at the library's idea of their size. */
 #define OTR_ABI_VERSION 608
@@ -766,6 +766,41 @@ int64_t otr_ctc_align_workspace_bytes(int32_t B, int32_t T, int32_t max_tgt);
 int32_t otr_ctc_align(const float* log_probs, int64_t ld, const int64_t* targets, int64_t ldt, const int32_t* in_len,
                       const int32_t* tgt_len, int32_t B, int32_t T, int32_t V, int32_t max_tgt, int32_t blank, void* workspace,
                       int64_t ws_bytes, int32_t* frame_token, int32_t* spans, float* label_logp, float* score, void* stream);
+
+/* ---- CTC segmentation of long recordings (Kuerzinger et al. 2020, the ctc-segmentation tool): where in minutes of audio a transcript
+ *      of many utterances lies, csrc/ctcseg.hip.  otr_ctc_align's recursion for up to 4095 labels, with a path that need not cover the
+ *      whole recording.  f32 in both builds.
+ * log_probs, ld, in_len (T_b = clamp(in_len[b], 0, T); frames t >= T_b are not read), targets, ldt, tgt_len, the extended states
+ * s = 0 .. 2L, ext(s) and x_t(c) as in otr_ctc_align, with 1 <= L = tgt_len[b] <= max_tgt <= 4095 and 1 <= T <= 2^20 (float(t) exact).
+ * free_start, free_end: 0 or 1.  skip_logp: f32, finite and <= 0, charged once for every frame the path does not cover.
+ *   Start: v_0(0) = x_0(blank), v_0(1) = x_0(l_0), -inf elsewhere; both carry back-pointer code 3, "the path starts here".
+ *   t >= 1: the candidates, in tie order, are stay v_{t-1}(s); v_{t-1}(s-1); v_{t-1}(s-2) where otr_ctc_align allows it (ext(s) is a
+ *   label and differs from ext(s-2)); for s in {0, 1} and only if free_start the virtual start float(t) * skip_logp (one f32 multiply
+ *   of the exactly converted t), code 3.  A later candidate wins only if it is strictly greater.  v_t(s) = max + x_t(ext(s)): one f32
+ *   add after an exact max.
+ *   End: with free_end every frame t is a candidate, for s = 2L and then 2L-1: e = v_t(s) + tail, tail = float(T_b-1-t) * skip_logp for
+ *   t < T_b-1 and exactly 0 at the last frame; otherwise only t = T_b-1 is.  The largest e wins; on ties the earliest t, then 2L
+ *   before 2L-1.  The trace follows the codes back from there until it meets a code 3.
+ * Outputs: score f32 [B] = the winning e; bounds int32 [B, 2] = the first covered frame and one past the last covered frame;
+ * frame_token int32 [B, T] = the path's token on covered frames (blank on blank frames), -1 on skipped frames and for t >= T_b; spans
+ * int32 [B, max_tgt, 2] and label_logp f32 [B, max_tgt] as in otr_ctc_align (sums in ascending t; rows j >= L hold -1 and 0).
+ * Infeasible -- L < 1 or L > max_tgt (L = 0 too, unlike otr_ctc_align), a label outside [0, V), T_b = 0, no path of finite score --:
+ * nothing is computed, score = -inf, bounds, frame_token and spans all -1, label_logp all 0; other recordings are unaffected.
+ * With free_start = free_end = 0 and L <= 127 the outputs equal otr_ctc_align's and bounds = (0, T_b).
+ * Why skip_logp: with skip_logp = 0 leaving a frame out costs nothing while covering it costs its log-prob, so the path shrinks its
+ * first and last labels to one frame each.  With ln p(token) > skip_logp > ln p(blank on noise), e.g. ln 0.5, covering a frame the
+ * label explains is cheaper than skipping it and skipping a frame of noise is cheaper than calling it blank.
+ * One launch, one workgroup per recording (no waiting between workgroups), no allocation, no host synchronisation, legal under stream
+ * capture.  workspace: otr_ctc_segment_workspace_bytes(B, T, max_tgt) bytes of 2-bit back-pointers, 8-byte aligned, never NULL; it need
+ * not be zeroed.  Every argument is checked before the launch (null pointers; B < 1, T outside [1, 2^20], V <= 1, max_tgt outside
+ * [1, 4095]; ld < V, ldt < max_tgt; blank outside [0, V); a flag other than 0 or 1; skip_logp positive, NaN or infinite; the
+ * workspace's size and alignment): a refused call leaves every output untouched.
+ * otr_ctc_segment_workspace_bytes: pure host function, -1 for a bad shape (B < 1, T outside [1, 2^20], max_tgt outside [1, 4095]). */
+int64_t otr_ctc_segment_workspace_bytes(int32_t B, int32_t T, int32_t max_tgt);
+int32_t otr_ctc_segment(const float* log_probs, int64_t ld, const int64_t* targets, int64_t ldt, const int32_t* in_len,
+                        const int32_t* tgt_len, int32_t B, int32_t T, int32_t V, int32_t max_tgt, int32_t blank, int32_t free_start,
+                        int32_t free_end, float skip_logp, void* workspace, int64_t ws_bytes, int32_t* frame_token, int32_t* spans,
+                        float* label_logp, float* score, int32_t* bounds, void* stream);
 
 /* ---- WER / CER scoring: batched edit distance with corpus totals (the editdistance.eval calls of eval.py:160-178 and
  *      tools/computer_wer.py), csrc/editdist.hip.  Integer only, identical in both builds.

@@ -212,6 +212,8 @@ SIGNATURES = {
                                _F32, _P, _P],
     'otr_ctc_align_workspace_bytes': [_I32, _I32, _I32],
     'otr_ctc_align': [_P, _I64, _P, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P],
+    'otr_ctc_segment_workspace_bytes': [_I32, _I32, _I32],
+    'otr_ctc_segment': [_P, _I64, _P, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F32, _P, _I64, _P, _P, _P, _P, _P, _P],
     'otr_edit_distance': [_P, _I64, _P, _P, _I64, _I64, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P],
     'otr_joint_prebeam': [_P, _I64, _P, _I64, _F32, _F32, _I64, _I32, _I32, _P, _P, _P],
     'otr_ctc_prefix_score': [_P, _I64, _P, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _P, _P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P,
@@ -268,7 +270,7 @@ _RESTYPE = {'otr_last_error_string': C.c_char_p, 'otr_dec_ffn_hsave_bytes': C.c_
             'otr_ln_bwd_proj_partial_rows': C.c_int64, 'otr_dwconv_bwd_partial_rows': C.c_int64, 'otr_dwconv_fwd_partial_rows': C.c_int64,
             'otr_conv2_wide_scratch_bytes': C.c_int64, 'otr_add2_colsum_partial_rows': C.c_int64,
             'otr_ctc_beam_workspace_bytes': C.c_int64, 'otr_ctc_align_workspace_bytes': C.c_int64, 'otr_mwer_workspace_floats': C.c_int64,
-            'otr_feature_prepare_workspace_bytes': C.c_int64}
+            'otr_feature_prepare_workspace_bytes': C.c_int64, 'otr_ctc_segment_workspace_bytes': C.c_int64}
 
 _libs = {}
 _kind = 'bf16'

@@ -3808,6 +3808,53 @@ def ctc_forced_align(log_probs, in_len, targets, tgt_len, blank=0):
     return frame_token, spans, label_logp, score
 
 
+CTC_SEGMENT_MAX_TGT = 4095
+
+
+def ctc_segment(log_probs, in_len, targets, tgt_len, blank=0, free_start=True, free_end=True, skip_logp=0.0):
+    """CTC segmentation on the device (include/otrans_hip.h otr_ctc_segment): the most probable CTC path of each recording's known
+    label sequence (up to 4095 labels) that may begin after the recording's first frame (free_start) and end before its last
+    (free_end); every frame it leaves out is charged skip_logp <= 0.  Arguments as ops.ctc_forced_align.  Returns (frame_token int32
+    [B, T]: the path's token per covered frame, blank on blank frames, -1 on skipped frames and past in_len; spans int32 [B, max_tgt,
+    2]; label_logp f32 [B, max_tgt]; score f32 [B]; bounds int32 [B, 2]: the first covered frame and one past the last).  A
+    recording that cannot be segmented (no labels, no frames, fewer frames than labels plus adjacent repeats, a length beyond
+    max_tgt) has score -inf, frame_token, spans and bounds -1, label_logp 0.  With both flags off and at most 127 labels the first
+    four outputs are ctc_forced_align's.  No autograd; one launch on the current stream, no host synchronisation."""
+    if targets.dim() != 2 or not 1 <= targets.shape[1] <= CTC_SEGMENT_MAX_TGT:
+        raise ValueError('ctc_segment: targets must be [B, max_tgt] with 1 <= max_tgt <= %d label columns, got %s'
+                         % (CTC_SEGMENT_MAX_TGT, tuple(targets.shape)))
+    _cuda(log_probs, in_len, targets, tgt_len)
+    if log_probs.dim() != 3 or log_probs.dtype != torch.float32:
+        raise L.OtransHipError('ctc_segment: log_probs must be f32 [B, T, V], got %s %s' % (log_probs.dtype, tuple(log_probs.shape)))
+    B, T, V = log_probs.shape
+    max_tgt = targets.shape[1]
+    lib = L.load()
+    dev = log_probs.device
+    lp = log_probs if log_probs.stride(2) == 1 and log_probs.stride(0) == T * log_probs.stride(1) else log_probs.contiguous()
+    tg = targets.to(torch.int64)
+    if tg.stride(1) != 1:
+        tg = tg.contiguous()
+    il = in_len.to(torch.int32).contiguous()
+    tl = tgt_len.to(torch.int32).contiguous()
+    need = lib.otr_ctc_segment_workspace_bytes(B, T, max_tgt)
+    skip_logp = float(skip_logp)
+    if (need < 0 or targets.shape[0] != B or il.numel() != B or tl.numel() != B or not 0 <= blank < V
+            or not (math.isfinite(skip_logp) and skip_logp <= 0.0)):
+        raise L.OtransHipError('ctc_segment: bad arguments B=%d T=%d V=%d targets %s blank=%d skip_logp=%r'
+                               % (B, T, V, tuple(targets.shape), blank, skip_logp))
+    ws = torch.empty(need // 8, dtype=torch.int64, device=dev)
+    frame_token = torch.empty((B, T), dtype=torch.int32, device=dev)
+    spans = torch.empty((B, max_tgt, 2), dtype=torch.int32, device=dev)
+    label_logp = torch.empty((B, max_tgt), dtype=torch.float32, device=dev)
+    score = torch.empty((B,), dtype=torch.float32, device=dev)
+    bounds = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    L.check(_timed('ctc_segment %dx%dx%d' % (B, T, max_tgt), {'bytes': B * T * (2 * max_tgt + 1) * 4},
+                   lambda: lib.otr_ctc_segment(_p(lp), lp.stride(1), _p(tg), tg.stride(0), _p(il), _p(tl), B, T, V, max_tgt, blank,
+                                               int(bool(free_start)), int(bool(free_end)), skip_logp, _p(ws), need, _p(frame_token),
+                                               _p(spans), _p(label_logp), _p(score), _p(bounds), _stream())), 'otr_ctc_segment')
+    return frame_token, spans, label_logp, score, bounds
+
+
 # ------------------------------------------------------------------ WER / CER scoring (csrc/editdist.hip)
 EDIT_MAX_LEN, EDIT_MAX_NBEST = 2048, 32
 
