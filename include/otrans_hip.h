@@ -40,7 +40,7 @@ extern "C" {
  * bump; 602: the rescoring entries, additions only; 603: otr_ctc_align, additions only; 604: otr_ngram_lookup and otr_ctc_beam_search_lm, additions only; 605:
  * otr_edit_distance, additions only; 606: otr_ngram_score_cands, otr_ngram_score_seqs and otr_rescore_select_add, additions only; 607: otr_ngram_count, otr_ngram_stats and otr_ngram_estimate, additions only;
  * 608: otr_mwer_workspace_floats and otr_mwer_loss, additions only; still 608: otr_feature_prepare_workspace_bytes, otr_feature_prepare and
- * otr_cmvn_accumulate, and after them otr_ctc_segment_workspace_bytes and otr_ctc_segment, were added without a bump -- no existing signature, structure or meaning changed, and a binding that needs them
+ * otr_cmvn_accumulate, after them otr_ctc_segment_workspace_bytes and otr_ctc_segment, and after those otr_distill_workspace_floats and otr_distill_loss (additions only), were added without a bump -- no existing signature, structure or meaning changed, and a binding that needs them
  * fails on the missing symbol of an older library when it loads it).  A binding compares otr_version() with the OTR_ABI_VERSION it was written against BEFORE its first call and refuses a
  * library that answers anything else: descriptors are passed by pointer and read at the library's idea of their size. */
 #define OTR_ABI_VERSION 608
@@ -1022,6 +1022,44 @@ int32_t otr_mwer_loss(const float* logits, int64_t ld, const int64_t* ys_out, in
                       int32_t B, int32_t N, int32_t max_len, int32_t V, const float* grad_scale, float* loss, float* seq_logp,
                       float* post, float* utt_err, float* dlogits, int64_t ld_dlogits, float* workspace, int64_t workspace_floats,
                       void* stream);
+
+/* ---- knowledge distillation (Hinton et al. 2015): the temperature-scaled KL divergence of a student's logits from a teacher's, per
+ *      frame, with its gradient into the student's logits, csrc/distill.hip.  f32 in every build.  Rows are [B, T]: row r = b * T + i
+ *      at student + r * ld_s (and teacher + r * ld_t, top_val / top_idx + r * K, dlogits + r * ld_d).
+ *   Row (b, i) is LIVE iff i < min(max(lengths[b], 0), T), lengths int32 [B] on the device -- and, in the sparse form, it lists at least
+ *   one entry; in the dense form, its teacher row holds at least one element above -inf (a teacher row of -inf throughout has no
+ *   distribution to distil).  Rows that are dead by lengths are never read; finding the other two kinds takes a read of the row's teacher.
+ *   n_live = the number of live rows, formed on the device.
+ *   With tau = temperature: p = softmax(student[r, :V] / tau).
+ *   Dense teacher (teacher != NULL):  q = softmax(teacher[r, :V] / tau); a teacher element of -inf gives q_v = 0 and a term of 0.
+ *   Sparse teacher (top_val f32, top_idx int32, both [B*T, K]): the LISTED entries of row r are the k with 0 <= top_idx[r, k] < V; q over
+ *   them is softmax(top_val[r, k] / tau) -- the top-K mass is renormalised, and the values may be logits or log-probs, the softmax being
+ *   shift-invariant -- and 0 elsewhere.  An index outside [0, V) drops its entry and is never used as an address.  Indices within a row
+ *   must be distinct (the caller's contract; otr_ctc_topk keeps it).  An entry of -inf is listed with q = 0.
+ *   kl_r = sum_v q_v (ln q_v - ln p_v)
+ *   loss = tau^2 / n_live * sum over the live rows of kl_r      (Hinton's scaling: the gradient's magnitude does not depend on tau)
+ *   dlogits[r, v] = g * tau / n_live * (p_v - q_v) on live rows for v < V, g = *grad_scale (a device scalar; NULL: 1).  EVERY other
+ *   element of dlogits [B*T, ld_d] is written as zero -- dead rows, columns V .. ld_d - 1 -- so the launch needs no memset.
+ *   n_live = 0: loss 0, gradient all zero.
+ * Outputs: loss f32 [1]; row_kl f32 [B*T] = kl_r, 0 on dead rows; dlogits (NULL: forward only, two launches).  workspace: at least
+ *   otr_distill_workspace_floats(B, T) floats (every row's maxima and reciprocal sums, and g tau / n_live); that entry runs on the host
+ *   and answers -1 for a shape otr_distill_loss refuses.
+ * Launches (at most three): a row pass, one wave per row, that reads the row ONCE -- student and teacher together -- into online
+ *   maxima / sums; the cross term sum_v e^{t_v/tau - m} (t_v - s_v) / tau is rescaled whenever the teacher's maximum moves, so kl_r needs
+ *   no second read (the sparse form gathers student[r, top_idx] after the row pass instead); one workgroup that adds row_kl up in a fixed
+ *   order; a gradient pass, one wave per row, that reads each live row once more.  No floating-point atomics: the same bits on every run.
+ *   Loads and stores are 16 bytes wide where the base is 16-byte aligned and the row stride a multiple of 4 floats (student, teacher and
+ *   dlogits judged separately), scalar otherwise.
+ * Refused before any launch (< 0, outputs untouched): both teacher forms or neither (the sparse form counts as given when top_val,
+ *   top_idx or K is non-zero); a NULL student, lengths, loss, row_kl, or one of top_val / top_idx in the sparse form; V outside
+ *   [1, 8192]; K outside [1, 128] in the sparse form; ld_s, ld_t (dense) or ld_d (with dlogits) below V; T < 1, B < 0, B * T >= 2^30;
+ *   temperature not finite or <= 0; a NULL, too small or not 16-byte aligned workspace.  B = 0 returns 0 without a launch.  Caller-owned buffers, no
+ *   allocation, memset or host synchronisation: capturable. */
+int64_t otr_distill_workspace_floats(int32_t B, int32_t T);
+int32_t otr_distill_loss(const float* student, int64_t ld_s, const float* teacher, int64_t ld_t, const float* top_val,
+                         const int32_t* top_idx, int32_t K, const int32_t* lengths, int32_t B, int32_t T, int32_t V, float temperature,
+                         const float* grad_scale, float* loss, float* row_kl, float* dlogits, int64_t ld_d, float* workspace,
+                         int64_t workspace_floats, void* stream);
 
 /* ---- transposed copies of many matrices in ONE launch (the W^T bf16 shadows that turn dx = dy.W into a
  *      forward-type GEMM; refreshed after every optimizer step).  table: DEVICE int64 [n_mats,4] rows of

@@ -232,6 +232,8 @@ SIGNATURES = {
     'otr_ngram_estimate': [_P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],
     'otr_mwer_workspace_floats': [_I32, _I32, _I32],
     'otr_mwer_loss': [_P, _I64, _P, _I64, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P],
+    'otr_distill_workspace_floats': [_I32, _I32],
+    'otr_distill_loss': [_P, _I64, _P, _I64, _P, _P, _I32, _P, _I32, _I32, _I32, _F32, _P, _P, _P, _P, _I64, _P, _I64, _P],
     'otr_decode_embed': [_P, _I64, _P, _P, _P, _P, _I64, _I32, _I32, _F32, _P],
     'otr_decode_lookup': [_P, _I64, _P, _P, _P, _P, _I64, _I32, _I32, _P],
     'otr_lstm_cell': [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P],
@@ -270,7 +272,8 @@ _RESTYPE = {'otr_last_error_string': C.c_char_p, 'otr_dec_ffn_hsave_bytes': C.c_
             'otr_ln_bwd_proj_partial_rows': C.c_int64, 'otr_dwconv_bwd_partial_rows': C.c_int64, 'otr_dwconv_fwd_partial_rows': C.c_int64,
             'otr_conv2_wide_scratch_bytes': C.c_int64, 'otr_add2_colsum_partial_rows': C.c_int64,
             'otr_ctc_beam_workspace_bytes': C.c_int64, 'otr_ctc_align_workspace_bytes': C.c_int64, 'otr_mwer_workspace_floats': C.c_int64,
-            'otr_feature_prepare_workspace_bytes': C.c_int64, 'otr_ctc_segment_workspace_bytes': C.c_int64}
+            'otr_feature_prepare_workspace_bytes': C.c_int64, 'otr_ctc_segment_workspace_bytes': C.c_int64,
+            'otr_distill_workspace_floats': C.c_int64}
 
 _libs = {}
 _kind = 'bf16'

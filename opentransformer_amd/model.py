@@ -143,7 +143,8 @@ class CTCModel(nn.Module):
     truth[:, 1:-1] and lengths targets_length - 1 (:95; SpeechToText's joint CTC term keeps the EOS instead).  The
     reference's inference / recognize / ts_forward call the encoder without the frontend and with a length where a mask
     belongs (:98-121, broken as shipped); inference() here is the working form: frontend -> encoder ->
-    CTCAssistor.inference, which is what recognize.CTCRecognizer consumes."""
+    CTCAssistor.inference, which is what recognize.CTCRecognizer consumes.  ts_forward (:105-115, the teacher-student forward: the
+    head's raw logits) has its working form in distill.DistillTraining, which reads assistor(memory, return_logits=True)."""
 
     def __init__(self, params):
         super().__init__()

@@ -4118,6 +4118,24 @@ def attention_rescore(logits, tokens, out_len, scores, max_len, V, ctc_weight, l
 MWER_MAX_NBEST, MWER_MAX_V = 32, 8192
 
 
+def _saved_logits_grad(ctx, g):
+    """backward of a loss whose forward launch wrote d loss / d logits into a saved [R, ldd] buffer (MwerLossFn, DistillLossFn): the
+    buffer itself when g is the cached unit seed of ops.backward, else g times it; at a padded width it leaves as the head of a
+    zero-tailed buffer"""
+    (dlogits,) = ctx.saved_tensors
+    seed = _state.get(('unit_grad', g.device, g.dtype))
+    if seed is not None and g.data_ptr() == seed.data_ptr():
+        out = dlogits                                              # g == 1: the saved buffer IS the gradient
+    else:
+        out = torch.empty_like(dlogits)
+        g = g.contiguous().float()
+        L.check(L.load().otr_scale(_p(dlogits), _p(out), dlogits.numel(), _p(g), 1.0, _stream()), 'otr_scale')
+    if out.shape[1] != ctx.V:
+        out._otr_zero_tail = tuple(out.shape)                      # LinearFn.backward may read it at its full width (_zero_tail_of)
+        out = out[:, :ctx.V]
+    return out.view(ctx.shape)
+
+
 class MwerLossFn(torch.autograd.Function):
     """The N-best expected number of errors (include/otrans_hip.h otr_mwer_loss) of teacher-forced logits [B*N*max_len, V] (any leading
     shape) + its gradient in the same call when the logits need one, like LabelSmoothingLossFn.  The head of a row-padded product
@@ -4157,18 +4175,7 @@ class MwerLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g, *_):
-        (dlogits,) = ctx.saved_tensors
-        seed = _state.get(('unit_grad', g.device, g.dtype))
-        if seed is not None and g.data_ptr() == seed.data_ptr():
-            out = dlogits                                          # g == 1: the saved buffer IS the gradient
-        else:
-            out = torch.empty_like(dlogits)
-            g = g.contiguous().float()
-            L.check(L.load().otr_scale(_p(dlogits), _p(out), dlogits.numel(), _p(g), 1.0, _stream()), 'otr_scale')
-        if out.shape[1] != ctx.V:
-            out._otr_zero_tail = tuple(out.shape)                  # LinearFn.backward may read it at its full width (_zero_tail_of)
-            out = out[:, :ctx.V]
-        return out.view(ctx.shape), None, None, None, None
+        return _saved_logits_grad(ctx, g), None, None, None, None
 
 
 def mwer_loss(logits, ys_out, n_rows, errors, grad_scale=None):
@@ -4197,3 +4204,146 @@ def mwer_loss(logits, ys_out, n_rows, errors, grad_scale=None):
         raise L.OtransHipError('mwer_loss: logits f32, ys_out int64 (rows contiguous), n_rows int32, errors int32 expected')
     loss, seq_logp, post, utt_err = MwerLossFn.apply(logits, ys_out, n_rows.contiguous(), errors.contiguous(), grad_scale)
     return loss, {'seq_logp': seq_logp.view(B, N), 'post': post, 'utt_err': utt_err}
+
+
+# ------------------------------------------------------------------ knowledge distillation (csrc/distill.hip)
+DISTILL_MAX_V, DISTILL_MAX_K = 8192, 128
+
+
+class DistillLossFn(torch.autograd.Function):
+    """The temperature-scaled KL divergence of student logits [B, T, V] from a teacher (include/otrans_hip.h otr_distill_loss): dense
+    (`teacher` [B, T, V]) or sparse (`top_val`, `top_idx` [B, T, K]), + its gradient into the student's logits in the same call when
+    they need one, like MwerLossFn: the head of a row-padded product is read in place, the gradient leaves as the head of a zero-tailed
+    [R, V8] buffer, `gscale` (a device scalar; None = 1) rides in the written gradient, and backward multiplies by the incoming gradient
+    unless that is the cached unit seed of ops.backward.  Returns (loss, row_kl [B, T]); only loss is differentiable, and only with
+    respect to the student.  The gradient is fp32."""
+
+    @staticmethod
+    def forward(ctx, student, teacher, top_val, top_idx, lengths, temperature, gscale):
+        B, T, V = student.shape
+        lg = student.reshape(-1, V)
+        ok = lg.stride(1) == 1 and (lg.shape[0] <= 1 or lg.stride(0) >= V)
+        if not ok:
+            lg = lg.contiguous()
+        ld = lg.stride(0) if lg.shape[0] > 1 else V
+        R = lg.shape[0]
+        need = ctx.needs_input_grad[0]
+        ldd = ld if (V < ld < V + 8 and ld % 8 == 0) else V          # the padded width goes back to LinearFn.backward with a zero tail
+        dev = lg.device
+        f32 = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)    # noqa: E731
+        loss, row_kl = f32(), f32(B, T)
+        dlogits = f32(R, ldd) if need else None
+        K, ld_t, tg = 0, 0, None
+        if teacher is not None:
+            tg = teacher.reshape(-1, V)
+            if not (tg.stride(1) == 1 and (R <= 1 or tg.stride(0) >= V)):
+                tg = tg.contiguous()
+            ld_t = tg.stride(0) if R > 1 else V
+        else:
+            K = top_val.shape[-1]
+            top_val, top_idx = top_val.reshape(-1, K).contiguous(), top_idx.reshape(-1, K).contiguous()
+        lib = L.load()
+        ws = f32(max(lib.otr_distill_workspace_floats(B, T), 4))
+        L.check(_timed('distill_loss %dx%dx%d%s' % (B, T, V, ' K=%d' % K if K else ''),
+                       {'bytes': R * ((V if K else 2 * V) + (ldd if need else 0)) * 4},
+                       lambda: lib.otr_distill_loss(_p(lg), ld, _p(tg), ld_t, _p(top_val), _p(top_idx), K, _p(lengths), B, T, V,
+                                                    float(temperature), _p(gscale), _p(loss), _p(row_kl), _p(dlogits), ldd, _p(ws),
+                                                    ws.numel(), _stream())), 'otr_distill_loss')
+        ctx.save_for_backward(dlogits)
+        ctx.shape, ctx.V = student.shape, V
+        ctx.mark_non_differentiable(row_kl)
+        return loss, row_kl
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        return _saved_logits_grad(ctx, g), None, None, None, None, None, None
+
+
+def _distill_args(who, student, lengths, temperature):
+    """the checks both forms share; returns (B, T, V)"""
+    if student.dim() != 3:
+        raise ValueError('%s: student logits must be [B, T, V], got %s' % (who, tuple(student.shape)))
+    B, T, V = student.shape
+    if not 1 <= V <= DISTILL_MAX_V:
+        raise ValueError('%s: vocabulary V=%d must be in [1, %d]' % (who, V, DISTILL_MAX_V))
+    if T < 1 or B * T >= 1 << 30:
+        raise ValueError('%s: B*T = %d*%d must be in [0, 2^30) with T >= 1' % (who, B, T))
+    if lengths.numel() != B:
+        raise ValueError('%s: lengths must hold B = %d entries, got %s' % (who, B, tuple(lengths.shape)))
+    tau = float(temperature)
+    if not (tau > 0 and tau != float('inf')):
+        raise ValueError('%s: temperature=%r must be finite and > 0' % (who, temperature))
+    return B, T, V
+
+
+def _distill_run(who, student, teacher, top_val, top_idx, lengths, temperature, grad_scale):
+    _cuda(student, teacher, top_val, top_idx, lengths, grad_scale)
+    if student.dtype != torch.float32 or lengths.dtype not in (torch.int32, torch.int64) or (
+            grad_scale is not None and grad_scale.dtype != torch.float32):
+        raise L.OtransHipError('%s: student f32, lengths int32 (or int64), grad_scale f32 expected' % who)
+    B, T = student.shape[:2]
+    if B == 0:
+        return student.new_zeros(()), student.new_zeros((0, T))
+    return DistillLossFn.apply(student, teacher, top_val, top_idx, lengths.to(torch.int32).contiguous(), float(temperature), grad_scale)
+
+
+def distill_loss(student_logits, teacher_logits, lengths, temperature=1.0, grad_scale=None):
+    """Knowledge-distillation loss against a dense teacher (include/otrans_hip.h otr_distill_loss): tau^2 / n_live times the sum over
+    the live rows (b, i < lengths[b]) of KL(softmax(teacher / tau) || softmax(student / tau)).  student_logits f32 [B, T, V] with unit
+    stride along the vocabulary (a view with a longer row stride, such as the head of a row-padded product, is read in place);
+    teacher_logits f32 of the same shape, it takes no gradient; lengths int32 [B] on the device.  grad_scale: a device scalar the
+    gradient into the student's logits is multiplied by (the loss scale), None = 1.  Returns (loss, row_kl [B, T] detached).
+    At most three launches on the current stream, no host synchronisation, the same bits on every run: capturable."""
+    B, T, V = _distill_args('distill_loss', student_logits, lengths, temperature)
+    if tuple(teacher_logits.shape) != (B, T, V):
+        raise ValueError('distill_loss: teacher logits %s do not match the student\'s %s' % (tuple(teacher_logits.shape), (B, T, V)))
+    _cuda(student_logits, teacher_logits)
+    if teacher_logits.dtype != torch.float32:
+        raise L.OtransHipError('distill_loss: teacher logits must be f32, got %s' % teacher_logits.dtype)
+    return _distill_run('distill_loss', student_logits, teacher_logits.detach(), None, None, lengths, temperature, grad_scale)
+
+
+def distill_loss_topk(student_logits, top_val, top_idx, lengths, temperature=1.0, grad_scale=None):
+    """distill_loss against a sparse teacher: top_val f32 / top_idx int32 [B, T, K] (what topk_rows returns; logits or log-probs), K <=
+    DISTILL_MAX_K.  The teacher's distribution of a row is the softmax of its listed values (index in [0, V); the top-K mass is
+    renormalised) and zero elsewhere; a row that lists nothing takes no part.  Indices within a row must be distinct."""
+    B, T, V = _distill_args('distill_loss_topk', student_logits, lengths, temperature)
+    if top_val.dim() != 3 or tuple(top_val.shape[:2]) != (B, T) or top_idx.shape != top_val.shape:
+        raise ValueError('distill_loss_topk: top_val and top_idx must both be [B, T, K] = [%d, %d, K], got %s and %s'
+                         % (B, T, tuple(top_val.shape), tuple(top_idx.shape)))
+    K = top_val.shape[2]
+    if not 1 <= K <= DISTILL_MAX_K:
+        raise ValueError('distill_loss_topk: K=%d entries per row must be in [1, %d]' % (K, DISTILL_MAX_K))
+    _cuda(student_logits, top_val, top_idx)
+    if top_val.dtype != torch.float32 or top_idx.dtype != torch.int32:
+        raise L.OtransHipError('distill_loss_topk: top_val f32 and top_idx int32 expected, got %s and %s' % (top_val.dtype, top_idx.dtype))
+    return _distill_run('distill_loss_topk', student_logits, None, top_val.detach(), top_idx, lengths, temperature, grad_scale)
+
+
+def topk_rows(x, lengths, K):
+    """The K largest entries of every row of x f32 [B, T, V] (include/otrans_hip.h otr_ctc_topk): (val f32 [B, T, K] descending, idx
+    int32 [B, T, K], ties to the lower index).  Rows at or past lengths[b] are left as zeros -- K copies of (0.0, index 0), which is
+    not a legal sparse row (the indices repeat): hand distill_loss_topk the same lengths, so that it never reads them.  The producer
+    of sparse teachers for distill_loss_topk: 2K numbers per frame instead of V.  One launch, no host synchronisation."""
+    if x.dim() != 3:
+        raise ValueError('topk_rows: x must be [B, T, V], got %s' % (tuple(x.shape),))
+    B, T, V = x.shape
+    K = int(K)
+    if not 1 <= V <= DISTILL_MAX_V:
+        raise ValueError('topk_rows: V=%d must be in [1, %d]' % (V, DISTILL_MAX_V))
+    if not 1 <= K <= min(DISTILL_MAX_K, V):
+        raise ValueError('topk_rows: K=%d must be in [1, min(%d, V=%d)]' % (K, DISTILL_MAX_K, V))
+    if T < 1 or lengths.numel() != B:
+        raise ValueError('topk_rows: T=%d must be >= 1 and lengths hold B = %d entries' % (T, B))
+    _cuda(x, lengths)
+    if x.dtype != torch.float32:
+        raise L.OtransHipError('topk_rows: x must be f32, got %s' % x.dtype)
+    x = x.detach()
+    if not (x.stride(2) == 1 and x.stride(1) >= V and x.stride(0) == T * x.stride(1)):
+        x = x.contiguous()
+    val = torch.zeros((B, T, K), dtype=torch.float32, device=x.device)
+    idx = torch.zeros((B, T, K), dtype=torch.int32, device=x.device)
+    if B:
+        L.check(L.load().otr_ctc_topk(_p(x), x.stride(1), _p(lengths.to(torch.int32).contiguous()), B, T, V, K, _p(val), _p(idx),
+                                      _stream()), 'otr_ctc_topk')
+    return val, idx
