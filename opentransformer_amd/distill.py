@@ -4,10 +4,9 @@ per frame, beside the student's own loss.  The teacher's posteriors come from a 
 teacher_outputs() returned earlier (offline; with topk = K they are the K best entries per frame, 2K numbers instead of V).  The
 working form of the reference's teacher-student hook (otrans/model/ctc.py:105-115 ts_forward)."""
 import torch
-import torch.nn as nn
 
 from . import ops
-from .model import CTCModel, SpeechToText
+from .model import CTCModel, ModelTraining, SpeechToText, shift_targets
 
 
 def _vocab(model):
@@ -15,15 +14,7 @@ def _vocab(model):
     return head.output_layer.weight.shape[0]
 
 
-def _shifted(truth, stacked):
-    """decoder input | loss target of a target matrix, as SpeechToText.forward forms them"""
-    if stacked or not truth.is_cuda or truth.stride(-1) != 1:
-        shifted = torch.stack((truth[:, :-1], truth[:, 1:]))
-        return shifted[0], shifted[1]
-    return truth[:, :-1], truth[:, 1:]                    # read in place
-
-
-class DistillTraining(nn.Module):
+class DistillTraining(ModelTraining):
     """Wraps the student as the submodule `model` (FusedAdam / FlatDataParallel see the same parameters under `model.`);
     forward(inputs, targets, teacher_out=None) -> (loss, aux) with loss = (1 - kd_weight) * own + kd_weight * kd.
 
@@ -61,28 +52,18 @@ class DistillTraining(nn.Module):
         object.__setattr__(self, 'teacher', teacher)      # not registered: out of parameters(), state_dict() and modules()
         self.kd_weight, self.temperature, self.topk = float(kd_weight), float(temperature), None if topk is None else int(topk)
 
-    def save_checkpoint(self, params, name):
-        return self.model.save_checkpoint(params, name)
-
-    def load_model(self, chkpt):
-        return self.model.load_model(chkpt)
-
-    def set_epoch(self, epoch):
-        return self.model.set_epoch(epoch)
-
     @torch.no_grad()
     def teacher_outputs(self, inputs, targets):
         """{'att': ..., 'ctc': ...} (the heads the teacher has): dense f32 logits, or (val, idx) of ops.topk_rows with topk = K"""
         teacher = self.teacher
         if teacher is None:
             raise ValueError('DistillTraining.teacher_outputs: there is no teacher')
-        if teacher.training:
+        if teacher.training:                              # the teacher stays in eval(): nothing to put back, no walk over its modules per step
             teacher.eval()
-        x, mask = teacher.frontend(inputs['inputs'], inputs['mask'])
-        memory, memory_mask, _ = teacher.encoder(x, mask)
+        memory, memory_mask = teacher.encode(inputs['inputs'], inputs['mask'])
         heads = {}
         if isinstance(teacher, SpeechToText):
-            dec_in, _ = _shifted(targets['targets'], False)
+            dec_in, _ = shift_targets(targets['targets'])
             heads['att'] = (teacher.decoder(dec_in, memory, memory_mask)[0], targets['targets_length'])
         if getattr(teacher, 'assistor', None) is not None:
             heads['ctc'] = (teacher.assistor(memory, return_logits=True), torch.sum(memory_mask, dim=-1))
@@ -108,40 +89,23 @@ class DistillTraining(nn.Module):
             if self.teacher is None:
                 raise ValueError('DistillTraining.forward: neither a teacher nor teacher_out was given')
             teacher_out = self.teacher_outputs(inputs, targets)
-        truth, truth_length = targets['targets'], targets['targets_length']
-        x, mask = model.frontend(inputs['inputs'], inputs['mask'])
-        memory, memory_mask, _ = model.encoder(x, mask)
-        kd_att = kd_ctc = loss_ctc = None
-        if isinstance(model, CTCModel):
-            memory_length = torch.sum(memory_mask, dim=-1)
-            ctc_logits = model.assistor(memory, return_logits=True)
-            own = model.assistor.compute_loss(ctc_logits, memory_length, truth[:, 1:-1].contiguous(), truth_length.add(-1))
-            if 'ctc' not in teacher_out:
-                raise ValueError('DistillTraining: teacher_out has no \'ctc\' entry for a CTCModel student')
-            kd = kd_ctc = self._kd('ctc', ctc_logits, memory_length, teacher_out)
-        else:
-            memory = ops.early_mark(memory, model)        # decoder and losses finish their backward before the encoder's starts (dp.py)
-            dec_in, target_out = _shifted(truth, model.ctc_weight > 0)
-            logits, _ = model.decoder(dec_in, memory, memory_mask)
-            own = model.crit(logits, target_out)
-            if 'att' not in teacher_out:
-                raise ValueError('DistillTraining: teacher_out has no \'att\' entry for a SpeechToText student')
-            kd = kd_att = self._kd('att', logits, truth_length, teacher_out)
-            if model.ctc_weight > 0:
-                memory_length = torch.sum(memory_mask, dim=-1)
-                ctc_logits = model.assistor(memory, return_logits=True)
-                loss_ctc = model.assistor.compute_loss(ctc_logits, memory_length, target_out, truth_length)
-                own = (1 - model.ctc_weight) * own + model.ctc_weight * loss_ctc
-                if 'ctc' in teacher_out:
-                    kd_ctc = self._kd('ctc', ctc_logits, memory_length, teacher_out)
-                    kd = (1 - model.ctc_weight) * kd_att + model.ctc_weight * kd_ctc
+        own_head = 'att' if isinstance(model, SpeechToText) else 'ctc'
+        if own_head not in teacher_out:
+            raise ValueError('DistillTraining: teacher_out has no \'%s\' entry for a %s student' % (own_head, type(model).__name__))
+        # a SpeechToText student marks its memory: decoder and losses finish their backward before the encoder's starts (dp.py)
+        memory, memory_mask = model.encode(inputs['inputs'], inputs['mask'], mark=isinstance(model, SpeechToText))
+        out = model.teacher_forced(memory, memory_mask, targets)
+        own, kd_att, kd_ctc = out.loss, None, None
+        if out.logits is not None:
+            kd = kd_att = self._kd('att', out.logits, targets['targets_length'], teacher_out)
+        if out.ctc_logits is not None and 'ctc' in teacher_out:
+            kd = kd_ctc = self._kd('ctc', out.ctc_logits, out.memory_length, teacher_out)
+            if kd_att is not None:
+                kd = (1 - model.ctc_weight) * kd_att + model.ctc_weight * kd_ctc
         total = (1 - self.kd_weight) * own + self.kd_weight * kd
         zero = torch.zeros_like(kd.detach())
         aux = {'Loss': own.detach(), 'KD': kd.detach(), 'KD_att': kd_att.detach() if kd_att is not None else zero,
                'KD_ctc': kd_ctc.detach() if kd_ctc is not None else zero}
-        if loss_ctc is not None:
-            aux['CTCLoss'] = loss_ctc.detach()
-        elif isinstance(model, CTCModel):
-            aux['CTCLoss'] = own.detach()
-        owner = self if getattr(self, '_otr_loss_scale', None) is not None else model
-        return ops.scale_loss_grad(total, owner), aux
+        if out.ctc is not None:
+            aux['CTCLoss'] = out.ctc.detach()
+        return self.scale_loss_grad(total), aux

@@ -2,14 +2,14 @@
 every hypothesis, one teacher-forced decoder pass over all of them and the N-best expected number of errors (Prabhavalkar et al. 2018;
 include/otrans_hip.h otr_mwer_loss) with its gradient -- no copy to the host anywhere in the step."""
 import torch
-import torch.nn as nn
 
 from . import ops
+from .model import ModelTraining, evaluating
 from .nn import BOS, EOS
 from .recognize import SpeechToTextRecognizer
 
 
-class MWERTraining(nn.Module):
+class MWERTraining(ModelTraining):
     """Wraps a SpeechToText as the submodule `model` (FusedAdam / FlatDataParallel see the same parameters under `model.`);
     forward(inputs, targets, hyps=None) -> (loss, aux) with loss = MWER + ce_weight * the model's own cross-entropy.
 
@@ -28,35 +28,18 @@ class MWERTraining(nn.Module):
             raise ValueError('MWERTraining: nbest=%d must be in [1, %d]' % (nbest, ops.MWER_MAX_NBEST))
         if max_len < 1 or ce_weight < 0:
             raise ValueError('MWERTraining: max_len=%r must be >= 1 and ce_weight=%r >= 0' % (max_len, ce_weight))
-        modes = [(m, m.training) for m in model.modules()]
         self.model = model
         self.nbest, self.max_len, self.ce_weight = int(nbest), int(max_len), float(ce_weight)
         if recognizer is None:
             search_kw.setdefault('apply_cache', False)
-            recognizer = SpeechToTextRecognizer(model, beam_width=beam_width or nbest, nbest=nbest, max_len=max_len, **search_kw)
+            with evaluating(model):                       # the recognizer's constructor puts the model into eval()
+                recognizer = SpeechToTextRecognizer(model, beam_width=beam_width or nbest, nbest=nbest, max_len=max_len, **search_kw)
         self.recognizer = recognizer
-        for m, was in modes:                              # the recognizer's constructor put the model into eval()
-            m.training = was
-
-    def save_checkpoint(self, params, name):
-        return self.model.save_checkpoint(params, name)
-
-    def load_model(self, chkpt):
-        return self.model.load_model(chkpt)
-
-    def set_epoch(self, epoch):
-        return self.model.set_epoch(epoch)
 
     def search(self, inputs, inputs_mask):
         """the recognizer's n-best (tokens int64 [B, N, L], lengths int32 [B, N]) with the model in eval() for the duration"""
-        modes = [(m, m.training) for m in self.model.modules()]
-        self.model.eval()
-        try:
-            with torch.no_grad():
-                tokens, lengths, _ = self.recognizer.recognize_tokens(inputs, inputs_mask)
-        finally:
-            for m, was in modes:
-                m.training = was
+        with evaluating(self.model), torch.no_grad():
+            tokens, lengths, _ = self.recognizer.recognize_tokens(inputs, inputs_mask)
         return tokens, lengths
 
     def forward(self, inputs, targets, hyps=None):
@@ -75,26 +58,17 @@ class MWERTraining(nn.Module):
         rows = min(self.max_len, L + 1)
         ys_in, ys_out, n_rows = ops.rescore_pack(tokens, lengths, torch.zeros((B, N), dtype=torch.float32, device=tokens.device), rows,
                                                  V, BOS, EOS)
-        x, mask = model.frontend(enc_inputs, enc_mask)
-        memory, memory_mask, _ = model.encoder(x, mask)
-        memory = ops.early_mark(memory, model)            # decoder and loss finish their backward before the encoder's starts (dp.py)
+        memory, memory_mask = model.encode(enc_inputs, enc_mask, mark=True)
         hidden = model.decoder.hidden(ys_in, memory, memory_mask, share=N)
         logits = ops.linear(hidden, model.decoder.output_layer.weight, model.decoder.output_layer.bias)
         mwer, stats = ops.mwer_loss(logits, ys_out, n_rows, errors)
         total, ce = mwer, None
         if self.ce_weight > 0:
-            if truth.is_cuda and truth.stride(-1) == 1:
-                dec_in, target_out = truth[:, :-1], truth[:, 1:]          # read in place, as SpeechToText.forward does
-            else:
-                shifted = torch.stack((truth[:, :-1], truth[:, 1:]))
-                dec_in, target_out = shifted[0], shifted[1]
-            ce_logits, _ = model.decoder(dec_in, memory, memory_mask)
-            ce = model.crit(ce_logits, target_out)
+            ce = model.teacher_forced(memory, memory_mask, targets, ctc=False).ce     # no CTC term: the targets are read in place
             total = mwer + self.ce_weight * ce
-        owner = self if getattr(self, '_otr_loss_scale', None) is not None else model
         valid = errors >= 0
         oracle = torch.where(valid, errors, torch.full_like(errors, torch.iinfo(torch.int32).max)).min(dim=1).values
         aux = {'MWER': mwer.detach(), 'CE': ce.detach() if ce is not None else torch.zeros_like(mwer.detach()),
                'errors_1best': errors[:, 0], 'errors_oracle': torch.where(valid.any(dim=1), oracle, torch.full_like(oracle, -1)),
                'post': stats['post']}
-        return ops.scale_loss_grad(total, owner), aux
+        return self.scale_loss_grad(total), aux

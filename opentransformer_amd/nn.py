@@ -756,9 +756,12 @@ class LabelSmoothingLoss(nn.Module):
         super().__init__()
         self.size, self.smoothing, self.padding_idx, self.normalize_length = size, smoothing, padding_idx, normalize_length
 
-    _otr_grad_scale = None
-
     def forward(self, logits, target, mask=None):
+        return self.root(logits, target, None, mask)
+
+    def root(self, logits, target, grad_scale, mask=None):
+        """forward() as the root of a backward pass (its own method: forward keeps the reference's signature).  grad_scale: the
+        device scalar that pass is seeded with (fp16 loss scale) or None; the fused loss launch folds it into the gradient."""
         assert logits.dim() == 3 and logits.size(-1) == self.size
         if mask is not None:          # a masked row contributes nothing, exactly like a PAD row (loss.py:31-35,45-46)
             target = target.masked_fill(mask.bool(), self.padding_idx)
@@ -766,8 +769,5 @@ class LabelSmoothingLoss(nn.Module):
             loss = ops.LabelSmoothingLossFn.apply(logits.float(), target, float(self.smoothing), int(self.padding_idx))
             kept = (target != self.padding_idx).sum().to(loss.dtype)
             loss = loss * (kept / target.numel())
-            return ops.ScaleGradFn.apply(loss, self._otr_grad_scale) if self._otr_grad_scale is not None and loss.requires_grad else loss
-        # _otr_grad_scale: set by the model around its call (an attribute, not an argument: forward keeps the reference's signature) --
-        # the device scalar its backward pass is seeded with (fp16 loss scale); the fused loss launch folds it into the gradient
-        return ops.label_smoothing_loss(logits.float(), target, float(self.smoothing), int(self.padding_idx),
-                                        grad_scale=self._otr_grad_scale)
+            return ops.ScaleGradFn.apply(loss, grad_scale) if grad_scale is not None and loss.requires_grad else loss
+        return ops.label_smoothing_loss(logits.float(), target, float(self.smoothing), int(self.padding_idx), grad_scale=grad_scale)

@@ -169,11 +169,7 @@ class RecurrentLanguageModel(nn.Module):
                 x = ops.dropout(x, p, self.training)
             x = ops.lstm_layer(x, *self._layer_params(k))
         logits = ops.linear(x, self.output_project.weight, self.output_project.bias)
-        self.crit._otr_grad_scale = ops.loss_scale_of(self)
-        try:
-            return self.crit(logits, target.t()), None
-        finally:
-            self.crit._otr_grad_scale = None
+        return self.crit.root(logits, target.t(), ops.loss_scale_of(self)), None
 
     def save_checkpoint(self, params, name):
         torch.save({'params': params, 'model': self.state_dict()}, name)
