@@ -40,7 +40,7 @@ extern "C" {
  * bump; 602: the rescoring entries, additions only; 603: otr_ctc_align, additions only; 604: otr_ngram_lookup and otr_ctc_beam_search_lm, additions only; 605:
  * otr_edit_distance, additions only; 606: otr_ngram_score_cands, otr_ngram_score_seqs and otr_rescore_select_add, additions only; 607: otr_ngram_count, otr_ngram_stats and otr_ngram_estimate, additions only;
  * 608: otr_mwer_workspace_floats and otr_mwer_loss, additions only; still 608: otr_feature_prepare_workspace_bytes, otr_feature_prepare and
- * otr_cmvn_accumulate, after them otr_ctc_segment_workspace_bytes and otr_ctc_segment, and after those otr_distill_workspace_floats and otr_distill_loss (additions only), were added without a bump -- no existing signature, structure or meaning changed, and a binding that needs them
+ * otr_cmvn_accumulate, after them otr_ctc_segment_workspace_bytes and otr_ctc_segment, and after those otr_distill_workspace_floats and otr_distill_loss (additions only), and last otr_bias_score_cands and otr_bias_score_seqs (additions only), were added without a bump -- no existing signature, structure or meaning changed, and a binding that needs them
  * fails on the missing symbol of an older library when it loads it).  A binding compares otr_version() with the OTR_ABI_VERSION it was written against BEFORE its first call and refuses a
  * library that answers anything else: descriptors are passed by pointer and read at the library's idea of their size. */
 #define OTR_ABI_VERSION 608
@@ -945,6 +945,53 @@ int32_t otr_rescore_select_add(const int64_t* tokens, const int32_t* out_len, co
                                const float* att_score, const float* lm_score, const float* add_score, int32_t B, int32_t W, int32_t T,
                                int32_t nbest, float ctc_weight, float lm_weight, float penalty, float lamda, float* total, int32_t* perm,
                                int64_t* nbest_tokens, int32_t* nbest_len, float* nbest_score, void* stream);
+
+/* ---- phrase biasing (hotwords) for the attention, joint and two-pass decoders (SpeechToTextRecognizer bias=...; opentransformer_amd/
+ *      bias.py PhraseBias builds the table), csrc/bias.hip.  f32 and integers only: the same code in every build.
+ * Phrase set: n sequences of unit ids, each of 1 .. BIAS_MAX_LEN = 16 ids in [0, V), none of them EOS, V <= 8192; phrase i has a
+ *   weight w_i >= 0, finite, earned per token.
+ * Trie: one node per distinct phrase prefix, the root = the empty prefix = node 0.  Per node u:
+ *   tok(u)       = the maximum of w_i over the phrases that pass through the edge into u;
+ *   end(u)       = some phrase ends at u;
+ *   psi_minus(u) = the sum of tok along root -> u, counted from just behind the last end node strictly above u (from the root where
+ *                  there is none), added in f32 from the root towards the leaf;
+ *   psi(u)       = end(u) ? 0 : psi_minus(u);  the root has psi_minus = psi = 0.
+ * state(x) of a token string x = the longest suffix of x that is a node (the root where none is).  Its depth is at most 16, so the
+ *   last 16 tokens of x decide it.  An id outside [0, V) is a token in no phrase.
+ * Addend of extending hypothesis g by candidate c:  a(g, c) = psi_minus(state(g c)) - psi(state(g)), ONE f32 subtraction.  EOS is in
+ *   no phrase, so state(g EOS) is the root and a = -psi(state(g)): a partial match is refunded.  Hence the addends of a string x sum to
+ *   (the psi_minus(v) of every step that landed on an end node v) + psi(state(x)), and with the EOS step to the first term alone: a
+ *   finished hypothesis carries its completed phrases, >= 0, however the search reached it.
+ *   No output links: a phrase that ends strictly inside a longer partial match of another phrase is credited only if the state itself
+ *   is its end node.  That is the rule, not an omission to repair with a second rule.
+ *   Column 0 of a prefix row is BOS by POSITION and is not a token (BOS == EOS here), as in otr_ngram_score_cands.
+ * Table: `capacity` entries of 16 bytes (capacity a power of two >= 2, the base 16-byte aligned), one per edge (u, token) -> child:
+ *   u32 u + 1 (0 = an empty entry), u32 token | end(child) << 31, u32 child, f32 psi_minus(child).  Open addressing, linear probing
+ *   from hash(u << 16 | token) & (capacity - 1) (the 64-bit mix of csrc/bias.hip bs_hash); a chain ends at the edge, at an empty entry
+ *   or after max_probe entries (the longest chain of the build).  n_nodes = the nodes incl. the root (n_nodes - 1 edges are stored);
+ *   max_len = the longest phrase.  A node number is only ever compared, never used as an index.
+ * otr_bias_score_cands: the twin of otr_ngram_score_cands -- preds, ldp, t / pos, flags, cand_idx, cand_score, rows, K', cand_out,
+ *   cand_add, beam, k_score, k_idx as there, with the same rules: a row with flags != 0 is copied unchanged, its addend 0, its select
+ *   -inf / eos; a -inf score stays -inf; NaN ranks as -inf; ties -> the lower token, then the lower slot; cand_out = cand_score + a
+ *   is one f32 addition and may alias cand_score.  K' <= 32, beam <= min(16, K').  A row owns 32 lanes, 8 rows per workgroup: lane
+ *   j <= 16 walks the last j tokens from the root, the lanes that arrive are the suffix chain of state(g); each candidate lane then
+ *   asks for child(n_j, c) from the deepest j down.  One launch, no allocation, memset, atomics, LDS or host synchronisation.
+ * otr_bias_score_seqs: the twin of otr_ngram_score_seqs -- tokens int64 [n_hyp, T] (an id < 0 or >= V inside the length is a token in
+ *   no phrase; whatever lies behind the length is not read), out_len int32 [n_hyp].  out f32 [n_hyp] = the summed addends of h EOS for
+ *   every slot with 0 <= out_len <= T (0 otherwise).  Summation order: one wave per hypothesis; lane i adds the addends of the
+ *   positions l = i, i + 64, .. (position out_len is EOS) in ascending l, starting from 0; then the 64 lane sums are combined by the
+ *   butterfly v_i += v_(i xor o) for o = 32, 16, 8, 4, 2, 1.  The same bits on every run.
+ * Both refuse (< 0, otr_last_error_string() names the argument) before the launch: a null pointer, K', beam, t / ldp, eos and V outside
+ *   their limits, a capacity that is no power of two, a table that is not 16-byte aligned, max_probe outside [1, capacity], n_nodes
+ *   outside [2, capacity + 1], max_len outside [1, 16].  rows == 0 / n_hyp == 0 returns 0 without a launch. */
+#define OTR_BIAS_MAX_LEN 16
+int32_t otr_bias_score_cands(const void* table, int64_t capacity, int32_t max_probe, int32_t n_nodes, int32_t max_len, int32_t V,
+                             const int64_t* preds, int64_t ldp, int32_t t, const int32_t* pos, const uint8_t* flags,
+                             const int32_t* cand_idx, const float* cand_score, int64_t rows, int32_t K, int32_t eos, float* cand_out,
+                             float* cand_add, int32_t beam, float* k_score, int64_t* k_idx, void* stream);
+int32_t otr_bias_score_seqs(const void* table, int64_t capacity, int32_t max_probe, int32_t n_nodes, int32_t max_len, int32_t V,
+                            const int64_t* tokens, const int32_t* out_len, int64_t n_hyp, int32_t T, int32_t eos, float* out,
+                            void* stream);
 
 /* ---- n-gram LM estimation (NGramLM.train: interpolated modified Kneser-Ney from unit-id sentences, the ARPA file the entries above
  *      start from), csrc/ngramtrain.hip.  Integers, f32 and f64 only: the same code in every build.  Order N in [1, 4], V in [1, 8192].

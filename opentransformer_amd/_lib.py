@@ -227,6 +227,8 @@ SIGNATURES = {
     'otr_ngram_score_cands': [_P, _I64, _I32, _I32, _I32, _P, _I64, _I32, _P, _P, _P, _P, _I64, _I32, _F32, _F32, _F32, _I32, _P, _P, _I32,
                               _P, _P, _P],
     'otr_ngram_score_seqs': [_P, _I64, _I32, _I32, _I32, _P, _P, _I64, _I32, _F32, _F32, _F32, _I32, _P, _P, _P],
+    'otr_bias_score_cands': [_P, _I64, _I32, _I32, _I32, _I32, _P, _I64, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _I32, _P, _P, _P],
+    'otr_bias_score_seqs': [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _I64, _I32, _I32, _P, _P],
     'otr_ngram_count': [_P, _I64, _P, _I64, _I32, _I32, _I32, _I32, _P, _I64, _P, _P],
     'otr_ngram_stats': [_P, _I64, _I32, _I32, _P, _P, _P],
     'otr_ngram_estimate': [_P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],

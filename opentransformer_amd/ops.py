@@ -3716,6 +3716,60 @@ def ngram_score_sequences(ngram, tokens, out_len, alpha=1.0, beta=0.0, eos=1, wi
     return (out, logp) if with_logp else out
 
 
+# ------------------------------------------------------------------ phrase biasing (csrc/bias.hip)
+def _bias_args(bias, dev):
+    """the table arguments both phrase-biasing entries take, in the order of include/otrans_hip.h"""
+    return _p(bias.device_table(dev)), bias.capacity, bias.max_probe, bias.n_nodes, bias.max_len, bias.vocab_size
+
+
+def bias_score_candidates(bias, preds, cand_idx, cand_score, eos, t=0, pos=None, flags=None, beam=0, cand_out=None, with_add=False,
+                          k_score=None, k_idx=None):
+    """The phrase-biasing addend of the pre-beam candidates (include/otrans_hip.h otr_bias_score_cands), the twin of
+    ngram_score_candidates with a bias.PhraseBias in the n-gram's place: preds int64 [R, ldp] (row r's prefix is preds[r, :t], t = pos + 1
+    with pos a device int32 scalar, when given; column 0 stands for BOS and is no token), cand_idx int32 / cand_score f32 [R, K'], flags
+    u8 [R] marks finished rows (copied unchanged).  cand_out (default: a new tensor; may be cand_score itself) = cand_score +
+    psi_minus(state(g c)) - psi(state(g)).  beam > 0: also the top-`beam` of each row in the prune's layout.  Returns (cand_out, cand_add
+    or None, k_score, k_idx).  One launch on the current stream, no host synchronisation: capturable (call bias.to(device) before)."""
+    _cuda(preds, cand_idx, cand_score, pos, flags)
+    if preds.dtype != torch.int64 or cand_idx.dtype != torch.int32 or cand_score.dtype != torch.float32:
+        raise L.OtransHipError('bias_score_candidates: preds int64, cand_idx int32, cand_score f32 expected')
+    if preds.dim() != 2 or preds.stride(1) != 1 or cand_idx.shape != cand_score.shape or not cand_idx.is_contiguous() \
+            or not cand_score.is_contiguous() or cand_idx.shape[0] != preds.shape[0]:
+        raise L.OtransHipError('bias_score_candidates: preds [R, ldp] and contiguous cand_idx / cand_score [R, K] expected, got %s %s %s'
+                               % (tuple(preds.shape), tuple(cand_idx.shape), tuple(cand_score.shape)))
+    R, K = cand_idx.shape
+    dev = preds.device
+    if cand_out is None:
+        cand_out = torch.empty_like(cand_score)
+    add = torch.empty_like(cand_score) if with_add else None
+    beam = int(beam)
+    if beam > 0 and k_score is None:
+        k_score = torch.empty((R, beam), dtype=torch.float32, device=dev)
+        k_idx = torch.empty((R, beam), dtype=torch.int64, device=dev)
+    L.check(L.load().otr_bias_score_cands(*_bias_args(bias, dev), _p(preds), preds.stride(0), int(t), _p(pos) if pos is not None else None,
+                                          _p(flags) if flags is not None else None, _p(cand_idx), _p(cand_score), R, K, int(eos),
+                                          _p(cand_out), _p(add) if add is not None else None, beam, _p(k_score) if beam > 0 else None,
+                                          _p(k_idx) if beam > 0 else None, _stream()), 'otr_bias_score_cands')
+    return cand_out, add, k_score, k_idx
+
+
+def bias_score_sequences(bias, tokens, out_len, eos=1):
+    """The phrase-biasing score of whole hypotheses (include/otrans_hip.h otr_bias_score_seqs): tokens int64 [..., T] (negative =
+    padding), out_len int32 [...] lengths -> f32 [...] = the summed addends of h + EOS: what the completed phrases of h earned.  One
+    launch on the current stream, the same bits on every run, capturable."""
+    _cuda(tokens, out_len)
+    if tokens.dtype != torch.int64 or tokens.shape[:-1] != out_len.shape:
+        raise L.OtransHipError('bias_score_sequences: tokens int64 [..., T] and out_len [...] expected, got %s %s %s'
+                               % (tokens.dtype, tuple(tokens.shape), tuple(out_len.shape)))
+    T = tokens.shape[-1]
+    tok, ln = tokens.contiguous(), out_len.to(torch.int32).contiguous()
+    dev = tokens.device
+    out = torch.empty(out_len.shape, dtype=torch.float32, device=dev)
+    L.check(L.load().otr_bias_score_seqs(*_bias_args(bias, dev), _p(tok) if T else None, _p(ln), ln.numel(), T, int(eos), _p(out),
+                                         _stream()), 'otr_bias_score_seqs')
+    return out
+
+
 NGRAM_TRAIN_ERRORS = {1: 'the count table is full', 2: 'an id inside a sentence is outside [1, V) or is the </s> unit',
                       4: 'a sentence length is outside [0, L]', 8: 'a context or a suffix is missing from the count table'}
 

@@ -24,6 +24,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
+from .bias import PhraseBias
 from .ngram import NGramLM
 from .nn import (BOS, EOS, PAD, LabelSmoothingLoss, PositionalEncoding, TransformerEncoderLayer)
 
@@ -369,7 +370,8 @@ class _JointCTC:
 class _BeamState:
     """The beams of one search over R = B * beam hypotheses, for both decode loops: ping-pong prefixes / scores / finished flags (a
     step reads phase cur and writes phase cur ^ 1 only), the per-row top-beam the scoring hands to the prune, the finished counter and,
-    where the recognizer asks for them, the joint search's state and the pinned n-gram LM with the plain search's pre-beam candidates.
+    where the recognizer asks for them, the joint search's state and the pinned n-gram LM / phrase table with the plain search's pre-beam
+    candidates.
     cached: the counter is [finished hypotheses, the prune kernel's arrival word] per phase, as otr_beam_prune_cached takes it -- the
     count of a step stays readable while the next step runs (CachedBeamState.run) --, else the one count of otr_beam_prune."""
 
@@ -389,9 +391,12 @@ class _BeamState:
         self.score0 = torch.tensor([0.0] + [-float('inf')] * (beam - 1), device=dev).repeat([b]).contiguous()
         self.joint = _JointCTC(b, Tm, self.V, rec.ctc_beam, beam, dev) if rec.joint_ctc else None
         self.ngram = rec.ngram_lm.to(dev) if rec.ngram_lm is not None else None     # pinned: a cached state's key holds its table's address
+        self.bias = rec.bias.to(dev) if rec.bias is not None else None              # pinned likewise
         self.cand = None
-        if self.ngram is not None and self.joint is None:      # the plain search with an n-gram: pre-beam + addend + select, no full top-k
-            self.cand = (new((R, rec.ngram_beam), torch.float32), new((R, rec.ngram_beam), torch.int32))
+        if (self.ngram is not None or self.bias is not None) and self.joint is None:
+            # the plain search with an n-gram or phrases: pre-beam + addend(s) + select, no full top-k
+            K = rec.ngram_beam if self.ngram is not None else rec.bias_beam
+            self.cand = (new((R, K), torch.float32), new((R, K), torch.int32))
 
     def reset(self):
         """the start of a search in phase 0: BOS alone in every prefix, one live hypothesis per utterance, nothing finished"""
@@ -417,13 +422,21 @@ class _BeamState:
             if self.ngram is not None:                    # the prefix score ranks by counting, in any order
                 ops.ngram_score_candidates(self.ngram, preds[cur], j.cand_i, j.cand_s, rec.alpha, rec.beta, EOS, t=t, pos=p_cur,
                                            flags=flags[cur], cand_out=j.cand_s)
+            if self.bias is not None:                     # behind the n-gram's addend, in place as well
+                ops.bias_score_candidates(self.bias, preds[cur], j.cand_i, j.cand_s, EOS, t=t, pos=p_cur, flags=flags[cur],
+                                          cand_out=j.cand_s)
             ops.ctc_prefix_score(j.lp, j.lengths, j.cand_i, preds[cur], t, beam, rec.model.assistor.blank, EOS, j.jsrc[cur], j.state[cur],
                                  j.state[nxt], pos=p_cur, cand_score=j.cand_s, ctc_weight=lam, beam=beam, flags=flags[cur],
                                  k_score=self.k_score, k_idx=self.k_idx, k_src=j.k_src)
-        elif self.cand is not None:                       # the n-gram alone: pre-beam + addend + select in otr_beam_topk's place
-            ops.joint_prebeam(logits, lm_logits, 1.0, lm_weight, rec.ngram_beam, V, *self.cand)
-            ops.ngram_score_candidates(self.ngram, preds[cur], self.cand[1], self.cand[0], rec.alpha, rec.beta, EOS, t=t, pos=p_cur,
-                                       flags=flags[cur], beam=beam, cand_out=self.cand[0], k_score=self.k_score, k_idx=self.k_idx)
+        elif self.cand is not None:                       # pre-beam + addend(s) + select in otr_beam_topk's place: the last scorer selects
+            select = dict(beam=beam, k_score=self.k_score, k_idx=self.k_idx)
+            ops.joint_prebeam(logits, lm_logits, 1.0, lm_weight, self.cand[0].shape[1], V, *self.cand)
+            if self.ngram is not None:
+                ops.ngram_score_candidates(self.ngram, preds[cur], self.cand[1], self.cand[0], rec.alpha, rec.beta, EOS, t=t, pos=p_cur,
+                                           flags=flags[cur], cand_out=self.cand[0], **({} if self.bias is not None else select))
+            if self.bias is not None:
+                ops.bias_score_candidates(self.bias, preds[cur], self.cand[1], self.cand[0], EOS, t=t, pos=p_cur, flags=flags[cur],
+                                          cand_out=self.cand[0], **select)
         else:
             L.check(lib.otr_beam_topk(_ptr(logits), logits.stride(0), _ptr(lm_logits), lm_logits.stride(0) if lm_logits is not None else V,
                                       lm_weight, self.R, V, beam, _ptr(self.k_score), _ptr(self.k_idx), stream), 'otr_beam_topk')
@@ -503,16 +516,29 @@ class SpeechToTextRecognizer(Recognizer):
     (ngram_beam defaults to min(V, int(1.5 * beam_width)); limits beam_width <= 16, beam_width <= ngram_beam <= min(V, 32), V <= 8192),
     which replace otr_beam_topk's full-vocabulary top-k.  With rescore=True the n-gram is fused into the first pass
     (ops.ctc_prefix_beam_search_lm) and the second pass adds the hypothesis's n-gram score, computed afresh with its </s> term
-    (otr_ngram_score_seqs), to the total.  alpha / beta default as in CTCRecognizer.  A path is not loaded here (build_recognizer does)."""
+    (otr_ngram_score_seqs), to the total.  alpha / beta default as in CTCRecognizer.  A path is not loaded here (build_recognizer does).
+    bias: None, or a bias.PhraseBias over the decoder's V units (phrase biasing, "hotwords"; include/otrans_hip.h otr_bias_score_cands
+    states the rule).  In the step loops every pre-beam candidate c of hypothesis g gains psi_minus(state(g c)) - psi(state(g)) -- the
+    per-token weight while g c spells on at a phrase, the refund of an unfinished match where it stops -- behind the n-gram's addend, if
+    any: in the joint search on the ctc_beam candidates, in the plain search on the K' tokens of highest att + lm, K' = ngram_beam
+    where an n-gram LM is given (a bias_beam that differs from it is refused), else bias_beam (default min(V, int(1.5 * beam_width)),
+    the pre-beam's limits).  ONLY pre-beam candidates are boosted: a phrase continuation the pre-beam dropped is not brought back;
+    raise K' (up to 32) for deeper reach.  With rescore=True the first pass (the CTC prefix beam search) is NOT biased: the second pass
+    adds the phrase score of each hypothesis (otr_bias_score_seqs; res['bias']) to the total, beside the n-gram's, so phrases re-rank
+    the n-best and no more."""
 
     def __init__(self, model, lm=None, lm_weight=0.1, ctc_weight=0.0, beam_width=5, nbest=1, max_len=50,
                  idx2unit=None, penalty=0, lamda=5, ngpu=1, apply_cache=False, joint_ctc=False, ctc_beam=None, rescore=False,
-                 cutoff_top_n=40, ngram_lm=None, alpha=0.1, beta=0.0, ngram_beam=None):
+                 cutoff_top_n=40, ngram_lm=None, alpha=0.1, beta=0.0, ngram_beam=None, bias=None, bias_beam=None):
         super().__init__(model, idx2unit, lm, lm_weight, ngpu)
         if ngram_lm is not None and not isinstance(ngram_lm, NGramLM):
             raise NotImplementedError('SpeechToTextRecognizer: ngram_lm must be an NGramLM, not %s: load the ARPA file with '
                                       'NGramLM.from_arpa(path, idx2unit) (KenLM binaries are not read)' % type(ngram_lm).__name__)
         self.ngram_lm, self.alpha, self.beta, self.ngram_beam = ngram_lm, float(alpha), float(beta), None
+        if bias is not None and not isinstance(bias, PhraseBias):
+            raise TypeError('SpeechToTextRecognizer: bias must be a PhraseBias, not %s: build one with PhraseBias(phrases, vocab_size) or '
+                            'PhraseBias.from_texts(lines, idx2unit)' % type(bias).__name__)
+        self.bias, self.bias_beam = bias, None
         self.rescore, self.cutoff_top_n = bool(rescore), int(cutoff_top_n)
         if self.rescore:
             if joint_ctc or apply_cache:
@@ -529,7 +555,7 @@ class SpeechToTextRecognizer(Recognizer):
         self.beam_width, self.max_len, self.nbest = beam_width, max_len, nbest
         self.penalty, self.lamda, self.ctc_weight, self.lm_weight = penalty, lamda, ctc_weight, lm_weight
         self.joint_ctc, self.ctc_beam = bool(joint_ctc), None
-        V = model.decoder.output_layer.weight.shape[0] if self.joint_ctc or ngram_lm is not None else None
+        V = model.decoder.output_layer.weight.shape[0] if self.joint_ctc or ngram_lm is not None or bias is not None else None
         if self.joint_ctc:
             if getattr(model, 'assistor', None) is None:
                 raise ValueError('joint_ctc=True needs the model\'s CTC head (model.assistor): build the model with ctc_weight > 0')
@@ -542,6 +568,18 @@ class SpeechToTextRecognizer(Recognizer):
             _vocab_limit('ngram_lm', V)
             if not self.rescore and not self.joint_ctc:       # the plain search pre-beams too (the joint search's limits are checked above)
                 self.ngram_beam = _prebeam_limits('ngram_lm', 'ngram_beam', beam_width, ngram_beam, V)
+        if bias is not None:
+            if bias.vocab_size != V:
+                raise ValueError('bias: the phrases were built for %d units, the decoder has V=%d' % (bias.vocab_size, V))
+            _vocab_limit('bias', V)
+            if not self.rescore and not self.joint_ctc:       # the plain search pre-beams: with the n-gram's K' where there is one
+                if self.ngram_beam is not None:
+                    if bias_beam is not None and int(bias_beam) != self.ngram_beam:
+                        raise ValueError('bias: bias_beam=%d differs from ngram_beam=%d: the two scorers share one pre-beam'
+                                         % (bias_beam, self.ngram_beam))
+                    self.bias_beam = self.ngram_beam
+                else:
+                    self.bias_beam = _prebeam_limits('bias', 'bias_beam', beam_width, bias_beam, V)
         self.attn_weights = {}
         self.apply_cache = bool(apply_cache)
         self.use_hipgraph = True
@@ -628,6 +666,8 @@ class SpeechToTextRecognizer(Recognizer):
                self.ctc_beam)
         if self.ngram_lm is not None:                        # a changed n-gram LM never replays a stale graph (the state pins its table)
             key += (self.ngram_lm.device_table(memory.device).data_ptr(), self.ngram_lm.capacity, self.alpha, self.beta, self.ngram_beam)
+        if self.bias is not None:                            # nor does a changed phrase set
+            key += (self.bias.device_table(memory.device).data_ptr(), self.bias.capacity, self.bias.n_nodes, self.bias_beam)
         st = self._cached_states.get(key)
         if st is None:
             if len(self._cached_states) >= 4:                # a few shapes; each holds caches + two graphs
@@ -667,6 +707,10 @@ class SpeechToTextRecognizer(Recognizer):
             tokens, out_len, scores, lm_scores = ops.ctc_prefix_beam_search_lm(log_probs, lengths, ng, self.alpha, self.beta, **kw)
             ctc = scores - lm_scores
             ng_score = ops.ngram_score_sequences(ng, tokens, out_len, self.alpha, self.beta, eos=EOS)
+        add_score, bias_score = ng_score, None
+        if self.bias is not None:                         # the phrases re-rank the n-best: the first pass above is not biased
+            bias_score = ops.bias_score_sequences(self.bias, tokens, out_len, eos=EOS)
+            add_score = bias_score if ng_score is None else ng_score + bias_score
         packed = ops.rescore_pack(tokens, out_len, scores, self.max_len, V, BOS, EOS)
         ys_in = packed[0]
         out_dec, out_lm = self._rescore_outputs()
@@ -674,9 +718,10 @@ class SpeechToTextRecognizer(Recognizer):
         lm_logits = _lm_logits(lm, ys_in, out=out_lm, every=True)
         res = ops.attention_rescore(logits, tokens, out_len, ctc, self.max_len, V, self.ctc_weight, lm_logits=lm_logits,
                                     lm_weight=float(self.lm_weight or 0.0) if lm is not None else 0.0, nbest=self.nbest,
-                                    penalty=self.penalty, lamda=self.lamda, packed=packed, bos=BOS, eos=EOS, add_score=ng_score)
+                                    penalty=self.penalty, lamda=self.lamda, packed=packed, bos=BOS, eos=EOS, add_score=add_score)
         res['beam'] = (tokens, out_len, scores)           # the first pass, in CTC order
         res['ctc'], res['ng'] = ctc, ng_score             # the terms of total beside att / lm (ng: None without an n-gram LM)
+        res['bias'] = bias_score                          # ... and the phrase score (None without a PhraseBias)
         return res
 
     def _rescore(self, inputs, inputs_mask):
@@ -1151,12 +1196,18 @@ def build_recognizer(model_type, model, lm, args, idx2unit):
         if isinstance(ngram_lm, str):
             ngram_lm = NGramLM.from_arpa(ngram_lm, idx2unit)
         kw = {k: getattr(args, k) for k in ('alpha', 'beta') if hasattr(args, k)}
+        bias = getattr(args, 'bias_phrases', None)
+        if isinstance(bias, str):                                               # a text file: one phrase per line
+            with open(bias, encoding='utf-8') as f:
+                bias = PhraseBias.from_texts(f, idx2unit, score=getattr(args, 'bias_score', 2.0),
+                                             vocab_size=model.decoder.output_layer.weight.shape[0])
         return SpeechToTextRecognizer(model=model, lm=lm, lm_weight=args.lm_weight, ctc_weight=args.ctc_weight,
                                       beam_width=args.beam_width, nbest=args.nbest, max_len=args.max_len,
                                       idx2unit=idx2unit, penalty=args.penalty, lamda=args.lamda, ngpu=args.ngpu,
                                       joint_ctc=getattr(args, 'joint_ctc', False), ctc_beam=getattr(args, 'ctc_beam', None),
                                       rescore=getattr(args, 'rescore', False), ngram_lm=ngram_lm,
-                                      ngram_beam=getattr(args, 'ngram_beam', None), **kw)
+                                      ngram_beam=getattr(args, 'ngram_beam', None), bias=bias,
+                                      bias_beam=getattr(args, 'bias_beam', None), **kw)
     if model_type == 'ctc':
         ngram_lm = args.ngram_lm
         if isinstance(ngram_lm, str):                                           # the reference passes the path on to ctcdecode
