@@ -40,7 +40,7 @@ extern "C" {
  * bump; 602: the rescoring entries, additions only; 603: otr_ctc_align, additions only; 604: otr_ngram_lookup and otr_ctc_beam_search_lm, additions only; 605:
  * otr_edit_distance, additions only; 606: otr_ngram_score_cands, otr_ngram_score_seqs and otr_rescore_select_add, additions only; 607: otr_ngram_count, otr_ngram_stats and otr_ngram_estimate, additions only;
  * 608: otr_mwer_workspace_floats and otr_mwer_loss, additions only; still 608: otr_feature_prepare_workspace_bytes, otr_feature_prepare and
- * otr_cmvn_accumulate, after them otr_ctc_segment_workspace_bytes and otr_ctc_segment, and after those otr_distill_workspace_floats and otr_distill_loss (additions only), and last otr_bias_score_cands and otr_bias_score_seqs (additions only), were added without a bump -- no existing signature, structure or meaning changed, and a binding that needs them
+ * otr_cmvn_accumulate, after them otr_ctc_segment_workspace_bytes and otr_ctc_segment, and after those otr_distill_workspace_floats and otr_distill_loss (additions only), after those otr_bias_score_cands and otr_bias_score_seqs (additions only), and last otr_ctc_beam_search_bias (an addition only), were added without a bump -- no existing signature, structure or meaning changed, and a binding that needs them
  * fails on the missing symbol of an older library when it loads it).  A binding compares otr_version() with the OTR_ABI_VERSION it was written against BEFORE its first call and refuses a
  * library that answers anything else: descriptors are passed by pointer and read at the library's idea of their size. */
 #define OTR_ABI_VERSION 608
@@ -739,6 +739,33 @@ int32_t otr_ctc_beam_search_lm(const float* top_lp, const int32_t* top_tok, cons
                                int32_t K, int32_t blank, int32_t W, void* workspace, int64_t ws_bytes, int64_t* tokens,
                                int32_t* out_len, float* scores, const void* table, int64_t capacity, int32_t max_probe,
                                int32_t order, float alpha, float beta, float oov_score, float* lm_scores, void* stream);
+
+/* ---- phrase biasing (hotwords) fused into the CTC prefix beam search (CTCRecognizer bias=..., and the first pass of
+ *      SpeechToTextRecognizer rescore=True, bias_first_pass=True), csrc/ctcbeam.hip + csrc/bias.h.  f32 and integers only.
+ * The phrase table, state, psi_minus, psi and the 16-token window are those of the phrase-biasing section below (otr_bias_score_cands);
+ *   there is no EOS inside the search.  bias_table / bias_capacity / bias_max_probe / bias_max_len are checked as that section's
+ *   entries check them (16-byte aligned, a power of two, max_probe in [1, capacity], max_len in [1, 16]).
+ * otr_ctc_beam_search_bias: otr_ctc_beam_search (ngram_table == NULL: capacity .. oov_score are not looked at and lm_scores must be
+ *   NULL) or otr_ctc_beam_search_lm (ngram_table given, its arguments checked as there, lm_scores required), and in either case every
+ *   contribution to pnb'(s+c) gains the phrase addend a(s, c) = psi_minus(state(s c)) - psi(state(s)), ONE f32 subtraction, whether
+ *   the extension creates s+c or merges into an s+c already in the beam.  Order of the f32 additions of an extension:
+ *   ((acoustic + n-gram addend) + phrase addend); the merge adds (n-gram addend + phrase addend), formed once when the slot was made,
+ *   to its acoustic term.  Blank and repeat stays gain nothing.  The blank is never emitted and never enters a state; a unit that is
+ *   in no phrase leads to the root and refunds the open match (a negative addend).  Candidates, ranking, tie order and the per-slot
+ *   cut are the plain search's; the addends enter an extension's score before it is ranked.
+ *   After the last frame every live slot r loses psi(state(h_r)) -- an utterance that ends inside a phrase keeps no credit for it --
+ *   from scores and from bias_scores, and the live slots are ranked again by the refunded score (descending, ties -> the earlier
+ *   slot); tokens, out_len, scores, lm_scores and bias_scores are written in that order.  Hence bias_scores f32 [B, W] = the summed
+ *   addends of h_r + EOS, the quantity otr_bias_score_seqs computes, whatever path the search took: bit for bit where the weights
+ *   are dyadic (every sum exact), else within (len + 1) * 2^-24 * sum |a|.  0 for slots past the live beam.  scores - lm_scores -
+ *   bias_scores is the acoustic part.  All weights 0 gives the outputs of otr_ctc_beam_search / otr_ctc_beam_search_lm bit for bit.
+ *   The workspace is otr_ctc_beam_workspace_bytes, unchanged.  One launch, no allocation, no host synchronisation. */
+int32_t otr_ctc_beam_search_bias(const float* top_lp, const int32_t* top_tok, const int32_t* lengths, int32_t B, int32_t T, int32_t V,
+                                 int32_t K, int32_t blank, int32_t W, void* workspace, int64_t ws_bytes, int64_t* tokens,
+                                 int32_t* out_len, float* scores, const void* ngram_table /* NULL = no n-gram */, int64_t capacity,
+                                 int32_t max_probe, int32_t order, float alpha, float beta, float oov_score,
+                                 float* lm_scores /* NULL iff no n-gram */, const void* bias_table, int64_t bias_capacity,
+                                 int32_t bias_max_probe, int32_t bias_max_len, float* bias_scores, void* stream);
 
 /* ---- CTC forced alignment (token time stamps from the CTC head: what ctcdecode's `timesteps`, dropped at recognize/ctc.py:64, gives
  *      for the decoded string), csrc/ctcalign.hip.  The most probable CTC path of a KNOWN label sequence.  f32 in both builds.

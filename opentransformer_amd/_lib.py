@@ -210,6 +210,8 @@ SIGNATURES = {
     'otr_ngram_lookup': [_P, _I64, _I32, _I32, _I32, _P, _P, _P, _I64, _F32, _P, _P],
     'otr_ctc_beam_search_lm': [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P, _P, _P, _P, _I64, _I32, _I32, _F32, _F32,
                                _F32, _P, _P],
+    'otr_ctc_beam_search_bias': [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P, _P, _P, _P, _I64, _I32, _I32, _F32, _F32,
+                                 _F32, _P, _P, _I64, _I32, _I32, _P, _P],
     'otr_ctc_align_workspace_bytes': [_I32, _I32, _I32],
     'otr_ctc_align': [_P, _I64, _P, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P],
     'otr_ctc_segment_workspace_bytes': [_I32, _I32, _I32],

@@ -1,8 +1,10 @@
-"""Phrase biasing (hotwords, contextual biasing) for SpeechToTextRecognizer(bias=...): a list of unit-id phrases whose tokens the
-search boosts while a hypothesis spells one of them, and refunds when it leaves the phrase unfinished.
+"""Phrase biasing (hotwords, contextual biasing) for SpeechToTextRecognizer(bias=...) and CTCRecognizer(mode='beam', bias=...): a list
+of unit-id phrases whose tokens the search boosts while a hypothesis spells one of them, and refunds when it leaves the phrase
+unfinished.
 
 PhraseBias builds the phrases' trie and the hash table of its edges with numpy; include/otrans_hip.h states the semantics and the
-entry layout, csrc/bias.hip is the device side of this file.  walk_host / addend_host / score_host probe the very table the kernels
+entry layout, csrc/bias.hip is the device side of this file (csrc/bias.h the probe it shares with the CTC prefix beam search,
+ops.ctc_prefix_beam_search_bias).  walk_host / addend_host / score_host probe the very table the kernels
 probe, in the kernels' order; ops.bias_score_candidates / ops.bias_score_sequences do the same on the device."""
 import numpy as np
 

@@ -1,54 +1,20 @@
 // Phrase biasing (hotwords) for the attention, joint and two-pass decoders (SpeechToTextRecognizer bias=...).  opentransformer_amd/bias.py
 // builds the table; include/otrans_hip.h states the semantics.  f32 and integers only: the same code in both builds.
 //
-// Table: the edges (node, token) -> child of the phrases' trie, open addressing, linear probing, capacity a power of two, nothing is
-// ever deleted.  Entry (16 bytes): u32 node + 1 (0 = empty), u32 token | end(child) << 31, u32 child, f32 psi_minus(child).  What a
-// step needs of a node -- psi_minus, and psi = end ? 0 : psi_minus -- travels with the edge that reaches it, so a node number is only
-// ever a key, never an index: no probe can leave the table whatever it holds.  No failure links: the device walks goto edges only.
+// The table, its probe (bs_child) and the host check of its arguments are bias.h's, shared with the CTC prefix beam search.
 //  * bias_score_cands: a row owns 32 lanes.  Lane j <= 16 walks the last j tokens of the prefix from the root; the lanes that arrive
 //                      are the suffix chain of state(g), the deepest of them the state itself.  Each candidate lane then asks for
 //                      child(n_j, c) from the deepest j down: the first that exists is state(g c).
 //  * bias_score_seqs:  one wave per hypothesis, one lane per position; the lane finds the state behind its token, its left neighbour
 //                      hands over the state in front of it.  Lane sums, then the wave's butterfly: the same order on every run.
-#include "common.h"
+#include "bias.h"
 
 #define NEG_INF (-__builtin_huge_valf())
 
-constexpr int BS_MAXLEN = 16;     // BIAS_MAX_LEN: ids per phrase, the depth of the trie
 constexpr int BS_MAXV = 8192;
 constexpr int BS_MAXK = 32;       // the pre-beam's K'
 constexpr int BS_MAXBEAM = 16;    // the prune's limit
 constexpr int BS_ROWS = 8;        // hypothesis rows per workgroup: 32 lanes each
-
-struct BsTable {
-  const uint4* e;
-  uint32_t mask;        // capacity - 1
-  int max_probe;
-};
-
-__device__ __forceinline__ uint32_t bs_hash(uint32_t node, uint32_t tok) {   // bias.py _hash: the same arithmetic in numpy
-  uint64_t z = (((uint64_t)node << 16) | (uint64_t)tok) * 0x9e3779b97f4a7c15ull;
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  return (uint32_t)(z ^ (z >> 31));
-}
-
-// the edge (node, tok): true where it is stored, with the child, psi_minus(child) and end(child).  0 <= tok < 8192.
-__device__ __forceinline__ bool bs_child(const BsTable& t, uint32_t node, uint32_t tok, uint32_t& child, float& pm, bool& end) {
-  uint32_t pos = bs_hash(node, tok) & t.mask;
-  for (int p = 0; p < t.max_probe; ++p) {
-    const uint4 e = ld_global_b128(t.e + pos);
-    if (e.x == node + 1u && (e.y & 0x7fffffffu) == tok) {
-      child = e.z;
-      pm = __uint_as_float(e.w);
-      end = (e.y >> 31) != 0u;
-      return true;
-    }
-    if (e.x == 0u) return false;
-    pos = (pos + 1u) & t.mask;
-  }
-  return false;
-}
 
 __global__ __launch_bounds__(256) void bias_score_cands_kernel(BsTable tb, int max_len, int V, const int64_t* preds, int64_t ldp, int t_host,
                                                                const int32_t* pos, const uint8_t* flags, const int32_t* cand_idx,
@@ -115,16 +81,21 @@ __global__ __launch_bounds__(256) void bias_score_cands_kernel(BsTable tb, int m
   }
 }
 
-// host: the checks both entries share; -1 and the error string on a refusal
-static int32_t bias_check_table(const char* who, const void* table, int64_t capacity, int32_t max_probe, int32_t n_nodes, int32_t max_len,
-                                int32_t V) {
+// host: the checks every entry that takes a phrase table shares (bias.h); -1 and the error string on a refusal
+int32_t otr_bias_check_table(const char* who, const void* table, int64_t capacity, int32_t max_probe, int32_t max_len) {
   OTR_REQUIRE(table != nullptr, "%s: null table", who);
   OTR_REQUIRE(((uintptr_t)table & 15u) == 0, "%s: table must be 16-byte aligned", who);
   OTR_REQUIRE(capacity >= 2 && capacity <= (1ll << 31) && (capacity & (capacity - 1)) == 0,
               "%s: capacity=%lld must be a power of two in [2, 2^31]", who, (long long)capacity);
   OTR_REQUIRE(max_probe >= 1 && max_probe <= capacity, "%s: max_probe=%d must be in [1, capacity]", who, max_probe);
-  OTR_REQUIRE(n_nodes >= 2 && (int64_t)n_nodes - 1 <= capacity, "%s: n_nodes=%d must be in [2, capacity + 1]", who, n_nodes);
   OTR_REQUIRE(max_len >= 1 && max_len <= BS_MAXLEN, "%s: max_len=%d must be in [1, %d]", who, max_len, BS_MAXLEN);
+  return 0;
+}
+// the same plus the two arguments only this file's entries take
+static int32_t bias_check_table(const char* who, const void* table, int64_t capacity, int32_t max_probe, int32_t n_nodes, int32_t max_len,
+                                int32_t V) {
+  if (otr_bias_check_table(who, table, capacity, max_probe, max_len) < 0) return -1;
+  OTR_REQUIRE(n_nodes >= 2 && (int64_t)n_nodes - 1 <= capacity, "%s: n_nodes=%d must be in [2, capacity + 1]", who, n_nodes);
   OTR_REQUIRE(V >= 1 && V <= BS_MAXV, "%s: V=%d must be in [1, %d]", who, V, BS_MAXV);
   return 0;
 }

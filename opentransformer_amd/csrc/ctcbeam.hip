@@ -9,7 +9,12 @@
 //                     search, <true> (otr_ctc_beam_search_lm) adds the n-gram LM addend of include/otrans_hip.h to every
 //                     extension.  There a slot also carries its LM context (ids, the backoffs of its suffixes, an OOV mask),
 //                     the addend of its last token and its summed LM score; the table (ngram.h) is probed once per
-//                     (slot, candidate) in step 1 and once per new slot in step 3.
+//                     (slot, candidate) in step 1 and once per new slot in step 3.  The second flag, <LM, true>
+//                     (otr_ctc_beam_search_bias), adds the phrase-biasing addend of bias.h behind the n-gram's: a slot then also
+//                     carries the suffix chain of its phrase state (16 nodes + a mask), psi of that state and its summed phrase
+//                     addends; the phrase table is probed in the same two places, and after the last frame the open matches are
+//                     refunded and the beam is ranked again.
+#include "bias.h"
 #include "ngram.h"
 
 #define NEG_INF (-__builtin_huge_valf())
@@ -124,15 +129,43 @@ __device__ __forceinline__ float cb_addend(const CbLm& lm, uint32_t found, const
   return lm.alpha * p + lm.beta;
 }
 
-template <bool LM>
+struct CbBias {        // the phrase path's arguments (unused where BIAS is false)
+  BsTable t;
+  int max_len;
+  float* bias_scores;
+};
+// state(s c) from the suffix chain of state(s): child(n_j, c) from the deepest chain entry down to the root, the first that exists.
+// mask: bit j = the last j tokens of s are a node (bit 0, the root, always); nodes[j - 1] = that node.  Returns psi_minus(state(s c)),
+// the root's 0 where no suffix goes on with c.  A node of depth max_len has no child and is not asked.
+__device__ __forceinline__ float cb_bias_next(const CbBias& bz, uint32_t mask, const uint32_t* nodes, int c) {
+  uint32_t m = mask & ((1u << bz.max_len) - 1u);       // max_len <= 16
+  while (m) {
+    const int j = 31 - __clz(m);
+    m &= ~(1u << j);
+    uint32_t child;
+    float pm = 0.f;
+    bool end;
+    if (bs_child(bz.t, j ? nodes[j - 1] : 0u, (uint32_t)c, child, pm, end)) return pm;
+  }
+  return 0.f;
+}
+
+template <bool LM, bool BIAS>
 __global__ __launch_bounds__(CB_NT) void ctc_beam_search_kernel(const float* top_lp, const int32_t* top_tok, const int32_t* lengths,
                                                                int T, int K, int blank, int W, int2* trie, int64_t* tokens,
-                                                               int32_t* out_len, float* scores, CbLm lm) {
+                                                               int32_t* out_len, float* scores, CbLm lm, CbBias bz) {
   constexpr int LW = LM ? CB_MAXW : 1;
+  constexpr int BW = BIAS ? CB_MAXW : 1;
+  constexpr int AW = (LM || BIAS) ? CB_MAXW : 1;
+  __shared__ uint32_t s_bn[2][BW][BS_MAXLEN];          // phrase state: the node of the last j tokens at [j - 1], where s_bm has bit j
+  __shared__ uint32_t s_bm[2][BW];                     // bit j (0 .. 16): the last j tokens are a node; bit 0 (the root) always
+  __shared__ float s_bpsi[2][BW], s_bs[2][BW];         // psi(state(s)); the summed phrase addends
+  __shared__ float s_fin[BW];                          // after the last frame: the refunded scores
+  __shared__ int s_perm[BW];                           //   and output row -> slot
   __shared__ uint64_t s_cx[2][LW];                     // LM context: <s> + prefix cut to its newest order-1 ids, newest id lowest
   __shared__ float s_bo[2][LW][NG_MAXN - 1];           // backoff of the newest k ids of the context at [k - 1], 0 where not stored
   __shared__ int s_cl[2][LW];                          // context length | OOV mask << 8 (bit j: the j-th newest id has no unigram)
-  __shared__ float s_add[2][LW], s_lm[2][LW];          // addend of the slot's last token (the 1b merge adds it), summed addends
+  __shared__ float s_add[2][AW], s_lm[2][LW];          // addend of the slot's last token, LM + phrase (the 1b merge adds it); summed LM addends
   __shared__ float f_lp[CB_MAXK];
   __shared__ int f_tok[CB_MAXK];
   __shared__ float s_pb[2][CB_MAXW], s_pnb[2][CB_MAXW];
@@ -148,8 +181,10 @@ __global__ __launch_bounds__(CB_NT) void ctc_beam_search_kernel(const float* top
   if (tid == 0) {
     s_pb[0][0] = 0.f; s_pnb[0][0] = NEG_INF; s_last[0][0] = -1; s_len[0][0] = 0; s_node[0][0] = -1;
     s_h[0][0] = CB_H0; s_ph[0][0] = 0;
+    if constexpr (LM || BIAS) s_add[0][0] = 0.f;
+    if constexpr (BIAS) { s_bm[0][0] = 1u; s_bpsi[0][0] = 0.f; s_bs[0][0] = 0.f; }
     if constexpr (LM) {
-      s_add[0][0] = 0.f; s_lm[0][0] = 0.f;
+      s_lm[0][0] = 0.f;
       s_cx[0][0] = (uint64_t)lm.V;
       int cl = 0;
       for (int k = 0; k < NG_MAXN - 1; ++k) s_bo[0][0][k] = 0.f;
@@ -196,6 +231,9 @@ __global__ __launch_bounds__(CB_NT) void ctc_beam_search_kernel(const float* top
             s += cb_addend(lm, f, lp, s_bo[cur][i], L, (cl >> 8) != 0);
           }
         }
+        if constexpr (BIAS) {                          // behind the n-gram's addend: a = psi_minus(state(s c)) - psi(state(s))
+          if (s != NEG_INF) s = __fadd_rn(s, __fsub_rn(cb_bias_next(bz, s_bm[cur][i], s_bn[cur][i], c), s_bpsi[cur][i]));
+        }
       }
       x_s[e] = CbPair{s, c};
     }
@@ -216,7 +254,7 @@ __global__ __launch_bounds__(CB_NT) void ctc_beam_search_kernel(const float* top
 #pragma unroll 8
         for (int i = 0; i < n; ++i)
           if (s_len[cur][i] == l0 && s_h[cur][i] == ph) {
-            if constexpr (LM)                            // the same string: the same addend as when slot j was made
+            if constexpr (LM || BIAS)                    // the same string: the same addend as when slot j was made
               pnb = cb_lae(pnb, (s_last[cur][i] == lj ? s_pb[cur][i] : cb_lae(s_pb[cur][i], s_pnb[cur][i])) + pl + s_add[cur][j]);
             else
               pnb = cb_lae(pnb, (s_last[cur][i] == lj ? s_pb[cur][i] : cb_lae(s_pb[cur][i], s_pnb[cur][i])) + pl);
@@ -266,6 +304,11 @@ __global__ __launch_bounds__(CB_NT) void ctc_beam_search_kernel(const float* top
           s_cx[nxt][r] = s_cx[cur][i]; s_cl[nxt][r] = s_cl[cur][i]; s_add[nxt][r] = s_add[cur][i]; s_lm[nxt][r] = s_lm[cur][i];
           for (int k = 0; k < NG_MAXN - 1; ++k) s_bo[nxt][r][k] = s_bo[cur][i][k];
         }
+        if constexpr (BIAS) {
+          if constexpr (!LM) s_add[nxt][r] = s_add[cur][i];
+          s_bm[nxt][r] = s_bm[cur][i]; s_bpsi[nxt][r] = s_bpsi[cur][i]; s_bs[nxt][r] = s_bs[cur][i];
+          for (int k = 0; k < BS_MAXLEN; ++k) s_bn[nxt][r][k] = s_bn[cur][i][k];
+        }
       } else {
         const int c = tp - 1;
         s_pb[nxt][r] = NEG_INF; s_pnb[nxt][r] = s;
@@ -288,26 +331,78 @@ __global__ __launch_bounds__(CB_NT) void ctc_beam_search_kernel(const float* top
           s_cl[nxt][r] = L2 | (oov << 8);
           for (int k = 0; k < NG_MAXN - 1; ++k) s_bo[nxt][r][k] = (k < L2 && (f >> k & 1)) ? bo[k] : 0.f;
         }
+        if constexpr (BIAS) {
+          // the new chain: child(n_j, c) for every j of the parent's chain below max_len (step 1 just touched the entries); the
+          // deepest of them is state(s c), its psi_minus the addend's first term
+          const uint32_t pm_mask = s_bm[cur][i] & ((1u << bz.max_len) - 1u);
+          uint32_t nm = 1u;
+          float pm_new = 0.f, psi_new = 0.f;
+          for (int j = 0; j < BS_MAXLEN; ++j) {        // ascending: the deepest hit is the last to set pm_new / psi_new
+            if (!(pm_mask >> j & 1u)) continue;
+            uint32_t child;
+            float pm = 0.f;
+            bool end;
+            if (bs_child(bz.t, j ? s_bn[cur][i][j - 1] : 0u, (uint32_t)c, child, pm, end)) {
+              s_bn[nxt][r][j] = child;                 // depth j + 1 <= 16
+              nm |= 2u << j;
+              pm_new = pm;
+              psi_new = end ? 0.f : pm;
+            }
+          }
+          const float a = __fsub_rn(pm_new, s_bpsi[cur][i]);
+          s_bm[nxt][r] = nm; s_bpsi[nxt][r] = psi_new;
+          s_bs[nxt][r] = __fadd_rn(s_bs[cur][i], a);
+          if constexpr (LM) s_add[nxt][r] = __fadd_rn(s_add[nxt][r], a);   // written just above by this thread: LM, then phrase
+          else s_add[nxt][r] = a;
+        }
       }
     }
     __syncthreads();
     n = s_n[nxt];
     cur = nxt;
   }
+  // BIAS: an open match is refunded -- every live slot loses psi(state(h)) -- and the live slots are ranked again by the refunded
+  // score, by counting: descending, ties -> the earlier slot.  s_perm: output row -> slot.
+  if constexpr (BIAS) {
+    if (tid < n) s_fin[tid] = __fsub_rn(cb_lae(s_pb[cur][tid], s_pnb[cur][tid]), s_bpsi[cur][tid]);
+    __syncthreads();
+    if (tid < n) {
+      const float v = s_fin[tid];
+      int r = 0;
+      for (int q = 0; q < n; ++q) {
+        const float o = s_fin[q];
+        r += o > v || (o == v && q < tid);
+      }
+      s_perm[r] = tid;
+    }
+    __syncthreads();
+  }
   // hypotheses, sorted by score (the last selection ranked them); slots past the live beam: score -inf, length 0, all -1
   int64_t* tk = tokens + (int64_t)b * W * T;
   for (int e = tid; e < W * T; e += CB_NT) {
     const int r = e / T, pos = e - r * T;
-    if (r >= n || pos >= s_len[cur][r]) tk[e] = -1;
+    bool pad = r >= n;
+    if (!pad) {
+      if constexpr (BIAS) pad = pos >= s_len[cur][s_perm[r]];
+      else pad = pos >= s_len[cur][r];
+    }
+    if (pad) tk[e] = -1;
   }
   if (tid < W) {
     const int r = tid;
     const bool live = r < n;
-    const int l = live ? s_len[cur][r] : 0;
-    scores[b * W + r] = live ? cb_lae(s_pb[cur][r], s_pnb[cur][r]) : NEG_INF;
-    if constexpr (LM) lm.lm_scores[b * W + r] = live ? s_lm[cur][r] : 0.f;
+    int src = r;                                       // the slot that output row r shows
+    if constexpr (BIAS) src = live ? s_perm[r] : r;
+    const int l = live ? s_len[cur][src] : 0;
+    if constexpr (BIAS) {
+      scores[b * W + r] = live ? s_fin[src] : NEG_INF;
+      bz.bias_scores[b * W + r] = live ? __fsub_rn(s_bs[cur][src], s_bpsi[cur][src]) : 0.f;
+    } else {
+      scores[b * W + r] = live ? cb_lae(s_pb[cur][r], s_pnb[cur][r]) : NEG_INF;
+    }
+    if constexpr (LM) lm.lm_scores[b * W + r] = live ? s_lm[cur][src] : 0.f;
     out_len[b * W + r] = l;
-    int node = live ? s_node[cur][r] : -1;
+    int node = live ? s_node[cur][src] : -1;
     for (int pos = l - 1; pos >= 0; --pos) {
       const int2 nd = tr[node];
       tk[(int64_t)r * T + pos] = nd.y;
@@ -351,8 +446,8 @@ extern "C" int32_t otr_ctc_beam_search(const float* top_lp, const int32_t* top_t
   const int64_t need = otr_ctc_beam_workspace_bytes(B, T, W);
   OTR_REQUIRE(ws_bytes >= need, "ctc_beam_search: workspace of %lld bytes, %lld needed (otr_ctc_beam_workspace_bytes)",
               (long long)ws_bytes, (long long)need);
-  hipLaunchKernelGGL(ctc_beam_search_kernel<false>, dim3(B), dim3(CB_NT), 0, (hipStream_t)stream, top_lp, top_tok, lengths, T, K, blank,
-                     W, (int2*)workspace, tokens, out_len, scores, CbLm{});
+  hipLaunchKernelGGL((ctc_beam_search_kernel<false, false>), dim3(B), dim3(CB_NT), 0, (hipStream_t)stream, top_lp, top_tok, lengths, T, K, blank,
+                     W, (int2*)workspace, tokens, out_len, scores, CbLm{}, CbBias{});
   return otr_check_launch("ctc_beam_search");
 }
 
@@ -374,7 +469,41 @@ extern "C" int32_t otr_ctc_beam_search_lm(const float* top_lp, const int32_t* to
   if (otr_ngram_check_table("ctc_beam_search_lm", table, capacity, max_probe, order, V) < 0) return -1;
   OTR_REQUIRE(alpha == alpha && beta == beta && oov_score == oov_score, "ctc_beam_search_lm: alpha, beta and oov_score must be numbers");
   const CbLm lm{NgTable{(const uint4*)table, (uint32_t)(capacity - 1), max_probe}, order, V, alpha, beta, oov_score, lm_scores};
-  hipLaunchKernelGGL(ctc_beam_search_kernel<true>, dim3(B), dim3(CB_NT), 0, (hipStream_t)stream, top_lp, top_tok, lengths, T, K, blank,
-                     W, (int2*)workspace, tokens, out_len, scores, lm);
+  hipLaunchKernelGGL((ctc_beam_search_kernel<true, false>), dim3(B), dim3(CB_NT), 0, (hipStream_t)stream, top_lp, top_tok, lengths, T, K, blank,
+                     W, (int2*)workspace, tokens, out_len, scores, lm, CbBias{});
   return otr_check_launch("ctc_beam_search_lm");
+}
+
+extern "C" int32_t otr_ctc_beam_search_bias(const float* top_lp, const int32_t* top_tok, const int32_t* lengths, int32_t B, int32_t T,
+                                            int32_t V, int32_t K, int32_t blank, int32_t W, void* workspace, int64_t ws_bytes,
+                                            int64_t* tokens, int32_t* out_len, float* scores, const void* ngram_table, int64_t capacity,
+                                            int32_t max_probe, int32_t order, float alpha, float beta, float oov_score, float* lm_scores,
+                                            const void* bias_table, int64_t bias_capacity, int32_t bias_max_probe, int32_t bias_max_len,
+                                            float* bias_scores, void* stream) {
+  OTR_REQUIRE(top_lp && top_tok && lengths && workspace && tokens && out_len && scores && bias_scores, "ctc_beam_search_bias: null pointer");
+  OTR_REQUIRE(B >= 1 && T >= 1, "ctc_beam_search_bias: bad shape B=%d T=%d", B, T);
+  OTR_REQUIRE(W >= 1 && W <= CB_MAXW, "ctc_beam_search_bias: beam width W=%d must be in [1, %d]", W, CB_MAXW);
+  OTR_REQUIRE(V >= 1 && V <= CB_MAXV, "ctc_beam_search_bias: V=%d must be in [1, %d]", V, CB_MAXV);
+  OTR_REQUIRE(K >= 1 && K <= CB_MAXK && K <= V, "ctc_beam_search_bias: K=%d must be in [1, min(%d, V=%d)]", K, CB_MAXK, V);
+  OTR_REQUIRE(blank >= 0 && blank < V, "ctc_beam_search_bias: blank=%d must be in [0, V=%d)", blank, V);
+  OTR_REQUIRE(((uintptr_t)workspace & 7) == 0, "ctc_beam_search_bias: workspace must be 8-byte aligned");
+  const int64_t need = otr_ctc_beam_workspace_bytes(B, T, W);
+  OTR_REQUIRE(ws_bytes >= need, "ctc_beam_search_bias: workspace of %lld bytes, %lld needed (otr_ctc_beam_workspace_bytes)",
+              (long long)ws_bytes, (long long)need);
+  if (otr_bias_check_table("ctc_beam_search_bias", bias_table, bias_capacity, bias_max_probe, bias_max_len) < 0) return -1;
+  const CbBias bz{BsTable{(const uint4*)bias_table, (uint32_t)(bias_capacity - 1), bias_max_probe}, bias_max_len, bias_scores};
+  hipStream_t s = (hipStream_t)stream;
+  if (!ngram_table) {                                  // no n-gram: its arguments are not looked at, lm_scores must not be given
+    OTR_REQUIRE(lm_scores == nullptr, "ctc_beam_search_bias: lm_scores given without an n-gram table");
+    hipLaunchKernelGGL((ctc_beam_search_kernel<false, true>), dim3(B), dim3(CB_NT), 0, s, top_lp, top_tok, lengths, T, K, blank, W,
+                       (int2*)workspace, tokens, out_len, scores, CbLm{}, bz);
+    return otr_check_launch("ctc_beam_search_bias");
+  }
+  OTR_REQUIRE(lm_scores != nullptr, "ctc_beam_search_bias: null lm_scores with an n-gram table");
+  if (otr_ngram_check_table("ctc_beam_search_bias", ngram_table, capacity, max_probe, order, V) < 0) return -1;
+  OTR_REQUIRE(alpha == alpha && beta == beta && oov_score == oov_score, "ctc_beam_search_bias: alpha, beta and oov_score must be numbers");
+  const CbLm lm{NgTable{(const uint4*)ngram_table, (uint32_t)(capacity - 1), max_probe}, order, V, alpha, beta, oov_score, lm_scores};
+  hipLaunchKernelGGL((ctc_beam_search_kernel<true, true>), dim3(B), dim3(CB_NT), 0, s, top_lp, top_tok, lengths, T, K, blank, W,
+                     (int2*)workspace, tokens, out_len, scores, lm, bz);
+  return otr_check_launch("ctc_beam_search_bias");
 }

@@ -3595,8 +3595,9 @@ def ctc_prefix_beam_search(log_probs, lengths, beam_width=5, cutoff_top_n=40, bl
     return _ctc_prefix_beam_search('ctc_prefix_beam_search', log_probs, lengths, beam_width, cutoff_top_n, blank, workspace, None)
 
 
-def _ctc_prefix_beam_search(who, log_probs, lengths, beam_width, cutoff_top_n, blank, workspace, lm):
-    """the argument checks, the buffers and the top-K pass both searches share; lm = None or (NGramLM, alpha, beta)"""
+def _ctc_prefix_beam_search(who, log_probs, lengths, beam_width, cutoff_top_n, blank, workspace, lm, bias=None):
+    """the argument checks, the buffers and the top-K pass every search shares; lm = None or (NGramLM, alpha, beta); bias = None or a
+    bias.PhraseBias (then the phrase-biased entry runs, with the n-gram too where lm is given)"""
     _cuda(log_probs, lengths)
     if log_probs.dim() != 3 or log_probs.dtype != torch.float32:
         raise L.OtransHipError('%s: log_probs must be f32 [B, T, V], got %s %s' % (who, log_probs.dtype, tuple(log_probs.shape)))
@@ -3619,6 +3620,20 @@ def _ctc_prefix_beam_search(who, log_probs, lengths, beam_width, cutoff_top_n, b
     out_len = torch.empty((B, W), dtype=torch.int32, device=dev)
     scores = torch.empty((B, W), dtype=torch.float32, device=dev)
     L.check(lib.otr_ctc_topk(_p(lp), lp.stride(1), _p(ln), B, T, V, K, _p(top_lp), _p(top_tok), _stream()), 'otr_ctc_topk')
+    if bias is not None:
+        bias_scores = torch.empty((B, W), dtype=torch.float32, device=dev)
+        lm_scores = torch.empty((B, W), dtype=torch.float32, device=dev) if lm is not None else None
+        if lm is not None:
+            ngram, alpha, beta = lm
+            ng = (_p(ngram.device_table(dev)), ngram.capacity, ngram.max_probe, ngram.order, float(alpha), float(beta), ngram.oov_score,
+                  _p(lm_scores))
+        else:
+            ng = (None, 0, 0, 0, 0.0, 0.0, 0.0, None)
+        L.check(lib.otr_ctc_beam_search_bias(_p(top_lp), _p(top_tok), _p(ln), B, T, V, K, blank, W, _p(workspace),
+                                             workspace.numel() * workspace.element_size(), _p(tokens), _p(out_len), _p(scores), *ng,
+                                             _p(bias.device_table(dev)), bias.capacity, bias.max_probe, bias.max_len, _p(bias_scores),
+                                             _stream()), 'otr_ctc_beam_search_bias')
+        return (tokens, out_len, scores, bias_scores) if lm is None else (tokens, out_len, scores, lm_scores, bias_scores)
     if lm is None:
         L.check(lib.otr_ctc_beam_search(_p(top_lp), _p(top_tok), _p(ln), B, T, V, K, blank, W, _p(workspace),
                                         workspace.numel() * workspace.element_size(), _p(tokens), _p(out_len), _p(scores), _stream()),
@@ -3642,6 +3657,30 @@ def ctc_prefix_beam_search_lm(log_probs, lengths, ngram, alpha, beta, beam_width
     lm_scores is that term alone (scores - lm_scores: the acoustic log-probability).  Same launches, same capturability."""
     return _ctc_prefix_beam_search('ctc_prefix_beam_search_lm', log_probs, lengths, beam_width, cutoff_top_n, blank, workspace,
                                    (ngram, alpha, beta))
+
+
+def ctc_prefix_beam_search_bias(log_probs, lengths, bias, ngram=None, alpha=0.0, beta=0.0, beam_width=5, cutoff_top_n=40, blank=0,
+                                workspace=None):
+    """ctc_prefix_beam_search with phrase biasing (hotwords) fused into the search (include/otrans_hip.h otr_ctc_beam_search_bias),
+    and the n-gram LM of ctc_prefix_beam_search_lm too where `ngram` is given: every extension s -> s+c gains psi_minus(state(s c)) -
+    psi(state(s)) of `bias` (an opentransformer_amd.bias.PhraseBias built for the V units of log_probs, none of its phrases holding
+    the blank), behind the n-gram's addend; after the last frame an open match is refunded and the beam ranked again.  Returns
+    (tokens, out_len, scores, bias_scores f32 [B, W]) without an n-gram, (tokens, out_len, scores, lm_scores, bias_scores) with one:
+    scores include every term, bias_scores is what the completed phrases of the hypothesis earned (ops.bias_score_sequences of it).
+    Same two launches, no host synchronisation: capturable (call bias.to(device), and ngram.to(device), before a capture)."""
+    from .bias import PhraseBias
+    if not isinstance(bias, PhraseBias):
+        raise L.OtransHipError('ctc_prefix_beam_search_bias: bias must be an opentransformer_amd.bias.PhraseBias, got %s'
+                               % type(bias).__name__)
+    V = log_probs.shape[-1]
+    if bias.vocab_size != V:
+        raise L.OtransHipError('ctc_prefix_beam_search_bias: the phrase set was built for %d units, log_probs has V=%d'
+                               % (bias.vocab_size, V))
+    held = [p for p in bias.phrases if blank in p]
+    if held:            # it could never match (the blank is never emitted): a vocabulary mix-up, not a phrase
+        raise L.OtransHipError('ctc_prefix_beam_search_bias: the phrase %r holds the blank id %d' % (held[0], blank))
+    return _ctc_prefix_beam_search('ctc_prefix_beam_search_bias', log_probs, lengths, beam_width, cutoff_top_n, blank, workspace,
+                                   None if ngram is None else (ngram, alpha, beta), bias)
 
 
 def ngram_lookup(ngram, ctx, ctx_len, tok):

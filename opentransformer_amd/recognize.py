@@ -523,14 +523,22 @@ class SpeechToTextRecognizer(Recognizer):
     any: in the joint search on the ctc_beam candidates, in the plain search on the K' tokens of highest att + lm, K' = ngram_beam
     where an n-gram LM is given (a bias_beam that differs from it is refused), else bias_beam (default min(V, int(1.5 * beam_width)),
     the pre-beam's limits).  ONLY pre-beam candidates are boosted: a phrase continuation the pre-beam dropped is not brought back;
-    raise K' (up to 32) for deeper reach.  With rescore=True the first pass (the CTC prefix beam search) is NOT biased: the second pass
-    adds the phrase score of each hypothesis (otr_bias_score_seqs; res['bias']) to the total, beside the n-gram's, so phrases re-rank
-    the n-best and no more."""
+    raise K' (up to 32) for deeper reach.  With rescore=True the second pass adds the phrase score of each hypothesis
+    (otr_bias_score_seqs; res['bias']) to the total, beside the n-gram's.  By default (bias_first_pass=False) the first pass (the CTC
+    prefix beam search) is NOT biased, so phrases re-rank the n-best and no more.  bias_first_pass=True makes the first pass the
+    phrase-biased search (ops.ctc_prefix_beam_search_bias, with the n-gram too where one is given): a phrase the acoustic model ranks
+    below the beam can then reach the second pass.  The acoustic term becomes scores - lm_scores - bias_scores of that search and the
+    total of a hypothesis keeps its formula; only which hypotheses are rescored changes.  bias_first_pass=True needs rescore=True and
+    a bias, and none of the phrases may hold the CTC head's blank."""
 
     def __init__(self, model, lm=None, lm_weight=0.1, ctc_weight=0.0, beam_width=5, nbest=1, max_len=50,
                  idx2unit=None, penalty=0, lamda=5, ngpu=1, apply_cache=False, joint_ctc=False, ctc_beam=None, rescore=False,
-                 cutoff_top_n=40, ngram_lm=None, alpha=0.1, beta=0.0, ngram_beam=None, bias=None, bias_beam=None):
+                 cutoff_top_n=40, ngram_lm=None, alpha=0.1, beta=0.0, ngram_beam=None, bias=None, bias_beam=None,
+                 bias_first_pass=False):
         super().__init__(model, idx2unit, lm, lm_weight, ngpu)
+        if bias_first_pass and (not rescore or bias is None):
+            raise ValueError('bias_first_pass=True biases the first pass of the two-pass decode: it needs rescore=True and bias=...')
+        self.bias_first_pass = bool(bias_first_pass)
         if ngram_lm is not None and not isinstance(ngram_lm, NGramLM):
             raise NotImplementedError('SpeechToTextRecognizer: ngram_lm must be an NGramLM, not %s: load the ARPA file with '
                                       'NGramLM.from_arpa(path, idx2unit) (KenLM binaries are not read)' % type(ngram_lm).__name__)
@@ -699,7 +707,14 @@ class SpeechToTextRecognizer(Recognizer):
         V = dec.output_layer.weight.shape[0]
         kw = dict(beam_width=W, cutoff_top_n=self.cutoff_top_n, blank=self.model.assistor.blank)
         ng, ctc, ng_score = self.ngram_lm, None, None
-        if ng is None:
+        if self.bias_first_pass:
+            # the phrases (and the n-gram) shape the n-best; the second pass takes the acoustic part and scores the strings afresh
+            out = ops.ctc_prefix_beam_search_bias(log_probs, lengths, self.bias, ng, self.alpha, self.beta, **kw)
+            tokens, out_len, scores = out[:3]
+            ctc = scores - out[-1] if ng is None else scores - out[3] - out[4]
+            if ng is not None:
+                ng_score = ops.ngram_score_sequences(ng, tokens, out_len, self.alpha, self.beta, eos=EOS)
+        elif ng is None:
             tokens, out_len, scores = ops.ctc_prefix_beam_search(log_probs, lengths, **kw)
             ctc = scores
         else:
@@ -708,7 +723,7 @@ class SpeechToTextRecognizer(Recognizer):
             ctc = scores - lm_scores
             ng_score = ops.ngram_score_sequences(ng, tokens, out_len, self.alpha, self.beta, eos=EOS)
         add_score, bias_score = ng_score, None
-        if self.bias is not None:                         # the phrases re-rank the n-best: the first pass above is not biased
+        if self.bias is not None:                         # the phrases re-rank the n-best, whether or not the first pass saw them
             bias_score = ops.bias_score_sequences(self.bias, tokens, out_len, eos=EOS)
             add_score = bias_score if ng_score is None else ng_score + bias_score
         packed = ops.rescore_pack(tokens, out_len, scores, self.max_len, V, BOS, EOS)
@@ -1048,16 +1063,23 @@ class CTCRecognizer(Recognizer):
     in beam mode every extension then gains alpha * ln P_LM + beta inside the search (ops.ctc_prefix_beam_search_lm), ctcdecode's
     character-based scorer; greedy mode ignores it, as the reference does.  A path is not loaded here (build_recognizer does that);
     without an LM alpha / beta are unused, as in ctcdecode without a scorer.  lm / lm_weight are unused in beam mode as in the
-    reference."""
+    reference.  bias: None, or a bias.PhraseBias over the CTC head's units (phrase biasing, "hotwords"): in beam mode every extension
+    s -> s c then gains psi_minus(state(s c)) - psi(state(s)) inside the search, behind the n-gram's addend if any, and a match left
+    open at the end of the utterance is refunded (ops.ctc_prefix_beam_search_bias; include/otrans_hip.h otr_ctc_beam_search_bias).
+    Greedy mode ignores bias, as it ignores ngram_lm.  The alignment of recognize_with_times runs on the acoustic log-probs alone."""
 
     def __init__(self, model, lm=None, lm_weight=0.1, ngram_lm=None, beam_width=5, idx2unit=None, ngpu=1,
-                 mode='greedy', alpha=0.1, beta=0.0, cutoff_top_n=40):
+                 mode='greedy', alpha=0.1, beta=0.0, cutoff_top_n=40, bias=None):
         super().__init__(model, idx2unit, lm, lm_weight, ngpu)
         if mode not in ('greedy', 'beam'):
             raise NotImplementedError("CTCRecognizer mode '%s': 'greedy' and 'beam' are built" % mode)
         if mode == 'beam' and ngram_lm is not None and not isinstance(ngram_lm, NGramLM):
             raise NotImplementedError('CTCRecognizer: ngram_lm must be an NGramLM, not %s: load the ARPA file with '
                                       'NGramLM.from_arpa(path, idx2unit) (KenLM binaries are not read)' % type(ngram_lm).__name__)
+        if bias is not None and not isinstance(bias, PhraseBias):
+            raise TypeError('CTCRecognizer: bias must be a PhraseBias, not %s: build one with PhraseBias(phrases, vocab_size) or '
+                            'PhraseBias.from_texts(lines, idx2unit)' % type(bias).__name__)
+        self.bias = bias
         self.beam_width, self.mode, self.ngram_lm = beam_width, mode, ngram_lm
         self.alpha, self.beta, self.cutoff_top_n = alpha, beta, cutoff_top_n
 
@@ -1111,8 +1133,12 @@ class CTCRecognizer(Recognizer):
         return self._best_lists(*self._beam(log_probs, length))
 
     def _beam(self, log_probs, length, with_scores=False):
-        """the beam of the CTC head's log-probs, with the n-gram LM fused in where one was given: (tokens, out_len[, scores])"""
+        """the beam of the CTC head's log-probs, with the n-gram LM and the phrases fused in where they were given: (tokens, out_len[,
+        scores])"""
         kw = dict(beam_width=self.beam_width, cutoff_top_n=self.cutoff_top_n, blank=self.model.assistor.blank)
+        if self.bias is not None:
+            return ops.ctc_prefix_beam_search_bias(log_probs, length, self.bias, self.ngram_lm, self.alpha, self.beta,
+                                                   **kw)[:3 if with_scores else 2]
         if self.ngram_lm is None:
             return ops.ctc_prefix_beam_search(log_probs, length, **kw)[:3 if with_scores else 2]
         return ops.ctc_prefix_beam_search_lm(log_probs, length, self.ngram_lm, self.alpha, self.beta, **kw)[:3 if with_scores else 2]
@@ -1207,12 +1233,18 @@ def build_recognizer(model_type, model, lm, args, idx2unit):
                                       joint_ctc=getattr(args, 'joint_ctc', False), ctc_beam=getattr(args, 'ctc_beam', None),
                                       rescore=getattr(args, 'rescore', False), ngram_lm=ngram_lm,
                                       ngram_beam=getattr(args, 'ngram_beam', None), bias=bias,
-                                      bias_beam=getattr(args, 'bias_beam', None), **kw)
+                                      bias_beam=getattr(args, 'bias_beam', None),
+                                      bias_first_pass=getattr(args, 'bias_first_pass', False), **kw)
     if model_type == 'ctc':
         ngram_lm = args.ngram_lm
         if isinstance(ngram_lm, str):                                           # the reference passes the path on to ctcdecode
             ngram_lm = NGramLM.from_arpa(ngram_lm, idx2unit)
+        bias = getattr(args, 'bias_phrases', None)
+        if isinstance(bias, str):                                               # a text file: one phrase per line
+            with open(bias, encoding='utf-8') as f:
+                bias = PhraseBias.from_texts(f, idx2unit, score=getattr(args, 'bias_score', 2.0),
+                                             vocab_size=model.assistor.output_layer.weight.shape[0])
         return CTCRecognizer(model=model, lm=lm, lm_weight=args.lm_weight, ngram_lm=ngram_lm,
                              beam_width=args.beam_width, idx2unit=idx2unit, ngpu=args.ngpu, mode=args.mode,
-                             alpha=args.alpha, beta=args.beta)
+                             alpha=args.alpha, beta=args.beta, bias=bias)
     raise NotImplementedError
