@@ -40,7 +40,7 @@ extern "C" {
  * bump; 602: the rescoring entries, additions only; 603: otr_ctc_align, additions only; 604: otr_ngram_lookup and otr_ctc_beam_search_lm, additions only; 605:
  * otr_edit_distance, additions only; 606: otr_ngram_score_cands, otr_ngram_score_seqs and otr_rescore_select_add, additions only; 607: otr_ngram_count, otr_ngram_stats and otr_ngram_estimate, additions only;
  * 608: otr_mwer_workspace_floats and otr_mwer_loss, additions only; still 608: otr_feature_prepare_workspace_bytes, otr_feature_prepare and
- * otr_cmvn_accumulate, after them otr_ctc_segment_workspace_bytes and otr_ctc_segment, and after those otr_distill_workspace_floats and otr_distill_loss (additions only), after those otr_bias_score_cands and otr_bias_score_seqs (additions only), and last otr_ctc_beam_search_bias (an addition only), were added without a bump -- no existing signature, structure or meaning changed, and a binding that needs them
+ * otr_cmvn_accumulate, after them otr_ctc_segment_workspace_bytes and otr_ctc_segment, and after those otr_distill_workspace_floats and otr_distill_loss (additions only), after those otr_bias_score_cands and otr_bias_score_seqs (additions only), and otr_ctc_beam_search_bias (an addition only), and last otr_edit_align and otr_nbest_consensus (additions only), were added without a bump -- no existing signature, structure or meaning changed, and a binding that needs them
  * fails on the missing symbol of an older library when it loads it).  A binding compares otr_version() with the OTR_ABI_VERSION it was written against BEFORE its first call and refuses a
  * library that answers anything else: descriptors are passed by pointer and read at the library's idea of their size. */
 #define OTR_ABI_VERSION 608
@@ -852,6 +852,39 @@ int32_t otr_ctc_segment(const float* log_probs, int64_t ld, const int64_t* targe
 int32_t otr_edit_distance(const int64_t* ref, int64_t ref_bs, const int32_t* ref_len, const int64_t* hyp, int64_t hyp_bs,
                           int64_t hyp_ns, const int32_t* hyp_len, int32_t B, int32_t N, int32_t Lr, int32_t Lh, int32_t eos,
                           int32_t* dist, int32_t* counts, int64_t* totals, void* stream);
+
+/* ---- per-token edit alignment, and the consensus of an n-best: token confidences and minimum Bayes risk (MBR) selection,
+ *      csrc/nbest.hip.  Integer alignment, f32 sums in a fixed order, no 16-bit operand: identical in both builds and on every run.
+ * otr_edit_align: the arguments, the eos cut and the validity rules of otr_edit_distance, widths 0 <= Lr, Lh <= OTR_NBEST_MAX_LEN.  The
+ *   alignment is the canonical one of otr_edit_distance, walked back from (R, H): at (i, j) the diagonal if D[i-1][j-1] + (ref[i-1] !=
+ *   hyp[j-1]) == D[i][j], else the cell above if D[i-1][j] + 1 == D[i][j] (a deletion), else the cell to the left (an insertion);
+ *   row 0 is all insertions, column 0 all deletions.  Outputs: dist int32 [B, N] = D[R][H]; code int8 [B, N, Lh]: 0 a match, 1 a
+ *   substitution, 2 an insertion for each of the H hypothesis tokens, -1 from H on; ref_pos int32 [B, N, Lh]: the index i-1 of the
+ *   reference token a match or substitution is aligned to, -1 on insertions and from H on.  The codes' counts of 1s and 2s are
+ *   otr_edit_distance's S and I, and D = R - (matches + substitutions).  An invalid pair gives dist -1 and -1 in all of code and
+ *   ref_pos.  Every element of the three outputs is written.  One launch, one wave per pair, the 2-bit back-pointers of a pair (16 KB
+ *   at 256 x 256) in LDS: no workspace.
+ * otr_nbest_consensus: tokens int64 [B, N, L], hypothesis (b, n) at tokens + b*tok_bs + n*tok_ns; lengths int32 [B, N], scores f32
+ *   [B, N] (both contiguous); eos as above; scale finite.  Slot (b, n) is LIVE if its score is finite and 0 <= lengths <= L.
+ *   post f32 [B, N] = softmax over the live slots of scale * score (formed as exp(scale * (score - pivot)), the pivot the live slot of
+ *     largest scale * score, summed with n ascending), 0 on dead slots;
+ *   risk f32 [B, N]: risk[b,i] = sum over the live j, ascending, of post[b,j] * dist(hypothesis i against hypothesis j as the
+ *     reference): the expected edit distance of i under the posterior; +inf on dead slots;
+ *   conf f32 [B, N, L]: conf[b,i,k] = sum over the live j, ascending, of post[b,j] * [otr_edit_align's code of token k of i against
+ *     j is 0]; j = i adds post[b,i].  0 from the hypothesis's end on and on dead slots;
+ *   best int32 [B]: the live slot of least risk, ties to the higher score, then the lower index; -1 without a live slot.
+ *   Every element of the four outputs is written.  Two launches (one workgroup per (b, i), one wave per pair, then the arg-min), no
+ *   atomics, no workspace.
+ * Both: checked before the launch (a refused call returns < 0, launches nothing, leaves the outputs untouched): 1 <= N <= 32, the
+ *   widths, 0 <= B <= 2^20 (B = 0 returns 0 without a launch), eos >= -1, strides >= 0.  No allocation, no host synchronisation;
+ *   capturable.  OTR_NBEST_MAX_LEN is what the back-pointers of one pair may take of a workgroup's 64 KB of LDS. */
+#define OTR_NBEST_MAX_LEN 256
+int32_t otr_edit_align(const int64_t* ref, int64_t ref_bs, const int32_t* ref_len, const int64_t* hyp, int64_t hyp_bs, int64_t hyp_ns,
+                       const int32_t* hyp_len, int32_t B, int32_t N, int32_t Lr, int32_t Lh, int32_t eos, int32_t* dist, int8_t* code,
+                       int32_t* ref_pos, void* stream);
+int32_t otr_nbest_consensus(const int64_t* tokens, int64_t tok_bs, int64_t tok_ns, const int32_t* lengths, const float* scores,
+                            float scale, int32_t B, int32_t N, int32_t L, int32_t eos, float* post, float* risk, int32_t* best,
+                            float* conf, void* stream);
 
 /* ---- joint CTC/attention beam search (SpeechToTextRecognizer joint_ctc=True; Watanabe et al. 2017, Algorithm 2; ESPnet's
  *      CTCPrefixScore), csrc/ctcscore.hip.  f32 in every build.  lambda = ctc_weight in [0, 1]; x_t(c) = log_probs of token c at frame

@@ -217,6 +217,8 @@ SIGNATURES = {
     'otr_ctc_segment_workspace_bytes': [_I32, _I32, _I32],
     'otr_ctc_segment': [_P, _I64, _P, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F32, _P, _I64, _P, _P, _P, _P, _P, _P],
     'otr_edit_distance': [_P, _I64, _P, _P, _I64, _I64, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P],
+    'otr_edit_align': [_P, _I64, _P, _P, _I64, _I64, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P],
+    'otr_nbest_consensus': [_P, _I64, _I64, _P, _P, _F32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P],
     'otr_joint_prebeam': [_P, _I64, _P, _I64, _F32, _F32, _I64, _I32, _I32, _P, _P, _P],
     'otr_ctc_prefix_score': [_P, _I64, _P, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _P, _P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P,
                              _F32, _P, _P, _P, _I32, _P, _P, _P, _P],

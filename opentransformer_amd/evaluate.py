@@ -9,6 +9,8 @@ one launch per batch that also adds the corpus totals into an int64 [8] tensor, 
 
 Units are whatever the token ids stand for: characters give CER, words WER.  score_texts scores word lists (two files of
 `utt_id word word ...` lines in tools/compute_wer.py) by mapping words to ids on the host first."""
+import math
+
 import torch
 
 from . import ops
@@ -48,20 +50,57 @@ class ErrorRateMeter:
         self.totals.zero_()
 
 
+def calibration(conf, correct, mask=None, eps=1e-6, bins=10):
+    """How well confidences predict outcomes: conf in [0, 1] and correct (bool or 0 / 1) device tensors of one shape, mask (bool, None:
+    all) the elements that count.  Returns {'nce', 'ece', 'tokens'}.  NCE, the normalised cross-entropy, is (H_prior - H_conf) /
+    H_prior: H_prior the entropy of the outcomes at their mean rate, H_conf the cross-entropy of the confidences (clamped to [eps,
+    1 - eps]); 1 is perfect, 0 no better than quoting the mean rate, negative worse; nan where every outcome is the same.  ECE, the
+    expected calibration error, is the sum over `bins` equal-width bins of n_k / n * |mean outcome - mean confidence|.  A few float64
+    reductions on the device and one read by the host."""
+    c = conf.reshape(-1).double()
+    y = correct.reshape(-1).double()
+    w = torch.ones_like(c) if mask is None else mask.reshape(-1).double()
+    cc = c.clamp(eps, 1.0 - eps)
+    hc = -(w * (y * torch.log(cc) + (1.0 - y) * torch.log1p(-cc))).sum()
+    k = (c * bins).long().clamp_(0, bins - 1)
+    zero = torch.zeros(bins, dtype=torch.float64, device=c.device)
+    gap = (zero.index_add(0, k, w * y) - zero.index_add(0, k, w * c)).abs().sum()
+    n, nc, hc, gap = torch.stack((w.sum(), (w * y).sum(), hc, gap)).tolist()
+    if n == 0:
+        return {'nce': float('nan'), 'ece': float('nan'), 'tokens': 0}
+    hp = -(nc * math.log(nc / n) + (n - nc) * math.log(1.0 - nc / n)) if 0 < nc < n else 0.0
+    return {'nce': (hp - hc) / hp if hp > 0 else float('nan'), 'ece': gap / n, 'tokens': int(n)}
+
+
 @torch.no_grad()
-def evaluate(recognizer, batches, meter=None):
+def evaluate(recognizer, batches, meter=None, confidence=False):
     """The decode-and-score loop of eval.py:126-193.  `batches` yields (utt_id, inputs, targets) as data.collate_fn_with_eos_bos
     builds them, on the recognizer's device.  The reference tokens are targets['targets'][:, 1:] with length targets_length - 1
     (eval.py:149: without BOS, without EOS); the hypotheses are recognizer.recognize_tokens(...), cut before their first EOS as
-    translate / nbest_translate cut the strings.  Nothing is copied to the host per batch by this loop; returns meter.result()."""
+    translate / nbest_translate cut the strings.  Nothing is copied to the host per batch by this loop; returns meter.result().
+    confidence=True: the hypotheses come from recognizer.recognize_tokens_with_confidence(...), a token of the 1-best counts as
+    correct where ops.edit_align against the reference calls it a match, and the result gains 'nce' and 'ece' (calibration() over all
+    the 1-best tokens of the pass, still one read at the end)."""
+    kept = []
     for _, inputs, targets in batches:
-        tokens, lengths, _ = recognizer.recognize_tokens(inputs['inputs'], inputs['mask'])
+        ref, ref_len = targets['targets'][:, 1:], targets['targets_length'] - 1
+        if confidence:
+            tokens, lengths, _, conf, _ = recognizer.recognize_tokens_with_confidence(inputs['inputs'], inputs['mask'])
+            W = ops.NBEST_MAX_LEN                         # a longer 1-best or reference is an invalid pair there: left out of nce / ece
+            code = ops.edit_align(ref[:, :W], ref_len, tokens[:, :1, :W], lengths[:, :1], eos=EOS)[1][:, 0]
+            kept.append((conf[:, :W].reshape(-1), (code == 0).reshape(-1), (code >= 0).reshape(-1)))
+        else:
+            tokens, lengths, _ = recognizer.recognize_tokens(inputs['inputs'], inputs['mask'])
         if meter is None:
             meter = ErrorRateMeter(tokens.device)
-        meter.update(targets['targets'][:, 1:], targets['targets_length'] - 1, tokens, lengths, eos=EOS)
+        meter.update(ref, ref_len, tokens, lengths, eos=EOS)
     if meter is None:
         raise ValueError('evaluate: no batches and no meter')
-    return meter.result()
+    out = meter.result()
+    if confidence:
+        cal = calibration(*(torch.cat(t) for t in zip(*kept)))
+        out['nce'], out['ece'] = cal['nce'], cal['ece']
+    return out
 
 
 def texts_to_ids(refs, hyps):

@@ -3999,6 +3999,87 @@ def edit_distance(ref, ref_len, hyp, hyp_len=None, eos=-1, totals=None):
     return dist, counts, totals
 
 
+# ------------------------------------------------------------------ per-token alignment, n-best consensus (csrc/nbest.hip)
+NBEST_MAX_LEN = 256         # OTR_NBEST_MAX_LEN: the back-pointers of one pair stay in LDS
+
+
+def edit_align(ref, ref_len, hyp, hyp_len=None, eos=-1):
+    """The canonical alignment of ops.edit_distance, per hypothesis token (include/otrans_hip.h otr_edit_align).  The arguments, the eos
+    cut and the validity rules are edit_distance's; widths up to NBEST_MAX_LEN.  Returns (dist int32 [B, N], code int8 [B, N, Lh]: 0
+    match, 1 substitution, 2 insertion, -1 past the hypothesis's end, ref_pos int32 [B, N, Lh]: the reference token a match or a
+    substitution is aligned to, -1 on insertions and past the end).  An invalid pair gives -1s.  int32 tokens are widened; views with a
+    contiguous last dimension are passed by stride.  One launch on the current stream, no host synchronisation, capturable."""
+    if hyp.dim() == 2:
+        hyp = hyp.unsqueeze(1)
+    if ref.dim() != 2 or hyp.dim() != 3 or hyp.shape[0] != ref.shape[0]:
+        raise ValueError('edit_align: ref must be [B, Lr] and hyp [B, N, Lh] or [B, Lh], got %s and %s' % (tuple(ref.shape), tuple(hyp.shape)))
+    B, N, Lh = hyp.shape
+    Lr = ref.shape[1]
+    if not 1 <= N <= EDIT_MAX_NBEST:
+        raise ValueError('edit_align: %d hypotheses per utterance, 1 .. %d supported' % (N, EDIT_MAX_NBEST))
+    if Lr > NBEST_MAX_LEN or Lh > NBEST_MAX_LEN:
+        raise ValueError('edit_align: widths Lr=%d Lh=%d, at most %d supported' % (Lr, Lh, NBEST_MAX_LEN))
+    _cuda(ref, ref_len, hyp, hyp_len)
+    if ref.dtype not in (torch.int32, torch.int64) or hyp.dtype not in (torch.int32, torch.int64):
+        raise L.OtransHipError('edit_align: tokens must be int32 or int64, got %s and %s' % (ref.dtype, hyp.dtype))
+    dev = ref.device
+    r, h = _rows_by_stride(ref), _rows_by_stride(hyp)
+    rl = ref_len.to(torch.int32).contiguous()
+    hl = (torch.full((B, N), Lh, dtype=torch.int32, device=dev) if hyp_len is None
+          else hyp_len.to(torch.int32).reshape(B, N).contiguous())
+    if rl.numel() != B or min(r.stride(0), h.stride(0), h.stride(1)) < 0:
+        raise L.OtransHipError('edit_align: bad arguments ref %s ref_len %s hyp %s' % (tuple(ref.shape), tuple(ref_len.shape), tuple(hyp.shape)))
+    dist = torch.empty((B, N), dtype=torch.int32, device=dev)
+    code = torch.empty((B, N, Lh), dtype=torch.int8, device=dev)
+    ref_pos = torch.empty((B, N, Lh), dtype=torch.int32, device=dev)
+    lib = L.load()
+    L.check(_timed('edit_align %dx%dx%dx%d' % (B, N, Lr, Lh), {'bytes': B * (Lr + N * Lh) * 8},
+                   lambda: lib.otr_edit_align(_p(r), r.stride(0), _p(rl), _p(h), h.stride(0), h.stride(1), _p(hl), B, N, Lr, Lh,
+                                              int(eos), _p(dist), _p(code), _p(ref_pos), _stream())), 'otr_edit_align')
+    return dist, code, ref_pos
+
+
+def nbest_consensus(tokens, lengths=None, scores=None, scale=1.0, eos=-1):
+    """Consensus of an n-best on the device (include/otrans_hip.h otr_nbest_consensus): tokens int [B, N, L], lengths [B, N] (None: the
+    full width, useful with eos), scores f32 [B, N] (None: all 0, a uniform posterior); eos >= 0: a hypothesis ends before its first
+    eos.  A slot is live if its score is finite and its length fits the width.  Returns (post f32 [B, N]: softmax of scale * score over
+    the live slots; risk f32 [B, N]: the expected edit distance of a hypothesis against the others under post, +inf on dead slots;
+    best int32 [B]: the live slot of least risk, ties to the higher score, then the lower index, -1 where none is live; conf f32
+    [B, N, L]: per token the posterior mass of the hypotheses whose alignment matches it, 0 past the end and on dead slots).  N up to
+    EDIT_MAX_NBEST, L up to NBEST_MAX_LEN.  Two launches on the current stream, no host synchronisation, capturable; the sums run in
+    a fixed order, so the outputs are the same bits on every run."""
+    if tokens.dim() != 3:
+        raise ValueError('nbest_consensus: tokens must be [B, N, L], got %s' % (tuple(tokens.shape),))
+    B, N, Lh = tokens.shape
+    if not 1 <= N <= EDIT_MAX_NBEST:
+        raise ValueError('nbest_consensus: %d hypotheses per utterance, 1 .. %d supported' % (N, EDIT_MAX_NBEST))
+    if Lh > NBEST_MAX_LEN:
+        raise ValueError('nbest_consensus: width L=%d, at most %d supported' % (Lh, NBEST_MAX_LEN))
+    scale = float(scale)
+    if not math.isfinite(scale):
+        raise ValueError('nbest_consensus: scale=%r must be finite' % (scale,))
+    _cuda(tokens, lengths, scores)
+    if tokens.dtype not in (torch.int32, torch.int64):
+        raise L.OtransHipError('nbest_consensus: tokens must be int32 or int64, got %s' % (tokens.dtype,))
+    dev = tokens.device
+    h = _rows_by_stride(tokens)
+    hl = (torch.full((B, N), Lh, dtype=torch.int32, device=dev) if lengths is None
+          else lengths.to(torch.int32).reshape(B, N).contiguous())
+    sc = (torch.zeros((B, N), dtype=torch.float32, device=dev) if scores is None
+          else scores.to(torch.float32).reshape(B, N).contiguous())
+    if min(h.stride(0), h.stride(1)) < 0:
+        raise L.OtransHipError('nbest_consensus: bad arguments tokens %s' % (tuple(tokens.shape),))
+    post = torch.empty((B, N), dtype=torch.float32, device=dev)
+    risk = torch.empty((B, N), dtype=torch.float32, device=dev)
+    best = torch.empty((B,), dtype=torch.int32, device=dev)
+    conf = torch.empty((B, N, Lh), dtype=torch.float32, device=dev)
+    lib = L.load()
+    L.check(_timed('nbest_consensus %dx%dx%d' % (B, N, Lh), {'bytes': B * N * Lh * 12},
+                   lambda: lib.otr_nbest_consensus(_p(h), h.stride(0), h.stride(1), _p(hl), _p(sc), scale, B, N, Lh, int(eos), _p(post),
+                                                   _p(risk), _p(best), _p(conf), _stream())), 'otr_nbest_consensus')
+    return post, risk, best, conf
+
+
 # ------------------------------------------------------------------ feature preparation for batch assembly (csrc/featprep.hip)
 FEATPREP_MAX_RANGES = 64
 _FEATPREP_MODES = {None: 0, 'utterance': 1, 'global': 2}

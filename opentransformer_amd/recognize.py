@@ -17,6 +17,7 @@ Both loops keep their beams in a _BeamState and end every step in its `advance` 
 logits.  CachedBeamState is a _BeamState plus what the cache needs.
 """
 import ctypes as C
+import math
 import weakref
 
 import torch
@@ -495,6 +496,35 @@ def _prebeam_limits(who, name, beam_width, K, V):
     return K
 
 
+def _mbr_args(who, mbr, mbr_scale, beam_width):
+    """(mbr, mbr_scale) of a recognizer's constructor, checked"""
+    mbr_scale = float(mbr_scale)
+    if not math.isfinite(mbr_scale):
+        raise ValueError('%s: mbr_scale=%r must be finite' % (who, mbr_scale))
+    if mbr and not 1 <= beam_width <= ops.EDIT_MAX_NBEST:
+        raise ValueError('%s: mbr=True takes the consensus of the whole beam: beam_width=%d, 1 .. %d supported'
+                         % (who, beam_width, ops.EDIT_MAX_NBEST))
+    return bool(mbr), mbr_scale
+
+
+def _consensus_nbest(tokens, lengths, scores, scale, mbr, n, eos):
+    """The consensus of a final beam (tokens [B, W, L], lengths [B, W], scores [B, W], best score first) and the n-best it leaves:
+    ordered by ascending risk where `mbr` (a stable sort: ties keep the higher score, then the lower rank; dead slots, of risk +inf,
+    last), as it stands otherwise.  -> (tokens [B, n, L], lengths [B, n], scores [B, n], conf f32 [B, L] and post f32 [B] of the
+    1-best).  Only the first ops.NBEST_MAX_LEN columns go into the consensus: a longer hypothesis is a dead slot there.  No host
+    synchronisation."""
+    L_ = tokens.size(-1)
+    post, risk, _, conf = ops.nbest_consensus(tokens[:, :, :ops.NBEST_MAX_LEN], lengths, scores, scale=scale, eos=eos)
+    if conf.size(-1) < L_:
+        conf = torch.nn.functional.pad(conf, (0, L_ - conf.size(-1)))
+    if not mbr:
+        return tokens[:, :n], lengths[:, :n], scores[:, :n], conf[:, 0], post[:, 0]
+    order = torch.sort(risk, dim=-1, stable=True)[1][:, :n]
+    first = order[:, :1]
+    return (torch.gather(tokens, 1, order.unsqueeze(-1).expand(-1, -1, L_)), torch.gather(lengths, 1, order), torch.gather(scores, 1, order),
+            torch.gather(conf, 1, first.unsqueeze(-1).expand(-1, -1, L_))[:, 0], torch.gather(post, 1, first)[:, 0])
+
+
 class SpeechToTextRecognizer(Recognizer):
     """recognize/speech2text.py:6-153.
     joint_ctc=False (the default, as in the reference): attention decoder (+ LM shallow fusion) only; ctc_weight is accepted and unused.
@@ -529,13 +559,20 @@ class SpeechToTextRecognizer(Recognizer):
     phrase-biased search (ops.ctc_prefix_beam_search_bias, with the n-gram too where one is given): a phrase the acoustic model ranks
     below the beam can then reach the second pass.  The acoustic term becomes scores - lm_scores - bias_scores of that search and the
     total of a hypothesis keeps its formula; only which hypotheses are rescored changes.  bias_first_pass=True needs rescore=True and
-    a bias, and none of the phrases may hold the CTC head's blank."""
+    a bias, and none of the phrases may hold the CTC head's blank.
+    mbr=True: minimum Bayes risk selection, in every mode.  The whole final beam (not only the nbest kept) is taken as a posterior,
+    softmax(mbr_scale * score), every hypothesis gets its expected edit distance against the others under it (ops.nbest_consensus,
+    include/otrans_hip.h otr_nbest_consensus) and the n-best is ordered by ascending risk, ties to the higher score, then the lower
+    rank, before nbest is cut; the scores returned are still the search's.  beam_width <= 32; a hypothesis of more than
+    ops.NBEST_MAX_LEN tokens is left out of the consensus and sorts last.  recognize_with_confidence gives the 1-best's tokens the
+    posterior mass that agrees with them, with or without mbr."""
 
     def __init__(self, model, lm=None, lm_weight=0.1, ctc_weight=0.0, beam_width=5, nbest=1, max_len=50,
                  idx2unit=None, penalty=0, lamda=5, ngpu=1, apply_cache=False, joint_ctc=False, ctc_beam=None, rescore=False,
                  cutoff_top_n=40, ngram_lm=None, alpha=0.1, beta=0.0, ngram_beam=None, bias=None, bias_beam=None,
-                 bias_first_pass=False):
+                 bias_first_pass=False, mbr=False, mbr_scale=1.0):
         super().__init__(model, idx2unit, lm, lm_weight, ngpu)
+        self.mbr, self.mbr_scale = _mbr_args('SpeechToTextRecognizer', mbr, mbr_scale, beam_width)
         if bias_first_pass and (not rescore or bias is None):
             raise ValueError('bias_first_pass=True biases the first pass of the two-pass decode: it needs rescore=True and bias=...')
         self.bias_first_pass = bool(bias_first_pass)
@@ -620,7 +657,7 @@ class SpeechToTextRecognizer(Recognizer):
         nbest_scores = sorted_scores[:, :min(beam, self.nbest)]
         return self.nbest_translate(nbest_preds), nbest_scores
 
-    def _nbest_device(self, scores, preds, steps, b):
+    def _nbest_device(self, scores, preds, steps, b, n=None):
         """_nbest's selection with torch ops on the device, no copy to the host: (tokens int64 [B, n, steps] without BOS, lengths int32
         [B, n]: a hypothesis ends before its first EOS, scores f32 [B, n]).  Equal scores may sort in another order than on the host.
         Without a length penalty the scores are the search's own, bit for bit _nbest's; with one the pow and the division run on
@@ -632,7 +669,7 @@ class SpeechToTextRecognizer(Recognizer):
             lengths = torch.sum(torch.ne(preds_d, EOS).float(), dim=-1)
             scores_d = scores_d / torch.pow((self.lamda + lengths) / (self.lamda + 1), self.penalty)
         sorted_scores, offset = torch.sort(scores_d, dim=-1, descending=True)
-        n = min(beam, self.nbest)
+        n = min(beam, self.nbest) if n is None else n
         tokens = torch.gather(preds_d, 1, offset[:, :n].unsqueeze(-1).expand(b, n, preds_d.size(-1)))[:, :, 1:].contiguous()
         is_eos = torch.eq(tokens, EOS)
         first = torch.where(is_eos.any(-1), is_eos.to(torch.int32).argmax(-1), torch.full_like(offset[:, :n], tokens.size(-1)))
@@ -643,13 +680,38 @@ class SpeechToTextRecognizer(Recognizer):
         """recognize() without the host: the n-best as device tensors (tokens int64 [B, n, L] without BOS, lengths int32 [B, n], scores
         f32 [B, n]), best first, for ops.edit_distance / evaluate.ErrorRateMeter.  The same searches and the same selection as
         recognize(): nbest_translate(tokens) gives its strings (it stops at the first EOS, which is where a length ends).  On the re-forward and cached
-        paths a hypothesis ends before its first EOS; on the rescore path the search's < 0 padding marks the end."""
+        paths a hypothesis ends before its first EOS; on the rescore path the search's < 0 padding marks the end.  With mbr=True the
+        n-best is in ascending order of risk."""
+        if self.mbr:
+            return self.recognize_tokens_with_confidence(inputs, inputs_mask)[:3]
+        return self._beam_device(inputs, inputs_mask, min(self.beam_width, self.nbest))
+
+    def _beam_device(self, inputs, inputs_mask, n):
+        """the n best-scoring hypotheses of the final beam as recognize_tokens returns them; n = beam_width: the whole beam"""
         if self.rescore:
-            res = self._rescore(inputs, inputs_mask)
+            res = self._rescore(inputs, inputs_mask, nbest=n)
             tok = res['tokens']
             return tok.masked_fill(tok < 0, EOS), torch.sum(tok >= 0, dim=-1, dtype=torch.int32), res['scores']
         search = self._search_cached if self.apply_cache else self._search
-        return self._nbest_device(*search(inputs, inputs_mask))
+        return self._nbest_device(*search(inputs, inputs_mask), n=n)
+
+    @torch.no_grad()
+    def recognize_tokens_with_confidence(self, inputs, inputs_mask):
+        """recognize_tokens() plus the consensus of the whole final beam (ops.nbest_consensus at mbr_scale), all on the device: (tokens,
+        lengths, scores of the n-best -- in ascending order of risk with mbr=True, by score otherwise --, conf f32 [B, L]: per token
+        of the 1-best the posterior mass of the hypotheses whose alignment matches it, post f32 [B]: the 1-best's own posterior)."""
+        return _consensus_nbest(*self._beam_device(inputs, inputs_mask, self.beam_width), self.mbr_scale, self.mbr,
+                                min(self.beam_width, self.nbest), EOS)
+
+    @torch.no_grad()
+    def recognize_with_confidence(self, inputs, inputs_mask):
+        """recognize() with token confidences: (texts: recognize()'s n-best strings, confidences: per utterance [(unit, confidence), ...]
+        for the 1-best, its units read in order being the words of its text, utt_posterior: the 1-best's posterior, a host tensor [B])"""
+        tokens, lengths, _, conf, post = self.recognize_tokens_with_confidence(inputs, inputs_mask)
+        tok, n, conf = tokens.cpu(), lengths.cpu(), conf.cpu()
+        texts = self.nbest_translate(torch.cat((tok, torch.full_like(tok[:, :, :1], EOS)), dim=-1))
+        confidences = [[(self.idx2unit[int(tok[b, 0, k])], float(conf[b, k])) for k in range(int(n[b, 0]))] for b in range(tok.size(0))]
+        return texts, confidences, post.cpu()
 
     @torch.no_grad()
     def recognize_cached(self, inputs, inputs_mask):
@@ -699,7 +761,7 @@ class SpeechToTextRecognizer(Recognizer):
         return self._rescore_out[1:]
 
     @torch.no_grad()
-    def rescore_pass(self, memory, memory_mask, log_probs, lengths):
+    def rescore_pass(self, memory, memory_mask, log_probs, lengths, nbest=None):
         """Everything of the two-pass decode behind the CTC head, on the device: the search over log_probs f32 [B, T', V], the pack, the
         decoder (and the LM) over all B x beam_width hypotheses at once, the scoring and the sorted n-best (ops.attention_rescore's
         dict plus 'beam' = the search's own (tokens, out_len, scores)).  No host synchronisation: capturable into one graph once the weight packs exist (after one eager call)."""
@@ -732,18 +794,19 @@ class SpeechToTextRecognizer(Recognizer):
         logits = _output(out_dec, dec.output_layer, dec.hidden(ys_in, memory, memory_mask, share=W))
         lm_logits = _lm_logits(lm, ys_in, out=out_lm, every=True)
         res = ops.attention_rescore(logits, tokens, out_len, ctc, self.max_len, V, self.ctc_weight, lm_logits=lm_logits,
-                                    lm_weight=float(self.lm_weight or 0.0) if lm is not None else 0.0, nbest=self.nbest,
+                                    lm_weight=float(self.lm_weight or 0.0) if lm is not None else 0.0,
+                                    nbest=self.nbest if nbest is None else nbest,
                                     penalty=self.penalty, lamda=self.lamda, packed=packed, bos=BOS, eos=EOS, add_score=add_score)
         res['beam'] = (tokens, out_len, scores)           # the first pass, in CTC order
         res['ctc'], res['ng'] = ctc, ng_score             # the terms of total beside att / lm (ng: None without an n-gram LM)
         res['bias'] = bias_score                          # ... and the phrase score (None without a PhraseBias)
         return res
 
-    def _rescore(self, inputs, inputs_mask):
-        """the two-pass decode of a batch: encoder, CTC head, rescore_pass"""
+    def _rescore(self, inputs, inputs_mask, nbest=None):
+        """the two-pass decode of a batch: encoder, CTC head, rescore_pass (nbest: how many it keeps, None: self.nbest)"""
         memory, memory_mask, _, _ = self.encode(inputs, inputs_mask)
         log_probs, length = self.model.assistor.inference(memory, memory_mask)
-        return self.rescore_pass(memory, memory_mask, log_probs.float().contiguous(), length)
+        return self.rescore_pass(memory, memory_mask, log_probs.float().contiguous(), length, nbest=nbest)
 
     @torch.no_grad()
     def recognize_rescore(self, inputs, inputs_mask):
@@ -754,6 +817,10 @@ class SpeechToTextRecognizer(Recognizer):
 
     @torch.no_grad()
     def recognize(self, inputs, inputs_mask):
+        if self.mbr:                                        # the risk-ordered n-best, selected on the device
+            tokens, _, scores = self.recognize_tokens(inputs, inputs_mask)
+            tok = tokens.cpu()
+            return self.nbest_translate(torch.cat((tok, torch.full_like(tok[:, :, :1], EOS)), dim=-1)), scores.cpu()
         if self.rescore:
             return self.recognize_rescore(inputs, inputs_mask)
         if self.apply_cache:
@@ -1066,11 +1133,17 @@ class CTCRecognizer(Recognizer):
     reference.  bias: None, or a bias.PhraseBias over the CTC head's units (phrase biasing, "hotwords"): in beam mode every extension
     s -> s c then gains psi_minus(state(s c)) - psi(state(s)) inside the search, behind the n-gram's addend if any, and a match left
     open at the end of the utterance is refunded (ops.ctc_prefix_beam_search_bias; include/otrans_hip.h otr_ctc_beam_search_bias).
-    Greedy mode ignores bias, as it ignores ngram_lm.  The alignment of recognize_with_times runs on the acoustic log-probs alone."""
+    Greedy mode ignores bias, as it ignores ngram_lm.  The alignment of recognize_with_times runs on the acoustic log-probs alone.
+    mbr=True (beam mode only): the beam_width hypotheses of the search are re-ordered by ascending risk under softmax(mbr_scale *
+    score), as SpeechToTextRecognizer does, and the 1-best everywhere is the hypothesis of least risk.  recognize_with_confidence gives
+    the 1-best's tokens the posterior mass that agrees with them (beam mode only: greedy decoding has no beam to take a consensus of)."""
 
     def __init__(self, model, lm=None, lm_weight=0.1, ngram_lm=None, beam_width=5, idx2unit=None, ngpu=1,
-                 mode='greedy', alpha=0.1, beta=0.0, cutoff_top_n=40, bias=None):
+                 mode='greedy', alpha=0.1, beta=0.0, cutoff_top_n=40, bias=None, mbr=False, mbr_scale=1.0):
         super().__init__(model, idx2unit, lm, lm_weight, ngpu)
+        if mbr and mode != 'beam':
+            raise ValueError("CTCRecognizer: mbr=True needs mode='beam': greedy decoding has no beam to take a consensus of")
+        self.mbr, self.mbr_scale = _mbr_args('CTCRecognizer', mbr, mbr_scale, beam_width)
         if mode not in ('greedy', 'beam'):
             raise NotImplementedError("CTCRecognizer mode '%s': 'greedy' and 'beam' are built" % mode)
         if mode == 'beam' and ngram_lm is not None and not isinstance(ngram_lm, NGramLM):
@@ -1134,14 +1207,50 @@ class CTCRecognizer(Recognizer):
 
     def _beam(self, log_probs, length, with_scores=False):
         """the beam of the CTC head's log-probs, with the n-gram LM and the phrases fused in where they were given: (tokens, out_len[,
-        scores])"""
+        scores]), in ascending order of risk with mbr=True"""
+        out = self._beam_search(log_probs, length)
+        if self.mbr:
+            out = _consensus_nbest(out[0], out[1].to(torch.int32), out[2].float(), self.mbr_scale, True, self.beam_width, -1)
+        return out[:3 if with_scores else 2]
+
+    def _beam_search(self, log_probs, length):
+        """the search's own (tokens, out_len, scores), best score first"""
         kw = dict(beam_width=self.beam_width, cutoff_top_n=self.cutoff_top_n, blank=self.model.assistor.blank)
         if self.bias is not None:
-            return ops.ctc_prefix_beam_search_bias(log_probs, length, self.bias, self.ngram_lm, self.alpha, self.beta,
-                                                   **kw)[:3 if with_scores else 2]
+            return ops.ctc_prefix_beam_search_bias(log_probs, length, self.bias, self.ngram_lm, self.alpha, self.beta, **kw)[:3]
         if self.ngram_lm is None:
-            return ops.ctc_prefix_beam_search(log_probs, length, **kw)[:3 if with_scores else 2]
-        return ops.ctc_prefix_beam_search_lm(log_probs, length, self.ngram_lm, self.alpha, self.beta, **kw)[:3 if with_scores else 2]
+            return ops.ctc_prefix_beam_search(log_probs, length, **kw)[:3]
+        return ops.ctc_prefix_beam_search_lm(log_probs, length, self.ngram_lm, self.alpha, self.beta, **kw)[:3]
+
+    @torch.no_grad()
+    def recognize_tokens_with_confidence(self, inputs, inputs_mask):
+        """recognize_tokens() plus the consensus of the search's beam_width hypotheses (ops.nbest_consensus at mbr_scale), on the device:
+        (tokens [B, 1, L], lengths [B, 1], scores [B, 1] of the 1-best -- the hypothesis of least risk with mbr=True --, conf f32 [B, L]:
+        per token the posterior mass of the hypotheses whose alignment matches it, post f32 [B]: the 1-best's own posterior)."""
+        if self.mode != 'beam':
+            raise ValueError("CTCRecognizer: confidences need mode='beam': greedy decoding has no beam to take a consensus of")
+        memory, memory_mask = self._encode(inputs, inputs_mask)
+        log_probs, length = self.model.assistor.inference(memory, memory_mask)
+        tokens, out_len, scores = self._beam_search(log_probs, length)
+        return _consensus_nbest(tokens, out_len.to(torch.int32), scores.float(), self.mbr_scale, self.mbr, 1, -1)
+
+    @torch.no_grad()
+    def recognize_with_confidence(self, inputs, inputs_mask):
+        """recognize() with token confidences: (texts, confidences: per utterance [(unit, confidence), ...] for the 1-best, its units
+        read in order being the words of its text as in recognize_with_times, utt_posterior: the 1-best's posterior, a host tensor [B])"""
+        tokens, lengths, _, conf, post = self.recognize_tokens_with_confidence(inputs, inputs_mask)
+        tok, n, conf = tokens[:, 0].cpu(), lengths[:, 0].cpu(), conf.cpu()
+        preds = [tok[b, :int(n[b])].tolist() for b in range(tok.size(0))]
+        confidences = []
+        for b, pred in enumerate(preds):
+            items = []
+            for k, t in enumerate(pred):                   # translate()'s walk: a list ends before its first EOS and skips PAD
+                if t == EOS:
+                    break
+                if t != PAD:
+                    items.append((self.idx2unit[t], float(conf[b, k])))
+            confidences.append(items)
+        return self.translate(preds), confidences, post.cpu()
 
     @torch.no_grad()
     def recognize_tokens(self, inputs, inputs_mask):
@@ -1234,7 +1343,8 @@ def build_recognizer(model_type, model, lm, args, idx2unit):
                                       rescore=getattr(args, 'rescore', False), ngram_lm=ngram_lm,
                                       ngram_beam=getattr(args, 'ngram_beam', None), bias=bias,
                                       bias_beam=getattr(args, 'bias_beam', None),
-                                      bias_first_pass=getattr(args, 'bias_first_pass', False), **kw)
+                                      bias_first_pass=getattr(args, 'bias_first_pass', False), mbr=getattr(args, 'mbr', False),
+                                      mbr_scale=getattr(args, 'mbr_scale', 1.0), **kw)
     if model_type == 'ctc':
         ngram_lm = args.ngram_lm
         if isinstance(ngram_lm, str):                                           # the reference passes the path on to ctcdecode
@@ -1246,5 +1356,6 @@ def build_recognizer(model_type, model, lm, args, idx2unit):
                                              vocab_size=model.assistor.output_layer.weight.shape[0])
         return CTCRecognizer(model=model, lm=lm, lm_weight=args.lm_weight, ngram_lm=ngram_lm,
                              beam_width=args.beam_width, idx2unit=idx2unit, ngpu=args.ngpu, mode=args.mode,
-                             alpha=args.alpha, beta=args.beta, bias=bias)
+                             alpha=args.alpha, beta=args.beta, bias=bias, mbr=getattr(args, 'mbr', False),
+                             mbr_scale=getattr(args, 'mbr_scale', 1.0))
     raise NotImplementedError
