@@ -26,6 +26,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from .bias import PhraseBias
+from .decode_ops import _rescore_check
 from .ngram import NGramLM
 from .nn import (BOS, EOS, PAD, LabelSmoothingLoss, PositionalEncoding, TransformerEncoderLayer)
 
@@ -590,7 +591,7 @@ class SpeechToTextRecognizer(Recognizer):
                 raise ValueError('rescore=True replaces the step loop: not together with %s' % ('joint_ctc=True' if joint_ctc else 'apply_cache=True'))
             if getattr(model, 'assistor', None) is None:
                 raise ValueError('rescore=True needs the model\'s CTC head (model.assistor): build the model with ctc_weight > 0')
-            ops._rescore_check('rescore=True', beam_width, model.decoder.output_layer.weight.shape[0], nbest, ctc_weight)
+            _rescore_check('rescore=True', beam_width, model.decoder.output_layer.weight.shape[0], nbest, ctc_weight)
             if max_len < 1 or self.cutoff_top_n < 1:
                 raise ValueError('rescore=True: max_len=%d and cutoff_top_n=%d must be >= 1' % (max_len, self.cutoff_top_n))
             if lm is not None and _lm_recurrent(lm) is None:
