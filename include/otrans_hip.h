@@ -40,7 +40,7 @@ extern "C" {
  * bump; 602: the rescoring entries, additions only; 603: otr_ctc_align, additions only; 604: otr_ngram_lookup and otr_ctc_beam_search_lm, additions only; 605:
  * otr_edit_distance, additions only; 606: otr_ngram_score_cands, otr_ngram_score_seqs and otr_rescore_select_add, additions only; 607: otr_ngram_count, otr_ngram_stats and otr_ngram_estimate, additions only;
  * 608: otr_mwer_workspace_floats and otr_mwer_loss, additions only; still 608: otr_feature_prepare_workspace_bytes, otr_feature_prepare and
- * otr_cmvn_accumulate, after them otr_ctc_segment_workspace_bytes and otr_ctc_segment, and after those otr_distill_workspace_floats and otr_distill_loss (additions only), after those otr_bias_score_cands and otr_bias_score_seqs (additions only), and otr_ctc_beam_search_bias (an addition only), and last otr_edit_align and otr_nbest_consensus (additions only), were added without a bump -- no existing signature, structure or meaning changed, and a binding that needs them
+ * otr_cmvn_accumulate, after them otr_ctc_segment_workspace_bytes and otr_ctc_segment, and after those otr_distill_workspace_floats and otr_distill_loss (additions only), after those otr_bias_score_cands and otr_bias_score_seqs (additions only), and otr_ctc_beam_search_bias (an addition only), after them otr_edit_align and otr_nbest_consensus (additions only), and last otr_mixspeech_mix and otr_ctc_loss_pair (additions only), were added without a bump -- no existing signature, structure or meaning changed, and a binding that needs them
  * fails on the missing symbol of an older library when it loads it).  A binding compares otr_version() with the OTR_ABI_VERSION it was written against BEFORE its first call and refuses a
  * library that answers anything else: descriptors are passed by pointer and read at the library's idea of their size. */
 #define OTR_ABI_VERSION 608
@@ -632,6 +632,43 @@ int32_t otr_conformer_conv_bwd_mid(const float* y, const void* ds, const float* 
 int32_t otr_ctc_loss(const float* log_probs, const int64_t* targets, int64_t ldt, const int32_t* in_len,
                      const int32_t* tgt_len, int32_t B, int32_t T, int32_t V, int32_t max_tgt, int32_t blank,
                      float* alpha_ws, float* nll, float* loss, float* dlogits, void* stream);
+
+/* ---- MixSpeech on the device (otrans/train/trainer.py:155-201, Trainer(mixspeech=True)); csrc/mixspeech.hip and csrc/ctc.hip.
+ * otr_mixspeech_mix: utterances 2p and 2p + 1 of a padded batch mixed frame by frame, P = B / 2 pairs (integer division: an odd last
+ *   utterance takes no part, trainer.py:160).  x f32 [B, T, F], utterance b at x + b * pitch (pitch >= T * F floats); lengths int32 [B],
+ *   clamped to [0, T]; lam a DEVICE f32 scalar, read by the kernel, never by the host.
+ *   out f32 [P, T, F] (contiguous): out[p, t, :] = lam * x[2p, t, :] + (1 - lam) * x[2p + 1, t, :], where a frame t >= lengths[b] of an
+ *   input utterance counts as 0.0f and is NOT read (the reference mixes the collate's zero padding: the same result, and padding that is
+ *   not zero cannot leak in).  1 - lam is rounded to f32 once, each product is rounded, then the sum: bit for bit the float32 numpy /
+ *   torch composition of trainer.py:172-173 (no fused multiply-add).
+ *   out_lengths int32 [P] = max(lengths[2p], lengths[2p + 1]) after the clamp; out_mask uint8 [P, T] = 1 where t < out_lengths[p], the
+ *   form otr_feature_prepare writes; frames at or past out_lengths[p] are written as exactly 0.0f.  EVERY cell of the three outputs is
+ *   written (they may be uninitialised).
+ *   One launch.  Loads and stores are 16 bytes wide where an utterance's base is 16-byte aligned (x[2p], x[2p + 1] and out[p] judged
+ *   separately), scalar otherwise and in the tail of a live span.  Refused before the launch (< 0, outputs untouched): a NULL pointer;
+ *   B < 2, B / 2 > 65535, T < 1, F < 1, T * F >= 2^31; pitch < T * F.  No allocation or host synchronisation: capturable.
+ * otr_ctc_loss_pair: the CTC term of MixSpeech in one call.  log_probs f32 [P, T, V] and in_len int32 [P] are scored against two label
+ *   sets: a = (targets_a int64 rows of stride ldt_a, tgt_len_a int32 [P]) with weight lam, b likewise with weight 1 - lam (lam a DEVICE
+ *   f32 scalar).  The two sets may be the even and the odd rows of one [B, W] matrix (ldt = 2W): nothing is copied.  max_tgt, blank and
+ *   the guards on in_len and tgt_len are those of otr_ctc_loss; in addition a label outside [0, V) makes its (utterance, set) infeasible.
+ *   nll f32 [2, P]: row k what otr_ctc_loss writes for set k alone (0 where infeasible or guarded).
+ *   loss3 f32 [3] = {lam * loss_a + (1 - lam) * loss_b, loss_a, loss_b}, loss_k = sum_p nll[k, p] / (P * max(L_kp, 1)): otr_ctc_loss's
+ *   value for set k, here added in utterance order (no atomics).
+ *   dlogits f32 [P, T, V] (NULL: losses only) = lam * g_a + (1 - lam) * g_b with g_k what otr_ctc_loss writes for set k alone.  An
+ *   infeasible or guarded (utterance, set) adds nothing and leaves the other set's share of the slab intact; where both are, the slab
+ *   is exactly zero, as are the frames at or past in_len.  A set whose weight is exactly 0 adds nothing whatever its labels are.
+ *   alpha_ws: f32 [2, P, T, 2 * max_tgt + 1] workspace.  Launches: the two sets' alpha sweeps side by side; one dense pass over [P, T, V]
+ *   (coefficient lam * ok_a * coef_a + (1 - lam) * ok_b * coef_b, known only after both sweeps; it also forms loss3); the two beta sweeps,
+ *   whose occupancies are added onto the slab with fp32 atomics (as in otr_ctc_loss, their order is free).  With the caller's
+ *   log-softmax that is ONE log-softmax and ONE dense pass where two otr_ctc_loss calls make two of each.
+ *   Refused before any launch (< 0, outputs untouched): a NULL pointer other than dlogits; P outside [1, 65535], T < 1, V < 2; max_tgt
+ *   outside [0, 127]; ldt_a or ldt_b below max_tgt; blank outside [0, V).  Capturable. */
+int32_t otr_mixspeech_mix(const float* x, int64_t pitch, const int32_t* lengths, const float* lam, int32_t B, int32_t T, int32_t F,
+                          float* out, int32_t* out_lengths, uint8_t* out_mask, void* stream);
+int32_t otr_ctc_loss_pair(const float* log_probs, const int64_t* targets_a, int64_t ldt_a, const int32_t* tgt_len_a,
+                          const int64_t* targets_b, int64_t ldt_b, const int32_t* tgt_len_b, const int32_t* in_len, const float* lam,
+                          int32_t P, int32_t T, int32_t V, int32_t max_tgt, int32_t blank, float* alpha_ws, float* nll, float* loss3,
+                          float* dlogits, void* stream);
 
 /* ---- one optimizer update over a replica's FLAT buffers (train/trainer.py:221-234 clip_grad_norm_(5) + gradient noise +
  *      NaN guard + scheduler.step + optimizer.step; train/scheduler.py:129-138 Noam lr; torch Adam with

@@ -3536,6 +3536,112 @@ class CTCLossFn(torch.autograd.Function):
         return out, None, None, None, None
 
 
+# ------------------------------------------------------------------ MixSpeech (csrc/mixspeech.hip, csrc/ctc.hip)
+CTC_MAX_TGT = 127
+
+
+class CTCLossPairFn(torch.autograd.Function):
+    """The CTC term of MixSpeech (include/otrans_hip.h otr_ctc_loss_pair): ONE log-softmax of the logits, scored against two label sets
+    with the device weights lam and 1 - lam, and one gradient lam * g_a + (1 - lam) * g_b written by the forward call.  Returns
+    (loss, loss_a, loss_b, nll [2, P]); only loss is differentiable.  backward scales the saved gradient by the incoming seed
+    (_saved_logits_grad: the buffer itself for the cached unit seed of ops.backward)."""
+
+    @staticmethod
+    def forward(ctx, logits, targets_a, targets_b, in_len, tgt_len_a, tgt_len_b, lam, blank):
+        P, T, V = logits.shape
+        lp = log_softmax(logits)
+        max_tgt = targets_a.shape[1]
+        dev = logits.device
+        f32 = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)    # noqa: E731
+        ws, nll, loss3 = f32(2, P, T, 2 * max_tgt + 1), f32(2, P), f32(3)
+        dlogits = f32(P * T, V) if ctx.needs_input_grad[0] else None
+        L.check(L.load().otr_ctc_loss_pair(_p(lp), _p(targets_a), targets_a.stride(0), _p(tgt_len_a), _p(targets_b), targets_b.stride(0),
+                                           _p(tgt_len_b), _p(in_len), _p(lam), P, T, V, max_tgt, blank, _p(ws), _p(nll), _p(loss3),
+                                           _p(dlogits), _stream()), 'otr_ctc_loss_pair')
+        ctx.save_for_backward(dlogits)
+        ctx.shape, ctx.V = logits.shape, V
+        loss, loss_a, loss_b = loss3[0], loss3[1], loss3[2]
+        ctx.mark_non_differentiable(loss_a, loss_b, nll)
+        return loss, loss_a, loss_b, nll
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        return _saved_logits_grad(ctx, g), None, None, None, None, None, None, None
+
+
+def _label_rows(who, name, t, P):
+    if t.dim() != 2 or t.shape[0] != P:
+        raise ValueError('%s: %s must be [P, W] = [%d, W], got %s' % (who, name, P, tuple(t.shape)))
+
+
+def ctc_loss_pair(logits, targets_a, targets_b, in_len, tgt_len_a, tgt_len_b, lam, blank=0):
+    """lam * CTC(logits, a) + (1 - lam) * CTC(logits, b) in one call (include/otrans_hip.h otr_ctc_loss_pair), each term what CTCLossFn
+    computes for that label set alone ('mean' over the P utterances of nll / max(L, 1), zero_infinity).  logits f32 [P, T, V];
+    targets_a / targets_b int64 [P, W], W <= 127, unit inner stride -- views with a longer row stride (the even and odd rows of one
+    matrix) are read in place; in_len, tgt_len_a, tgt_len_b [P] (int32 or int64); lam a 1-element f32 DEVICE tensor, never read by the
+    host.  Returns (loss, loss_a, loss_b): loss carries the gradient, loss_a and loss_b are detached device scalars.  One log-softmax,
+    three launches, no host synchronisation: capturable."""
+    who = 'ctc_loss_pair'
+    if logits.dim() != 3:
+        raise ValueError('%s: logits must be [P, T, V], got %s' % (who, tuple(logits.shape)))
+    P, T, V = logits.shape
+    if P < 1 or T < 1 or V < 2:
+        raise ValueError('%s: logits [P, T, V] = %s need P >= 1, T >= 1 and V >= 2' % (who, (P, T, V)))
+    _label_rows(who, 'targets_a', targets_a, P)
+    _label_rows(who, 'targets_b', targets_b, P)
+    if targets_a.shape[1] != targets_b.shape[1]:
+        raise ValueError('%s: the two label sets have widths %d and %d, one padded width expected' % (who, targets_a.shape[1], targets_b.shape[1]))
+    if targets_a.shape[1] > CTC_MAX_TGT:
+        raise ValueError('%s: target width %d > %d not supported' % (who, targets_a.shape[1], CTC_MAX_TGT))
+    for name, t in (('in_len', in_len), ('tgt_len_a', tgt_len_a), ('tgt_len_b', tgt_len_b)):
+        if t.numel() != P:
+            raise ValueError('%s: %s must hold P = %d entries, got %s' % (who, name, P, tuple(t.shape)))
+    if not torch.is_tensor(lam) or lam.numel() != 1:
+        raise ValueError('%s: lam must be a 1-element device tensor, got %r' % (who, lam if not torch.is_tensor(lam) else tuple(lam.shape)))
+    if not 0 <= int(blank) < V:
+        raise ValueError('%s: blank=%r outside [0, V=%d)' % (who, blank, V))
+    _cuda(logits, targets_a, targets_b, in_len, tgt_len_a, tgt_len_b, lam)
+    if (logits.dtype != torch.float32 or targets_a.dtype != torch.int64 or targets_b.dtype != torch.int64 or lam.dtype != torch.float32
+            or any(t.dtype not in (torch.int32, torch.int64) for t in (in_len, tgt_len_a, tgt_len_b))):
+        raise L.OtransHipError('%s: logits f32, targets int64, lengths int32 (or int64), lam f32 expected' % who)
+    W = targets_a.shape[1]
+    rows = [t if (t.stride(1) == 1 and t.stride(0) >= W) or W == 0 else t.contiguous() for t in (targets_a, targets_b)]
+    lens = [t.reshape(-1).to(torch.int32).contiguous() for t in (in_len, tgt_len_a, tgt_len_b)]
+    loss, loss_a, loss_b, _ = CTCLossPairFn.apply(logits, rows[0], rows[1], lens[0], lens[1], lens[2], lam.detach(), int(blank))
+    return loss, loss_a, loss_b
+
+
+def mixspeech_mix(x, lengths, lam):
+    """The mixed half batch of MixSpeech (include/otrans_hip.h otr_mixspeech_mix): x f32 [B, T, F] (unit stride over T and F; the
+    utterance pitch is passed on), lengths [B] (int32 or int64), lam a 1-element f32 DEVICE tensor.  Returns (out f32 [P, T, F],
+    out_lengths int32 [P], out_mask bool [P, T]) with P = B // 2: out[p] = lam * x[2p] + (1 - lam) * x[2p + 1] bit for bit as float32
+    torch forms it on zero-padded input, with the length and mask of the longer utterance.  Frames at or past an utterance's length are
+    not read.  One launch, no host synchronisation, no gradient (the features are data)."""
+    who = 'mixspeech_mix'
+    if x.dim() != 3:
+        raise ValueError('%s: x must be [B, T, F], got %s' % (who, tuple(x.shape)))
+    B, T, F_ = x.shape
+    if B < 2 or T < 1 or F_ < 1:
+        raise ValueError('%s: x [B, T, F] = %s needs B >= 2, T >= 1 and F >= 1' % (who, (B, T, F_)))
+    if lengths.numel() != B:
+        raise ValueError('%s: lengths must hold B = %d entries, got %s' % (who, B, tuple(lengths.shape)))
+    if not torch.is_tensor(lam) or lam.numel() != 1:
+        raise ValueError('%s: lam must be a 1-element device tensor, got %r' % (who, lam if not torch.is_tensor(lam) else tuple(lam.shape)))
+    _cuda(x, lengths, lam)
+    if x.dtype != torch.float32 or lam.dtype != torch.float32 or lengths.dtype not in (torch.int32, torch.int64):
+        raise L.OtransHipError('%s: x f32, lengths int32 (or int64), lam f32 expected' % who)
+    x = x.detach()
+    if not (x.stride(2) == 1 and x.stride(1) == F_ and x.stride(0) >= T * F_):
+        x = x.contiguous()
+    P = B // 2
+    out = torch.empty((P, T, F_), dtype=torch.float32, device=x.device)
+    out_len = torch.empty((P,), dtype=torch.int32, device=x.device)
+    out_mask = torch.empty((P, T), dtype=torch.bool, device=x.device)
+    L.check(L.load().otr_mixspeech_mix(_p(x), x.stride(0), _p(lengths.reshape(-1).to(torch.int32).contiguous()), _p(lam), B, T, F_, _p(out),
+                                       _p(out_len), _p(out_mask), _stream()), 'otr_mixspeech_mix')
+    return out, out_len, out_mask
+
+
 # ------------------------------------------------------------------ minimum word error rate training (csrc/mwer.hip)
 MWER_MAX_NBEST, MWER_MAX_V = 32, 8192
 
