@@ -349,7 +349,9 @@ typedef struct {
   uint64_t rng_offset;
   float a_scale;                /* r05: y = LN(x + a_scale * dropout(a)), da = a_scale * dropout'(dz); 0 means 1 (older callers) */
   const uint8_t* a_row_mask;    /* r05: [M] or NULL; rows with 0 take no branch: a row := 0 forward, da row := 0 backward (the
-                                 * masked_fill of module/conformer.py:109 folded into the residual add that consumes the branch) */
+                                 * masked_fill of module/conformer.py:109 folded into the residual add that consumes the branch).
+                                 * A fill, not a multiply: `a` of a masked row is not read, whatever it holds (NaN, Inf) stays out
+                                 * of z, y and the statistics, and da of a masked row or a dropped element is exactly 0 */
   int32_t dy_dtype;             /* r06, backward entries: OTR_F32 (0) or the library's 16-bit type -- the LayerNorm's output fed a 16-bit
                                  * reader only (a Linear), whose input gradient then comes back in that type (half the bytes of the
                                  * input-gradient GEMM's output); forward entries may pass y = NULL then and write the 16-bit twin alone */
@@ -366,7 +368,8 @@ int32_t otr_add_layernorm_bwd(const otr_ln_desc_t* d, const float* dy, const flo
                               float* dgamma, float* dbeta, float* da_colsum, float* partial, void* stream);
 /* partial (may be NULL): f32 [otr_add_layernorm_bwd_partial_rows(M), 3, d].  When given, NOTHING is added to dgamma / dbeta /
  * da_colsum (they may be NULL); each workgroup writes its own sums (dgamma | dbeta | da column sums) to its row and the
- * caller column-sums the rows (otr_colsum / otr_colsum_grouped): no atomics, deterministic. */
+ * caller column-sums the rows (otr_colsum / otr_colsum_grouped): no atomics, deterministic.  With da == NULL there are no da column
+ * sums: segment 2 ([.., 2, d], and columns [2d, 3d) of the 5 d / 7 d forms below) is NOT written and keeps what it held -- do not sum it. */
 int64_t otr_add_layernorm_bwd_partial_rows(int64_t M);
 /* the same with dx = skip + (gradient w.r.t. the LayerNorm input), skip f32 [M,d] or NULL: a pre-norm residual
  * x + f(LN(x)) (encoder/conformer.py:50-73; normalize_before layers) hands x two gradients, and this saves the elementwise
@@ -380,7 +383,8 @@ int32_t otr_add_layernorm_bwd_skip(const otr_ln_desc_t* d, const float* dy, cons
  * the result of the convolution branch's residual add) -- in one launch each way (r05).  Forward writes y2 (+ 16-bit twin), the pre-norm
  * sum z and both LayerNorms' row statistics; backward takes d y2, recomputes y1 = LN1(z) from z / mean / rstd, and leaves
  * partial f32 [otr_add_layernorm_bwd_partial_rows(M)][5 d] = per-workgroup sums of dgamma | dbeta | da | dgamma2 | dbeta2 (the
- * caller column-sums them).  skip / dx / da as otr_add_layernorm_bwd_skip. */
+ * caller column-sums them).  skip / dx / da as otr_add_layernorm_bwd_skip.  d y2 is f32: otr_add_layernorm2_bwd and
+ * otr_add_layernorm3_bwd refuse a descriptor whose dy_dtype is not OTR_F32 (only d y3 may be 16-bit, by dy3_dtype). */
 int32_t otr_add_layernorm2_fwd(const otr_ln_desc_t* d, const float* x, const void* a, const float* gamma, const float* beta,
                                const float* gamma2, const float* beta2, const uint64_t* seed, float* y2, void* y2_bf16, float* z,
                                float* mean, float* rstd, float* mean2, float* rstd2, void* stream);

@@ -45,6 +45,31 @@ __device__ __forceinline__ float drop_scale(uint64_t seed, uint64_t idx, uint32_
   return otr_rand32(seed, idx) >= thr ? inv_keep : 0.f;
 }
 
+// one row of z = x [+ a * sc] into the lane's registers (and p.z), with the lane's share of the row sum
+template <class AT, bool WITH_A>
+__device__ __forceinline__ void ln_fwd_load_row(const LnArgs& p, int64_t row, int lane, bool drop, uint64_t seed, uint32_t thr, float inv_keep,
+                                                float (&v)[LN_MAXV][4], float& s) {
+  const int d = p.d;
+#pragma unroll
+  for (int i = 0; i < LN_MAXV; ++i) {
+    int col = (i * 64 + lane) * 4;
+    if (col < d) {
+      ld4<float>(p.x + row * d + col, v[i]);
+      if constexpr (WITH_A) {
+        float a[4];
+        ld4<AT>(reinterpret_cast<const AT*>(p.a) + row * d + col, a);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float sc = drop ? drop_scale(seed, p.rng_offset + (uint64_t)(row * d + col + e), thr, inv_keep) : inv_keep;
+          v[i][e] += a[e] * sc;
+        }
+      }
+      if (p.z) st4<float>(p.z + row * d + col, v[i]);
+      s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
+    }
+  }
+}
+
 template <class AT, bool HAS_A, bool LN2 = false> __global__ __launch_bounds__(256) void add_ln_fwd_kernel(LnArgs p) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int64_t row = (int64_t)blockIdx.x * 4 + wid;
@@ -56,25 +81,11 @@ template <class AT, bool HAS_A, bool LN2 = false> __global__ __launch_bounds__(2
   const float inv_keep = (drop ? 1.f / (1.f - p.p_drop) : 1.f) * p.a_scale;
   float v[LN_MAXV][4];
   float s = 0.f;
-  const float am = (HAS_A && p.amask) ? (p.amask[row] ? 1.f : 0.f) : 1.f;
-#pragma unroll
-  for (int i = 0; i < LN_MAXV; ++i) {
-    int col = (i * 64 + lane) * 4;
-    if (col < d) {
-      ld4<float>(p.x + row * d + col, v[i]);
-      if constexpr (HAS_A) {
-        float a[4];
-        ld4<AT>(reinterpret_cast<const AT*>(p.a) + row * d + col, a);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float sc = drop ? drop_scale(seed, p.rng_offset + (uint64_t)(row * d + col + e), thr, inv_keep) : inv_keep;
-          v[i][e] += a[e] * sc * am;
-        }
-      }
-      if (p.z) st4<float>(p.z + row * d + col, v[i]);
-      s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
-    }
-  }
+  // (wave-uniform: one row per wave) a masked row takes no branch by a select -- its `a` is neither loaded nor added, so a NaN / Inf
+  // there (padded frames of a 16-bit branch) never reaches z, the statistics or y; a multiply with 0 would pass it on.  The select is
+  // around the whole row, so the loads of an unmasked row are issued as they always were
+  if (HAS_A && (!p.amask || p.amask[row] != 0)) ln_fwd_load_row<AT, true>(p, row, lane, drop, seed, thr, inv_keep, v, s);
+  else ln_fwd_load_row<AT, false>(p, row, lane, drop, seed, thr, inv_keep, v, s);
   const float mean = wave_sum(s) / d;
   float q = 0.f;
 #pragma unroll
@@ -336,12 +347,12 @@ template <class AT, bool HAS_A, int NV, bool LN2 = false> __global__ __launch_bo
           st4<float>(p.dx + row * d + col, dz);
           if constexpr (HAS_A) {
             if (p.da) {
-              const float am = p.amask ? (p.amask[row] ? 1.f : 0.f) : 1.f;
+              const bool take_a = !p.amask || p.amask[row] != 0;      // a select, as forward: da of a masked row is 0 whatever dz holds
               float o[4];
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
                 float sc = drop ? drop_scale(seed, p.rng_offset + (uint64_t)(row * d + col + e), thr, inv_keep) : inv_keep;
-                o[e] = dz[e] * sc * am;
+                o[e] = take_a ? dz[e] * sc : 0.f;
                 dab[i][e] += o[e];
               }
               st4<AT>(reinterpret_cast<AT*>(p.da) + row * d + col, o);
@@ -516,6 +527,7 @@ extern "C" int32_t otr_add_layernorm2_bwd(const otr_ln_desc_t* d, const float* d
   if (int32_t e = ln_check(d)) return e;
   OTR_REQUIRE(dy2 && z && mean && rstd && gamma && beta && mean2 && rstd2 && gamma2 && dx && partial, "add_layernorm2_bwd: null pointer");
   OTR_REQUIRE(d->p_drop == 0.f || seed, "add_layernorm2_bwd: dropout needs seed");
+  OTR_REQUIRE(d->dy_dtype == OTR_F32, "add_layernorm2_bwd: dy2 is read as f32, dy_dtype=%d", d->dy_dtype);
   if (d->M == 0) return 0;
   LnArgs p{};
   p.dy = dy2; p.zin = z; p.mean = const_cast<float*>(mean); p.rstd = const_cast<float*>(rstd); p.gamma = gamma; p.beta = beta;
@@ -562,7 +574,7 @@ extern "C" int32_t otr_add_layernorm3_fwd(const otr_ln_desc_t* d, const float* x
   return otr_check_launch("add_layernorm3_fwd");
 }
 
-// d y2 (may be NULL: zeros) and d y3 -> dx (= skip + d z), da; partial f32 [otr_add_layernorm_bwd_partial_rows(M)][7 d]:
+// d y2 (f32, required: the caller passes zeros when none arrived) and d y3 -> dx (= skip + d z), da; partial f32 [otr_add_layernorm_bwd_partial_rows(M)][7 d]:
 // dgamma | dbeta | da column sums | dgamma2 | dbeta2 | dgamma3 | dbeta3
 extern "C" int32_t otr_add_layernorm3_bwd(const otr_ln_desc_t* d, const float* dy2, const void* dy3, int32_t dy3_dtype, const float* z, const float* mean,
                                           const float* rstd, const float* gamma, const float* beta, const float* mean2, const float* rstd2,
@@ -572,6 +584,7 @@ extern "C" int32_t otr_add_layernorm3_bwd(const otr_ln_desc_t* d, const float* d
   OTR_REQUIRE(dy2 && dy3 && z && mean && rstd && gamma && beta && mean2 && rstd2 && gamma2 && beta2 && mean3 && rstd3 && gamma3 && dx && partial,
               "add_layernorm3_bwd: null pointer");
   OTR_REQUIRE(d->p_drop == 0.f || seed, "add_layernorm3_bwd: dropout needs seed");
+  OTR_REQUIRE(d->dy_dtype == OTR_F32, "add_layernorm3_bwd: dy2 is read as f32, dy_dtype=%d (d y3 has dy3_dtype)", d->dy_dtype);
   if (d->M == 0) return 0;
   LnArgs p{};
   OTR_REQUIRE(dy3_dtype == OTR_F32 || dy3_dtype == OTR_H16, "add_layernorm3_bwd: bad dy3 dtype");

@@ -116,6 +116,12 @@ def test_argument_errors_of_the_fused_and_grouped_entries():
     assert lib.otr_add_layernorm2_fwd(C.byref(lnd), one, one, one, one, None, one, None, one, None, one, one, one, one, one, None) < 0   # gamma2 missing
     assert lib.otr_add_layernorm2_bwd(C.byref(lnd), one, one, one, one, one, one, one, one, one, None, None, one, one, None, None) < 0   # no partial buffer
     assert b'add_layernorm2_bwd' in lib.otr_last_error_string()
+    ln16 = _lib.LnDesc(8, 16, 0, 1e-5, 0.0, 0, 0.0, None, hcode)                                          # d y2 is f32, whatever dy_dtype says
+    assert lib.otr_add_layernorm2_bwd(C.byref(ln16), one, one, one, one, one, one, one, one, one, None, None, one, one, one, None) < 0
+    assert b'add_layernorm2_bwd: dy2 is read as f32' in lib.otr_last_error_string()
+    assert lib.otr_add_layernorm3_bwd(C.byref(ln16), one, one, 0, one, one, one, one, one, one, one, one, one, one, one, one, None, None, one, one,
+                                      one, None) < 0
+    assert b'add_layernorm3_bwd: dy2 is read as f32' in lib.otr_last_error_string()
     assert lib.otr_dwconv_fwd_part(one, hcode, one, None, one, None, 2, 8, 16, 5, 2, None) < 0                 # no partial buffer
     assert lib.otr_bn_swish_fwd_part(one, one, 0, one, one, None, None, one, one, hcode, 16, 16, 1e-5, 0.1, None) < 0   # no partial rows
     assert lib.otr_dwconv_fwd_partial_rows(7968) == 249

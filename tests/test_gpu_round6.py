@@ -276,13 +276,14 @@ def test_residual_layernorm3_matches_torch(mode, M, d):
         g3 = torch.randn(2, M, d, generator=g).to(DEV)
         outs = (z, y2, y3)
         grads = torch.autograd.grad(outs, [x, a] + [p for n in norms for p in (n.weight, n.bias)], (gz, g2, g3.to(y3.dtype)))
-        gref = torch.autograd.grad((zr, y2r, y3r), [xr, ar] + ps, (gz, g2, g3.to(y3.dtype).float()))
+        gref = torch.autograd.grad((zr, y2r, y3r), [xr, ar] + ps, (gz, g2, g3.to(y3.dtype).float()), retain_graph=True)
         for nm, u, v in zip(('dx', 'da', 'dg1', 'db1', 'dg2', 'db2', 'dg3', 'db3'), grads, gref):
             assert rel(u.float(), v) < (1e-4 if mode == 'fp32' else tol), (nm, rel(u.float(), v))
         # only d y3 arrives (the others None): zeros stand in
         g_only3 = torch.autograd.grad(ops.residual_layernorm3(x, a, 0.5, 0.0, norms[0], norms[1], norms[2], a_mask=am)[2], x, g3.to(y3.dtype))[0]
-        r_only3 = torch.autograd.grad(y3r, xr, g3.to(y3.dtype).float(), retain_graph=True)[0] if False else None
+        r_only3 = torch.autograd.grad(y3r, xr, g3.to(y3.dtype).float())[0]
         assert torch.isfinite(g_only3).all()
+        assert rel(g_only3, r_only3) < (1e-4 if mode == 'fp32' else tol), rel(g_only3, r_only3)
     finally:
         ops.set_compute_dtype('bf16')
 
