@@ -1,6 +1,6 @@
 """What every wrapper over the C ABI needs and nothing else: the process state, the kernel-timing hook, the device check, torch's
-current stream and a tensor's address.  ops.py imports these back under the same names; a leaf module (decode_ops.py, data_ops.py)
-imports this module and never ops."""
+current stream, a tensor's address and a lengths vector in the ABI's form.  ops.py imports these back under the same names; a leaf
+module (decode_ops.py, data_ops.py) imports this module and never ops."""
 import ctypes as C
 
 import torch
@@ -46,3 +46,8 @@ def _p(t, offset_elems=0):
     if t is None:
         return None
     return C.c_void_p(t.data_ptr() + offset_elems * t.element_size())
+
+
+def _len32(t):
+    """a vector of lengths as the entries take it: flat, int32, contiguous"""
+    return t.reshape(-1).to(torch.int32).contiguous()

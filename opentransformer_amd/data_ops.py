@@ -1,15 +1,15 @@
 """No-autograd wrappers over the C ABI (include/otrans_hip.h) for what builds batches and language models from data: feature
-preparation and the n-gram estimator's passes.  The rules are those of ops.py: raw data_ptr()s and torch's current stream go to
-libotrans_hip.so, a non-CUDA tensor raises.  ops.py re-exports every public name below; callers write `ops.X`."""
+preparation, the MixSpeech mix and the n-gram estimator's passes.  The rules are those of ops.py: raw data_ptr()s and torch's current
+stream go to libotrans_hip.so, a non-CUDA tensor raises.  ops.py re-exports every public name below; callers write `ops.X`."""
 import ctypes as C
 
 import torch
 
 from . import _lib as L
-from ._runtime import _cuda, _p, _stream, _timed
+from ._runtime import _cuda, _p, _stream, _timed, _len32
 
-__all__ = ['feature_prepare', 'cmvn_accumulate', 'FEATPREP_MAX_RANGES', 'ngram_train_count', 'ngram_train_stats', 'ngram_train_estimate',
-           'NGRAM_TRAIN_ERRORS']
+__all__ = ['feature_prepare', 'cmvn_accumulate', 'FEATPREP_MAX_RANGES', 'mixspeech_mix', 'ngram_train_count', 'ngram_train_stats',
+           'ngram_train_estimate', 'NGRAM_TRAIN_ERRORS']
 
 NGRAM_TRAIN_ERRORS = {1: 'the count table is full', 2: 'an id inside a sentence is outside [1, V) or is the </s> unit',
                       4: 'a sentence length is outside [0, L]', 8: 'a context or a suffix is missing from the count table'}
@@ -135,3 +135,40 @@ def cmvn_accumulate(src, row_off, lengths, acc):
         raise L.OtransHipError('cmvn_accumulate: acc must be a contiguous float64 [%d] tensor' % (2 * F_ + 1))
     L.check(L.load().otr_cmvn_accumulate(_p(src), _p(ro), _p(ln), B, F_, _p(acc), _stream()), 'otr_cmvn_accumulate')
     return acc
+
+
+# ------------------------------------------------------------------ MixSpeech: the mixed half batch (csrc/mixspeech.hip)
+def _lam_check(who, lam):
+    """the mixing weight of MixSpeech as mixspeech_mix and loss_ops.ctc_loss_pair take it"""
+    if not torch.is_tensor(lam) or lam.numel() != 1:
+        raise ValueError('%s: lam must be a 1-element device tensor, got %r' % (who, lam if not torch.is_tensor(lam) else tuple(lam.shape)))
+
+
+def mixspeech_mix(x, lengths, lam):
+    """The mixed half batch of MixSpeech (include/otrans_hip.h otr_mixspeech_mix): x f32 [B, T, F] (unit stride over T and F; the
+    utterance pitch is passed on), lengths [B] (int32 or int64), lam a 1-element f32 DEVICE tensor.  Returns (out f32 [P, T, F],
+    out_lengths int32 [P], out_mask bool [P, T]) with P = B // 2: out[p] = lam * x[2p] + (1 - lam) * x[2p + 1] bit for bit as float32
+    torch forms it on zero-padded input, with the length and mask of the longer utterance.  Frames at or past an utterance's length are
+    not read.  One launch, no host synchronisation, no gradient (the features are data)."""
+    who = 'mixspeech_mix'
+    if x.dim() != 3:
+        raise ValueError('%s: x must be [B, T, F], got %s' % (who, tuple(x.shape)))
+    B, T, F_ = x.shape
+    if B < 2 or T < 1 or F_ < 1:
+        raise ValueError('%s: x [B, T, F] = %s needs B >= 2, T >= 1 and F >= 1' % (who, (B, T, F_)))
+    if lengths.numel() != B:
+        raise ValueError('%s: lengths must hold B = %d entries, got %s' % (who, B, tuple(lengths.shape)))
+    _lam_check(who, lam)
+    _cuda(x, lengths, lam)
+    if x.dtype != torch.float32 or lam.dtype != torch.float32 or lengths.dtype not in (torch.int32, torch.int64):
+        raise L.OtransHipError('%s: x f32, lengths int32 (or int64), lam f32 expected' % who)
+    x = x.detach()
+    if not (x.stride(2) == 1 and x.stride(1) == F_ and x.stride(0) >= T * F_):
+        x = x.contiguous()
+    P = B // 2
+    out = torch.empty((P, T, F_), dtype=torch.float32, device=x.device)
+    out_len = torch.empty((P,), dtype=torch.int32, device=x.device)
+    out_mask = torch.empty((P, T), dtype=torch.bool, device=x.device)
+    L.check(L.load().otr_mixspeech_mix(_p(x), x.stride(0), _p(_len32(lengths)), _p(lam), B, T, F_, _p(out), _p(out_len), _p(out_mask),
+                                       _stream()), 'otr_mixspeech_mix')
+    return out, out_len, out_mask

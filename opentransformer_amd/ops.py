@@ -3382,501 +3382,13 @@ class LookaheadConvFn(torch.autograd.Function):
         return dx, dw.view(ctx.wshape)
 
 
-# ---------------------------------------------------------------------------------------- losses
-class LabelSmoothingLossFn(torch.autograd.Function):
-    """LabelSmoothingLoss.forward (module/loss.py:21-48) + its gradient in the same pass."""
-
-    @staticmethod
-    def forward(ctx, logits, target, smoothing, pad_idx):
-        _cuda(logits, target)
-        V = logits.shape[-1]
-        lg = logits.reshape(-1, V)
-        # the head of a row-padded product (ops.padded_rows: rows of V8 = ceil8(V) floats) is read in place, and the gradient
-        # leaves as the head of a zero-tailed [R, V8] buffer
-        ld = lg.stride(0) if (lg.dim() == 2 and lg.shape[0] > 1 and lg.stride(1) == 1 and lg.dtype == torch.float32) else V
-        if not (V < ld < V + 8 and ld % 8 == 0 and lg.data_ptr() % 16 == 0):
-            lg, ld = lg.contiguous(), V
-        R = lg.shape[0]
-        tg = target.reshape(-1).contiguous()
-        loss = torch.empty((), dtype=torch.float32, device=lg.device)
-        dlogits = torch.empty((R, ld), dtype=torch.float32, device=lg.device) if ctx.needs_input_grad[0] else None
-        scratch = torch.empty((R + 2,), dtype=torch.float32, device=lg.device)
-        L.check(L.load().otr_label_smoothing_loss_ld(_p(lg), ld, _p(tg), R, V, smoothing, pad_idx, _p(loss), _p(dlogits), ld,
-                                                     _p(scratch), _stream()), 'otr_label_smoothing_loss_ld')
-        ctx.save_for_backward(dlogits)
-        ctx.shape, ctx.V = logits.shape, V
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        (dlogits,) = ctx.saved_tensors
-        out = torch.empty_like(dlogits)
-        g = g.contiguous().float()
-        L.check(L.load().otr_scale(_p(dlogits), _p(out), dlogits.numel(), _p(g), 1.0, _stream()), 'otr_scale')
-        if out.shape[1] != ctx.V:
-            out._otr_zero_tail = tuple(out.shape)                  # LinearFn.backward may read it at its full width (_zero_tail_of)
-            out = out[:, :ctx.V]
-        return out.view(ctx.shape), None, None, None
+# ---------------------------------------------------------------------------------------- losses (loss_ops.py)
+_LS_FUSED = True        # label_smoothing_loss reads it here on every call: the switch lives in ops, loss_ops.py keeps no copy
 
 
-class LabelSmoothingLossFusedFn(torch.autograd.Function):
-    """LabelSmoothingLoss.forward + its gradient + the scalar factor of the backward seed in ONE launch (otr_label_smoothing_loss_fused).
-    Semantics: loss = LabelSmoothingLossFn(...), d loss / d logits multiplied by `gscale` (a device scalar; None = 1) -- i.e.
-    ScaleGradFn o LabelSmoothingLossFn.  The kernel writes gscale x d loss / d logits; backward multiplies by the incoming gradient,
-    unless that is the cached unit seed of ops.backward (then the buffer leaves as it is: no launch)."""
-
-    @staticmethod
-    def forward(ctx, logits, ld, target, ldt, Lt, V, smoothing, pad_idx, gscale, ticket):
-        lg = logits.reshape(-1, V)              # a view (label_smoothing_loss checked the strides)
-        R = lg.shape[0]
-        loss = torch.empty((), dtype=torch.float32, device=lg.device)
-        need = ctx.needs_input_grad[0]
-        # the logits' producer takes its output gradient as a 16-bit operand (_Grad16Link: the row-padded output layer): the
-        # gradient is written in that type, one rounding where every other branch gradient of the model already has one
-        g16 = getattr(logits, '_otr_g16', None)
-        ctx.g16 = g16 if (need and g16 is not None and g16.armed and is_half() and ld % 8 == 0) else None
-        ddt = half_dtype() if ctx.g16 is not None else torch.float32
-        dlogits = torch.empty((R, ld), dtype=ddt, device=lg.device) if need else None
-        scratch = torch.empty((R + 2,), dtype=torch.float32, device=lg.device)
-        L.check(L.load().otr_label_smoothing_loss_fused(_p(lg), ld, _p(target), ldt, Lt, R, V, smoothing, pad_idx, _p(gscale), _p(loss),
-                                                        _p(dlogits), _code(ddt), ld, _p(scratch), _p(ticket), _stream()),
-                'otr_label_smoothing_loss_fused')
-        ctx.save_for_backward(dlogits)
-        ctx.shape, ctx.V = logits.shape, V
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        (dlogits,) = ctx.saved_tensors
-        seed = _state.get(('unit_grad', g.device, g.dtype))
-        unit = seed is not None and g.data_ptr() == seed.data_ptr()
-        if ctx.g16 is not None:
-            link = ctx.g16
-            if unit and link.buf is None and _in_backward():
-                link.buf = dlogits                                 # [R, ld] 16-bit, zero behind column V: LinearFn.backward's operand
-                _park(link)
-                return (_zero_placeholder(dlogits.device, ctx.shape),) + (None,) * 9
-            dlogits = dlogits.float()                              # a gradient other than the unit seed: the general (fp32) route
-            unit = False if not unit else unit
-        if unit:
-            out = dlogits                                          # g == 1: the saved buffer IS the gradient
-        else:
-            out = torch.empty_like(dlogits)
-            g = g.contiguous().float()
-            L.check(L.load().otr_scale(_p(dlogits), _p(out), dlogits.numel(), _p(g), 1.0, _stream()), 'otr_scale')
-        if out.shape[1] != ctx.V:
-            out._otr_zero_tail = tuple(out.shape)                  # LinearFn.backward may read it at its full width (_zero_tail_of)
-            out = out[:, :ctx.V]
-        return (out.view(ctx.shape),) + (None,) * 9
-
-
-_LS_FUSED = True
-
-
-def _ls_ticket(device):
-    """the arrival counter of otr_label_smoothing_loss_fused: one zeroed uint32 per device, allocated outside any capture"""
-    t = _state.setdefault('ls_ticket', {}).get(device)
-    if t is None and not torch.cuda.is_current_stream_capturing():
-        t = _state['ls_ticket'][device] = torch.zeros(4, dtype=torch.int32, device=device)
-    return t
-
-
-def label_smoothing_loss(logits, target, smoothing, pad_idx, grad_scale=None):
-    """LabelSmoothingLoss (module/loss.py:21-48) of logits [..., V] against target [...]; with grad_scale (a device scalar, the loss
-    scale) the gradient that flows back into the logits carries that factor (= ops.ScaleGradFn applied to the loss).  One launch where
-    the fused kernel's alignment rules hold (fp32 logits with 16-byte aligned rows -- the row-padded output layer's are -- V <= 8192,
-    <= 8192 rows), the three-kernel form + ScaleGradFn otherwise."""
-    V = logits.shape[-1]
-    lg = logits.reshape(-1, V)
-    ok = (_LS_FUSED and lg.is_cuda and lg.dtype == torch.float32 and lg.dim() == 2 and lg.stride(1) == 1 and V <= 8192 and 0 < lg.shape[0] <= 8192
-          and lg.data_ptr() % 16 == 0 and target.dtype == torch.int64)
-    if ok:
-        ld = lg.stride(0) if lg.shape[0] > 1 else (V + 3) // 4 * 4
-        ok = ld % 4 == 0 and V <= ld < V + 8
-    ticket = _ls_ticket(lg.device) if ok else None
-    if ok and ticket is not None:
-        if target.dim() == 2 and target.stride(1) == 1 and target.stride(0) >= target.shape[1] and target.numel() == lg.shape[0]:
-            tg, ldt, Lt = target, target.stride(0), target.shape[1]
-        else:
-            tg = target.reshape(-1).contiguous()
-            ldt = Lt = tg.numel()
-        if Lt <= 0x7fffffff and tg.numel() == lg.shape[0] and (lg.shape[0] == 1 or lg.shape[0] % Lt == 0):
-            return LabelSmoothingLossFusedFn.apply(logits, ld, tg, ldt, Lt, V, smoothing, pad_idx, grad_scale, ticket)
-    loss = LabelSmoothingLossFn.apply(logits, target, smoothing, pad_idx)
-    return ScaleGradFn.apply(loss, grad_scale) if (grad_scale is not None and loss.requires_grad) else loss
-
-
-class CTCLossFn(torch.autograd.Function):
-    """CTCAssistor.compute_loss (model/ctc.py:50-53): log_softmax + CTC ('mean', zero_infinity)."""
-
-    @staticmethod
-    def forward(ctx, logits, targets, in_len, tgt_len, blank):
-        _cuda(logits, targets, in_len, tgt_len)
-        B, T, V = logits.shape
-        lp = log_softmax(logits)
-        tg = targets.contiguous()
-        il = in_len.to(torch.int32).contiguous()
-        tl = tgt_len.to(torch.int32).contiguous()
-        max_tgt = tg.shape[1]
-        ws = torch.empty((B, T, 2 * max_tgt + 1), dtype=torch.float32, device=logits.device)
-        nll = torch.empty((B,), dtype=torch.float32, device=logits.device)
-        loss = torch.empty((), dtype=torch.float32, device=logits.device)
-        dlogits = torch.empty_like(lp) if ctx.needs_input_grad[0] else None
-        L.check(L.load().otr_ctc_loss(_p(lp), _p(tg), tg.stride(0), _p(il), _p(tl), B, T, V, max_tgt, blank, _p(ws),
-                                      _p(nll), _p(loss), _p(dlogits), _stream()), 'otr_ctc_loss')
-        ctx.save_for_backward(dlogits)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        (dlogits,) = ctx.saved_tensors
-        out = torch.empty_like(dlogits)
-        g = g.contiguous().float()
-        L.check(L.load().otr_scale(_p(dlogits), _p(out), dlogits.numel(), _p(g), 1.0, _stream()), 'otr_scale')
-        return out, None, None, None, None
-
-
-# ------------------------------------------------------------------ MixSpeech (csrc/mixspeech.hip, csrc/ctc.hip)
-CTC_MAX_TGT = 127
-
-
-class CTCLossPairFn(torch.autograd.Function):
-    """The CTC term of MixSpeech (include/otrans_hip.h otr_ctc_loss_pair): ONE log-softmax of the logits, scored against two label sets
-    with the device weights lam and 1 - lam, and one gradient lam * g_a + (1 - lam) * g_b written by the forward call.  Returns
-    (loss, loss_a, loss_b, nll [2, P]); only loss is differentiable.  backward scales the saved gradient by the incoming seed
-    (_saved_logits_grad: the buffer itself for the cached unit seed of ops.backward)."""
-
-    @staticmethod
-    def forward(ctx, logits, targets_a, targets_b, in_len, tgt_len_a, tgt_len_b, lam, blank):
-        P, T, V = logits.shape
-        lp = log_softmax(logits)
-        max_tgt = targets_a.shape[1]
-        dev = logits.device
-        f32 = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)    # noqa: E731
-        ws, nll, loss3 = f32(2, P, T, 2 * max_tgt + 1), f32(2, P), f32(3)
-        dlogits = f32(P * T, V) if ctx.needs_input_grad[0] else None
-        L.check(L.load().otr_ctc_loss_pair(_p(lp), _p(targets_a), targets_a.stride(0), _p(tgt_len_a), _p(targets_b), targets_b.stride(0),
-                                           _p(tgt_len_b), _p(in_len), _p(lam), P, T, V, max_tgt, blank, _p(ws), _p(nll), _p(loss3),
-                                           _p(dlogits), _stream()), 'otr_ctc_loss_pair')
-        ctx.save_for_backward(dlogits)
-        ctx.shape, ctx.V = logits.shape, V
-        loss, loss_a, loss_b = loss3[0], loss3[1], loss3[2]
-        ctx.mark_non_differentiable(loss_a, loss_b, nll)
-        return loss, loss_a, loss_b, nll
-
-    @staticmethod
-    def backward(ctx, g, *_):
-        return _saved_logits_grad(ctx, g), None, None, None, None, None, None, None
-
-
-def _label_rows(who, name, t, P):
-    if t.dim() != 2 or t.shape[0] != P:
-        raise ValueError('%s: %s must be [P, W] = [%d, W], got %s' % (who, name, P, tuple(t.shape)))
-
-
-def ctc_loss_pair(logits, targets_a, targets_b, in_len, tgt_len_a, tgt_len_b, lam, blank=0):
-    """lam * CTC(logits, a) + (1 - lam) * CTC(logits, b) in one call (include/otrans_hip.h otr_ctc_loss_pair), each term what CTCLossFn
-    computes for that label set alone ('mean' over the P utterances of nll / max(L, 1), zero_infinity).  logits f32 [P, T, V];
-    targets_a / targets_b int64 [P, W], W <= 127, unit inner stride -- views with a longer row stride (the even and odd rows of one
-    matrix) are read in place; in_len, tgt_len_a, tgt_len_b [P] (int32 or int64); lam a 1-element f32 DEVICE tensor, never read by the
-    host.  Returns (loss, loss_a, loss_b): loss carries the gradient, loss_a and loss_b are detached device scalars.  One log-softmax,
-    three launches, no host synchronisation: capturable."""
-    who = 'ctc_loss_pair'
-    if logits.dim() != 3:
-        raise ValueError('%s: logits must be [P, T, V], got %s' % (who, tuple(logits.shape)))
-    P, T, V = logits.shape
-    if P < 1 or T < 1 or V < 2:
-        raise ValueError('%s: logits [P, T, V] = %s need P >= 1, T >= 1 and V >= 2' % (who, (P, T, V)))
-    _label_rows(who, 'targets_a', targets_a, P)
-    _label_rows(who, 'targets_b', targets_b, P)
-    if targets_a.shape[1] != targets_b.shape[1]:
-        raise ValueError('%s: the two label sets have widths %d and %d, one padded width expected' % (who, targets_a.shape[1], targets_b.shape[1]))
-    if targets_a.shape[1] > CTC_MAX_TGT:
-        raise ValueError('%s: target width %d > %d not supported' % (who, targets_a.shape[1], CTC_MAX_TGT))
-    for name, t in (('in_len', in_len), ('tgt_len_a', tgt_len_a), ('tgt_len_b', tgt_len_b)):
-        if t.numel() != P:
-            raise ValueError('%s: %s must hold P = %d entries, got %s' % (who, name, P, tuple(t.shape)))
-    if not torch.is_tensor(lam) or lam.numel() != 1:
-        raise ValueError('%s: lam must be a 1-element device tensor, got %r' % (who, lam if not torch.is_tensor(lam) else tuple(lam.shape)))
-    if not 0 <= int(blank) < V:
-        raise ValueError('%s: blank=%r outside [0, V=%d)' % (who, blank, V))
-    _cuda(logits, targets_a, targets_b, in_len, tgt_len_a, tgt_len_b, lam)
-    if (logits.dtype != torch.float32 or targets_a.dtype != torch.int64 or targets_b.dtype != torch.int64 or lam.dtype != torch.float32
-            or any(t.dtype not in (torch.int32, torch.int64) for t in (in_len, tgt_len_a, tgt_len_b))):
-        raise L.OtransHipError('%s: logits f32, targets int64, lengths int32 (or int64), lam f32 expected' % who)
-    W = targets_a.shape[1]
-    rows = [t if (t.stride(1) == 1 and t.stride(0) >= W) or W == 0 else t.contiguous() for t in (targets_a, targets_b)]
-    lens = [t.reshape(-1).to(torch.int32).contiguous() for t in (in_len, tgt_len_a, tgt_len_b)]
-    loss, loss_a, loss_b, _ = CTCLossPairFn.apply(logits, rows[0], rows[1], lens[0], lens[1], lens[2], lam.detach(), int(blank))
-    return loss, loss_a, loss_b
-
-
-def mixspeech_mix(x, lengths, lam):
-    """The mixed half batch of MixSpeech (include/otrans_hip.h otr_mixspeech_mix): x f32 [B, T, F] (unit stride over T and F; the
-    utterance pitch is passed on), lengths [B] (int32 or int64), lam a 1-element f32 DEVICE tensor.  Returns (out f32 [P, T, F],
-    out_lengths int32 [P], out_mask bool [P, T]) with P = B // 2: out[p] = lam * x[2p] + (1 - lam) * x[2p + 1] bit for bit as float32
-    torch forms it on zero-padded input, with the length and mask of the longer utterance.  Frames at or past an utterance's length are
-    not read.  One launch, no host synchronisation, no gradient (the features are data)."""
-    who = 'mixspeech_mix'
-    if x.dim() != 3:
-        raise ValueError('%s: x must be [B, T, F], got %s' % (who, tuple(x.shape)))
-    B, T, F_ = x.shape
-    if B < 2 or T < 1 or F_ < 1:
-        raise ValueError('%s: x [B, T, F] = %s needs B >= 2, T >= 1 and F >= 1' % (who, (B, T, F_)))
-    if lengths.numel() != B:
-        raise ValueError('%s: lengths must hold B = %d entries, got %s' % (who, B, tuple(lengths.shape)))
-    if not torch.is_tensor(lam) or lam.numel() != 1:
-        raise ValueError('%s: lam must be a 1-element device tensor, got %r' % (who, lam if not torch.is_tensor(lam) else tuple(lam.shape)))
-    _cuda(x, lengths, lam)
-    if x.dtype != torch.float32 or lam.dtype != torch.float32 or lengths.dtype not in (torch.int32, torch.int64):
-        raise L.OtransHipError('%s: x f32, lengths int32 (or int64), lam f32 expected' % who)
-    x = x.detach()
-    if not (x.stride(2) == 1 and x.stride(1) == F_ and x.stride(0) >= T * F_):
-        x = x.contiguous()
-    P = B // 2
-    out = torch.empty((P, T, F_), dtype=torch.float32, device=x.device)
-    out_len = torch.empty((P,), dtype=torch.int32, device=x.device)
-    out_mask = torch.empty((P, T), dtype=torch.bool, device=x.device)
-    L.check(L.load().otr_mixspeech_mix(_p(x), x.stride(0), _p(lengths.reshape(-1).to(torch.int32).contiguous()), _p(lam), B, T, F_, _p(out),
-                                       _p(out_len), _p(out_mask), _stream()), 'otr_mixspeech_mix')
-    return out, out_len, out_mask
-
-
-# ------------------------------------------------------------------ minimum word error rate training (csrc/mwer.hip)
-MWER_MAX_NBEST, MWER_MAX_V = 32, 8192
-
-
-def _saved_logits_grad(ctx, g):
-    """backward of a loss whose forward launch wrote d loss / d logits into a saved [R, ldd] buffer (MwerLossFn, DistillLossFn): the
-    buffer itself when g is the cached unit seed of ops.backward, else g times it; at a padded width it leaves as the head of a
-    zero-tailed buffer"""
-    (dlogits,) = ctx.saved_tensors
-    seed = _state.get(('unit_grad', g.device, g.dtype))
-    if seed is not None and g.data_ptr() == seed.data_ptr():
-        out = dlogits                                              # g == 1: the saved buffer IS the gradient
-    else:
-        out = torch.empty_like(dlogits)
-        g = g.contiguous().float()
-        L.check(L.load().otr_scale(_p(dlogits), _p(out), dlogits.numel(), _p(g), 1.0, _stream()), 'otr_scale')
-    if out.shape[1] != ctx.V:
-        out._otr_zero_tail = tuple(out.shape)                      # LinearFn.backward may read it at its full width (_zero_tail_of)
-        out = out[:, :ctx.V]
-    return out.view(ctx.shape)
-
-
-class MwerLossFn(torch.autograd.Function):
-    """The N-best expected number of errors (include/otrans_hip.h otr_mwer_loss) of teacher-forced logits [B*N*max_len, V] (any leading
-    shape) + its gradient in the same call when the logits need one, like LabelSmoothingLossFn.  The head of a row-padded product
-    (ops.padded_rows: rows of V8 = ceil8(V) floats) is read in place and the gradient leaves as the head of a zero-tailed [R, V8]
-    buffer.  `gscale` (a device scalar; None = 1) rides in the written gradient; backward multiplies by the incoming gradient unless
-    that is the cached unit seed of ops.backward.  Returns (loss, seq_logp [B*N], post [B, N], utt_err [B]); only loss is
-    differentiable.  The gradient is fp32: a 16-bit hand-over armed by the logits' Linear (_Grad16Link) is left unused."""
-
-    @staticmethod
-    def forward(ctx, logits, ys_out, n_rows, errors, gscale):
-        V = logits.shape[-1]
-        B, N = errors.shape
-        max_len = ys_out.shape[1]
-        lg = logits.reshape(-1, V)
-        ok = lg.stride(1) == 1 and (lg.shape[0] <= 1 or lg.stride(0) >= V)
-        if not ok:
-            lg = lg.contiguous()
-        ld = lg.stride(0) if lg.shape[0] > 1 else V
-        R = lg.shape[0]
-        need = ctx.needs_input_grad[0]
-        ldd = ld if (V < ld < V + 8 and ld % 8 == 0) else V          # the padded width goes back to LinearFn.backward with a zero tail
-        dev = lg.device
-        f32 = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)    # noqa: E731
-        loss, seq_logp, post, utt_err = f32(), f32(B * N), f32(B, N), f32(B)
-        dlogits = f32(R, ldd) if need else None
-        lib = L.load()
-        nws = lib.otr_mwer_workspace_floats(B, N, max_len)
-        ws = f32(max(nws, 1))
-        L.check(_timed('mwer_loss %dx%dx%dx%d' % (B, N, max_len, V), {'bytes': R * (2 * V + ldd) * 4},
-                       lambda: lib.otr_mwer_loss(_p(lg), ld, _p(ys_out), ys_out.stride(0), _p(n_rows), _p(errors), B, N, max_len, V,
-                                                 _p(gscale), _p(loss), _p(seq_logp), _p(post), _p(utt_err), _p(dlogits), ldd, _p(ws),
-                                                 ws.numel(), _stream())), 'otr_mwer_loss')
-        ctx.save_for_backward(dlogits)
-        ctx.shape, ctx.V = logits.shape, V
-        ctx.mark_non_differentiable(seq_logp, post, utt_err)
-        return loss, seq_logp, post, utt_err
-
-    @staticmethod
-    def backward(ctx, g, *_):
-        return _saved_logits_grad(ctx, g), None, None, None, None
-
-
-def mwer_loss(logits, ys_out, n_rows, errors, grad_scale=None):
-    """Minimum word error rate loss over an n-best list (include/otrans_hip.h otr_mwer_loss).  logits f32 [B*N, max_len, >= V] or
-    [B*N*max_len, V] with unit stride along the vocabulary (a view with a longer row stride is read in place): the teacher-forced
-    decoder output on rescore_pack's ys_in; ys_out int64 [B*N, max_len] and n_rows int32 [B*N] from rescore_pack; errors int32 [B, N]
-    from edit_distance (< 0: the slot is left out).  grad_scale: a device scalar the gradient into the logits is multiplied by (the
-    loss scale), None = 1.  Returns (loss, {'seq_logp' [B, N] (-inf: not live), 'post' [B, N], 'utt_err' [B]}), the dict detached.
-    At most three launches on the current stream, no host synchronisation, the same bits on every run: capturable."""
-    if errors.dim() != 2 or ys_out.dim() != 2 or ys_out.shape[0] != errors.numel() or n_rows.numel() != errors.numel():
-        raise ValueError('mwer_loss: errors must be [B, N], ys_out [B*N, max_len] and n_rows [B*N], got %s, %s and %s'
-                         % (tuple(errors.shape), tuple(ys_out.shape), tuple(n_rows.shape)))
-    B, N = errors.shape
-    V, max_len = logits.shape[-1], ys_out.shape[1]
-    if not 1 <= N <= MWER_MAX_NBEST:
-        raise ValueError('mwer_loss: N=%d hypotheses per utterance must be in [1, %d]' % (N, MWER_MAX_NBEST))
-    if not 1 <= V <= MWER_MAX_V:
-        raise ValueError('mwer_loss: vocabulary V=%d must be in [1, %d]' % (V, MWER_MAX_V))
-    if max_len < 1 or B * N * max_len >= 1 << 30:
-        raise ValueError('mwer_loss: B*N*max_len = %d*%d*%d must be in [1, 2^30)' % (B, N, max_len))
-    if logits.numel() != B * N * max_len * V:
-        raise ValueError('mwer_loss: logits %s do not hold B*N*max_len = %d rows of V = %d' % (tuple(logits.shape), B * N * max_len, V))
-    _cuda(logits, ys_out, n_rows, errors, grad_scale)
-    if (logits.dtype != torch.float32 or ys_out.dtype != torch.int64 or n_rows.dtype != torch.int32 or errors.dtype != torch.int32
-            or ys_out.stride(1) != 1 or ys_out.stride(0) < max_len):
-        raise L.OtransHipError('mwer_loss: logits f32, ys_out int64 (rows contiguous), n_rows int32, errors int32 expected')
-    loss, seq_logp, post, utt_err = MwerLossFn.apply(logits, ys_out, n_rows.contiguous(), errors.contiguous(), grad_scale)
-    return loss, {'seq_logp': seq_logp.view(B, N), 'post': post, 'utt_err': utt_err}
-
-
-# ------------------------------------------------------------------ knowledge distillation (csrc/distill.hip)
-DISTILL_MAX_V, DISTILL_MAX_K = 8192, 128
-
-
-class DistillLossFn(torch.autograd.Function):
-    """The temperature-scaled KL divergence of student logits [B, T, V] from a teacher (include/otrans_hip.h otr_distill_loss): dense
-    (`teacher` [B, T, V]) or sparse (`top_val`, `top_idx` [B, T, K]), + its gradient into the student's logits in the same call when
-    they need one, like MwerLossFn: the head of a row-padded product is read in place, the gradient leaves as the head of a zero-tailed
-    [R, V8] buffer, `gscale` (a device scalar; None = 1) rides in the written gradient, and backward multiplies by the incoming gradient
-    unless that is the cached unit seed of ops.backward.  Returns (loss, row_kl [B, T]); only loss is differentiable, and only with
-    respect to the student.  The gradient is fp32."""
-
-    @staticmethod
-    def forward(ctx, student, teacher, top_val, top_idx, lengths, temperature, gscale):
-        B, T, V = student.shape
-        lg = student.reshape(-1, V)
-        ok = lg.stride(1) == 1 and (lg.shape[0] <= 1 or lg.stride(0) >= V)
-        if not ok:
-            lg = lg.contiguous()
-        ld = lg.stride(0) if lg.shape[0] > 1 else V
-        R = lg.shape[0]
-        need = ctx.needs_input_grad[0]
-        ldd = ld if (V < ld < V + 8 and ld % 8 == 0) else V          # the padded width goes back to LinearFn.backward with a zero tail
-        dev = lg.device
-        f32 = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)    # noqa: E731
-        loss, row_kl = f32(), f32(B, T)
-        dlogits = f32(R, ldd) if need else None
-        K, ld_t, tg = 0, 0, None
-        if teacher is not None:
-            tg = teacher.reshape(-1, V)
-            if not (tg.stride(1) == 1 and (R <= 1 or tg.stride(0) >= V)):
-                tg = tg.contiguous()
-            ld_t = tg.stride(0) if R > 1 else V
-        else:
-            K = top_val.shape[-1]
-            top_val, top_idx = top_val.reshape(-1, K).contiguous(), top_idx.reshape(-1, K).contiguous()
-        lib = L.load()
-        ws = f32(max(lib.otr_distill_workspace_floats(B, T), 4))
-        L.check(_timed('distill_loss %dx%dx%d%s' % (B, T, V, ' K=%d' % K if K else ''),
-                       {'bytes': R * ((V if K else 2 * V) + (ldd if need else 0)) * 4},
-                       lambda: lib.otr_distill_loss(_p(lg), ld, _p(tg), ld_t, _p(top_val), _p(top_idx), K, _p(lengths), B, T, V,
-                                                    float(temperature), _p(gscale), _p(loss), _p(row_kl), _p(dlogits), ldd, _p(ws),
-                                                    ws.numel(), _stream())), 'otr_distill_loss')
-        ctx.save_for_backward(dlogits)
-        ctx.shape, ctx.V = student.shape, V
-        ctx.mark_non_differentiable(row_kl)
-        return loss, row_kl
-
-    @staticmethod
-    def backward(ctx, g, *_):
-        return _saved_logits_grad(ctx, g), None, None, None, None, None, None
-
-
-def _distill_args(who, student, lengths, temperature):
-    """the checks both forms share; returns (B, T, V)"""
-    if student.dim() != 3:
-        raise ValueError('%s: student logits must be [B, T, V], got %s' % (who, tuple(student.shape)))
-    B, T, V = student.shape
-    if not 1 <= V <= DISTILL_MAX_V:
-        raise ValueError('%s: vocabulary V=%d must be in [1, %d]' % (who, V, DISTILL_MAX_V))
-    if T < 1 or B * T >= 1 << 30:
-        raise ValueError('%s: B*T = %d*%d must be in [0, 2^30) with T >= 1' % (who, B, T))
-    if lengths.numel() != B:
-        raise ValueError('%s: lengths must hold B = %d entries, got %s' % (who, B, tuple(lengths.shape)))
-    tau = float(temperature)
-    if not (tau > 0 and tau != float('inf')):
-        raise ValueError('%s: temperature=%r must be finite and > 0' % (who, temperature))
-    return B, T, V
-
-
-def _distill_run(who, student, teacher, top_val, top_idx, lengths, temperature, grad_scale):
-    _cuda(student, teacher, top_val, top_idx, lengths, grad_scale)
-    if student.dtype != torch.float32 or lengths.dtype not in (torch.int32, torch.int64) or (
-            grad_scale is not None and grad_scale.dtype != torch.float32):
-        raise L.OtransHipError('%s: student f32, lengths int32 (or int64), grad_scale f32 expected' % who)
-    B, T = student.shape[:2]
-    if B == 0:
-        return student.new_zeros(()), student.new_zeros((0, T))
-    return DistillLossFn.apply(student, teacher, top_val, top_idx, lengths.to(torch.int32).contiguous(), float(temperature), grad_scale)
-
-
-def distill_loss(student_logits, teacher_logits, lengths, temperature=1.0, grad_scale=None):
-    """Knowledge-distillation loss against a dense teacher (include/otrans_hip.h otr_distill_loss): tau^2 / n_live times the sum over
-    the live rows (b, i < lengths[b]) of KL(softmax(teacher / tau) || softmax(student / tau)).  student_logits f32 [B, T, V] with unit
-    stride along the vocabulary (a view with a longer row stride, such as the head of a row-padded product, is read in place);
-    teacher_logits f32 of the same shape, it takes no gradient; lengths int32 [B] on the device.  grad_scale: a device scalar the
-    gradient into the student's logits is multiplied by (the loss scale), None = 1.  Returns (loss, row_kl [B, T] detached).
-    At most three launches on the current stream, no host synchronisation, the same bits on every run: capturable."""
-    B, T, V = _distill_args('distill_loss', student_logits, lengths, temperature)
-    if tuple(teacher_logits.shape) != (B, T, V):
-        raise ValueError('distill_loss: teacher logits %s do not match the student\'s %s' % (tuple(teacher_logits.shape), (B, T, V)))
-    _cuda(student_logits, teacher_logits)
-    if teacher_logits.dtype != torch.float32:
-        raise L.OtransHipError('distill_loss: teacher logits must be f32, got %s' % teacher_logits.dtype)
-    return _distill_run('distill_loss', student_logits, teacher_logits.detach(), None, None, lengths, temperature, grad_scale)
-
-
-def distill_loss_topk(student_logits, top_val, top_idx, lengths, temperature=1.0, grad_scale=None):
-    """distill_loss against a sparse teacher: top_val f32 / top_idx int32 [B, T, K] (what topk_rows returns; logits or log-probs), K <=
-    DISTILL_MAX_K.  The teacher's distribution of a row is the softmax of its listed values (index in [0, V); the top-K mass is
-    renormalised) and zero elsewhere; a row that lists nothing takes no part.  Indices within a row must be distinct."""
-    B, T, V = _distill_args('distill_loss_topk', student_logits, lengths, temperature)
-    if top_val.dim() != 3 or tuple(top_val.shape[:2]) != (B, T) or top_idx.shape != top_val.shape:
-        raise ValueError('distill_loss_topk: top_val and top_idx must both be [B, T, K] = [%d, %d, K], got %s and %s'
-                         % (B, T, tuple(top_val.shape), tuple(top_idx.shape)))
-    K = top_val.shape[2]
-    if not 1 <= K <= DISTILL_MAX_K:
-        raise ValueError('distill_loss_topk: K=%d entries per row must be in [1, %d]' % (K, DISTILL_MAX_K))
-    _cuda(student_logits, top_val, top_idx)
-    if top_val.dtype != torch.float32 or top_idx.dtype != torch.int32:
-        raise L.OtransHipError('distill_loss_topk: top_val f32 and top_idx int32 expected, got %s and %s' % (top_val.dtype, top_idx.dtype))
-    return _distill_run('distill_loss_topk', student_logits, None, top_val.detach(), top_idx, lengths, temperature, grad_scale)
-
-
-def topk_rows(x, lengths, K):
-    """The K largest entries of every row of x f32 [B, T, V] (include/otrans_hip.h otr_ctc_topk): (val f32 [B, T, K] descending, idx
-    int32 [B, T, K], ties to the lower index).  Rows at or past lengths[b] are left as zeros -- K copies of (0.0, index 0), which is
-    not a legal sparse row (the indices repeat): hand distill_loss_topk the same lengths, so that it never reads them.  The producer
-    of sparse teachers for distill_loss_topk: 2K numbers per frame instead of V.  One launch, no host synchronisation."""
-    if x.dim() != 3:
-        raise ValueError('topk_rows: x must be [B, T, V], got %s' % (tuple(x.shape),))
-    B, T, V = x.shape
-    K = int(K)
-    if not 1 <= V <= DISTILL_MAX_V:
-        raise ValueError('topk_rows: V=%d must be in [1, %d]' % (V, DISTILL_MAX_V))
-    if not 1 <= K <= min(DISTILL_MAX_K, V):
-        raise ValueError('topk_rows: K=%d must be in [1, min(%d, V=%d)]' % (K, DISTILL_MAX_K, V))
-    if T < 1 or lengths.numel() != B:
-        raise ValueError('topk_rows: T=%d must be >= 1 and lengths hold B = %d entries' % (T, B))
-    _cuda(x, lengths)
-    if x.dtype != torch.float32:
-        raise L.OtransHipError('topk_rows: x must be f32, got %s' % x.dtype)
-    x = x.detach()
-    if not (x.stride(2) == 1 and x.stride(1) >= V and x.stride(0) == T * x.stride(1)):
-        x = x.contiguous()
-    val = torch.zeros((B, T, K), dtype=torch.float32, device=x.device)
-    idx = torch.zeros((B, T, K), dtype=torch.int32, device=x.device)
-    if B:
-        L.check(L.load().otr_ctc_topk(_p(x), x.stride(1), _p(lengths.to(torch.int32).contiguous()), B, T, V, K, _p(val), _p(idx),
-                                      _stream()), 'otr_ctc_topk')
-    return val, idx
-
-
-# ops remains the namespace the package, tests, tools and docstrings use: the leaf modules' public names live here too
+# ops remains the namespace the package, tests, tools and docstrings use: the other modules' public names live here too.  loss_ops
+# imports this module back (it needs the autograd core above), so it comes last, when everything it reaches for is defined
 from .decode_ops import *      # noqa: E402,F401,F403
 from .data_ops import *        # noqa: E402,F401,F403
+from .loss_ops import *        # noqa: E402,F401,F403
+from .loss_ops import _ls_ticket      # noqa: E402,F401  (tests/test_gpu_round5.py reads ops._ls_ticket)
