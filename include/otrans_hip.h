@@ -40,7 +40,7 @@ extern "C" {
  * bump; 602: the rescoring entries, additions only; 603: otr_ctc_align, additions only; 604: otr_ngram_lookup and otr_ctc_beam_search_lm, additions only; 605:
  * otr_edit_distance, additions only; 606: otr_ngram_score_cands, otr_ngram_score_seqs and otr_rescore_select_add, additions only; 607: otr_ngram_count, otr_ngram_stats and otr_ngram_estimate, additions only;
  * 608: otr_mwer_workspace_floats and otr_mwer_loss, additions only; still 608: otr_feature_prepare_workspace_bytes, otr_feature_prepare and
- * otr_cmvn_accumulate, after them otr_ctc_segment_workspace_bytes and otr_ctc_segment, and after those otr_distill_workspace_floats and otr_distill_loss (additions only), after those otr_bias_score_cands and otr_bias_score_seqs (additions only), and otr_ctc_beam_search_bias (an addition only), after them otr_edit_align and otr_nbest_consensus (additions only), and last otr_mixspeech_mix and otr_ctc_loss_pair (additions only), were added without a bump -- no existing signature, structure or meaning changed, and a binding that needs them
+ * otr_cmvn_accumulate, after them otr_ctc_segment_workspace_bytes and otr_ctc_segment, and after those otr_distill_workspace_floats and otr_distill_loss (additions only), after those otr_bias_score_cands and otr_bias_score_seqs (additions only), and otr_ctc_beam_search_bias (an addition only), after them otr_edit_align and otr_nbest_consensus (additions only), after them otr_mixspeech_mix and otr_ctc_loss_pair (additions only), and last otr_ctc_mwer_workspace_floats and otr_ctc_mwer_loss (additions only), were added without a bump -- no existing signature, structure or meaning changed, and a binding that needs them
  * fails on the missing symbol of an older library when it loads it).  A binding compares otr_version() with the OTR_ABI_VERSION it was written against BEFORE its first call and refuses a
  * library that answers anything else: descriptors are passed by pointer and read at the library's idea of their size. */
 #define OTR_ABI_VERSION 608
@@ -673,6 +673,51 @@ int32_t otr_ctc_loss_pair(const float* log_probs, const int64_t* targets_a, int6
                           const int64_t* targets_b, int64_t ldt_b, const int32_t* tgt_len_b, const int32_t* in_len, const float* lam,
                           int32_t P, int32_t T, int32_t V, int32_t max_tgt, int32_t blank, float* alpha_ws, float* nll, float* loss3,
                           float* dlogits, void* stream);
+
+/* ---- minimum word error rate training of the CTC model (sequence-discriminative training on the n-best of the CTC prefix beam
+ *      search), csrc/ctc.hip: otr_ctc_loss_pair generalised to N hypotheses per utterance plus, optionally, the reference, with a
+ *      posterior step between the sweeps.  f32 in every build.  B utterances with N hypothesis slots each, slot (b, n).
+ *   log_probs f32 [B, T, V] (already log-softmaxed); in_len int32 [B], clamped to [0, T] as in otr_ctc_loss; hyps int64 tokens, row
+ *   (b, n) at hyps + (b*N + n)*ldh; hyp_len int32 [B, N]; errors int32 [B, N] (otr_edit_distance's dist; < 0: invalid).  ref int64 rows
+ *   of stride ldr with ref_len int32 [B]: the reference labels of the interpolated CTC term, or all three NULL / 0: no CTC term.
+ *   ctc_weight >= 0 and scale > 0 are host floats; gscale a DEVICE f32 scalar (NULL: 1) that rides in the written gradient, as
+ *   otr_mwer_loss's grad_scale does; max_tgt <= 127 bounds hyp_len and ref_len as in otr_ctc_loss; blank is the blank index.
+ *   ll_n = the CTC log-likelihood of hypothesis n, what -otr_ctc_loss's nll is for those labels.
+ *   Slot (b, n) is LIVE iff errors >= 0, hyp_len lies in [0, max_tgt], every label inside hyp_len lies in [0, V) and an alignment
+ *   exists (ll_n > -inf: in_len[b] > 0 and the labels, with a blank between equal neighbours, fit into the frames).  A hypothesis of
+ *   length 0 is valid (one state, all blank).  Nothing behind hyp_len is read, nothing at all of a slot with errors < 0.
+ *   Per utterance: P_n = softmax over the live n of scale * ll_n (max-subtracted), E_b = sum_n P_n W_n with W = errors.
+ *   mwer = (1 / B_live) sum_b E_b, B_live = the number of utterances with at least one live slot; B_live = 0: mwer 0.
+ *   ctc = otr_ctc_loss's value for (ref, ref_len): sum_b nll_ref[b] * coef_b, coef_b = 1 / (B * max(ref_len[b], 1)); 0 without ref.
+ *   c_n = scale * P_n (W_n - E_b).  d E_b / d logits[t, v] = sum_n c_n (gamma_n[t, v] - softmax[t, v]) with gamma_n the occupancy of
+ *   (t, v) under hypothesis n; sum_n c_n is identically zero, so the dense softmax term of the hypotheses cancels and the MWER gradient
+ *   touches only the columns of the hypotheses' labels and of the blank.  A dense term survives only for the reference.
+ * Outputs: loss3 f32 [3] = {mwer + ctc_weight * ctc, mwer, ctc}; seq_logp f32 [B, N] = ll_n, -inf where the slot is not live; post f32
+ *   [B, N] = P, 0 where not live; utt_err f32 [B] = E_b (0 without a live slot); nll_ref f32 [B]: what otr_ctc_loss writes for the
+ *   reference (0 where infeasible or guarded, and 0 throughout without ref).  The sums over the utterances go through one fixed tree,
+ *   no atomics: these outputs have the same bits on every run.
+ *   dlogits f32 [B, T, V] (NULL: forward only) = g * [ctc_weight * ok_ref * coef_b * (softmax - gamma_ref) + sum over the live n of
+ *   (c_n / B_live) * gamma_n], g = *gscale.  EVERY cell is written by the call, no memset is needed: the dense pass writes
+ *   g * ctc_weight * ok_ref * coef_b * exp(lp) on the frames below in_len and exact 0 elsewhere -- it does not read lp where that
+ *   coefficient is 0 -- and the beta sweeps then add -wc * gamma onto the slab, wc = g * ctc_weight * coef_b for the reference and
+ *   -g * c_n / B_live for a live slot.  A slot whose wc is exactly 0 returns before it touches anything: every slot at N = 1, where
+ *   the loss is W and the gradient of the MWER term exactly zero.  The occupancies go on with fp32 atomics in free order, as in
+ *   otr_ctc_loss: the gradient is not bit-reproducible.
+ *   workspace: at least otr_ctc_mwer_workspace_floats(B, N, T, max_tgt) floats = the alpha tables [N + 1, B, T, 2*max_tgt + 1] and the
+ *   weights wc [B, N + 1]; that entry runs on the host and answers -1 for a shape otr_ctc_mwer_loss refuses.
+ * Launches: the alpha sweeps on a grid (B, N + 1) (N without ref), which leave ll; one workgroup over the B * N scalars (post, utt_err,
+ *   loss3, wc); the dense or zero pass, in the chunks of otr_ctc_loss_pair's, 16 bytes per access where an utterance's base is 16-byte
+ *   aligned (log_probs and dlogits judged separately) and scalar otherwise; the beta sweeps on the same grid.  Forward only: the first two.
+ * Refused before any launch (< 0, outputs untouched): a NULL pointer other than ref / ref_len / gscale / dlogits; only some of ref,
+ *   ldr (non-zero) and ref_len given; B outside [1, 65535], N outside [1, 32], T < 1, V < 2; max_tgt outside [0, 127]; ldh or (with
+ *   ref) ldr below max_tgt; blank outside [0, V); ctc_weight < 0 or scale <= 0 or either not finite; a workspace smaller than
+ *   otr_ctc_mwer_workspace_floats answers.  No allocation or host synchronisation: capturable. */
+int64_t otr_ctc_mwer_workspace_floats(int32_t B, int32_t N, int32_t T, int32_t max_tgt);
+int32_t otr_ctc_mwer_loss(const float* log_probs, const int32_t* in_len, const int64_t* hyps, int64_t ldh, const int32_t* hyp_len,
+                          const int32_t* errors, const int64_t* ref, int64_t ldr, const int32_t* ref_len, float ctc_weight, float scale,
+                          const float* gscale, int32_t B, int32_t N, int32_t T, int32_t V, int32_t max_tgt, int32_t blank, float* loss3,
+                          float* seq_logp, float* post, float* utt_err, float* nll_ref, float* dlogits, float* workspace,
+                          int64_t workspace_floats, void* stream);
 
 /* ---- one optimizer update over a replica's FLAT buffers (train/trainer.py:221-234 clip_grad_norm_(5) + gradient noise +
  *      NaN guard + scheduler.step + optimizer.step; train/scheduler.py:129-138 Noam lr; torch Adam with

@@ -11,7 +11,7 @@ from .model import (BuildFrontEnd, BuildEncoder, BuildDecoder, End2EndModel, Spe
                     CTCAssistor)
 from . import evaluate                                   # noqa: F401  (WER / CER scoring on the device: evaluate.evaluate(recognizer, batches))
 from .evaluate import ErrorRateMeter, score_texts        # noqa: F401
-from .mwer import MWERTraining                           # noqa: F401  (minimum word error rate training on the n-best of the beam search)
+from .mwer import MWERTraining, CTCMWERTraining          # noqa: F401  (minimum word error rate training on the n-best of the beam search: attention model, CTC model)
 from .distill import DistillTraining                     # noqa: F401  (knowledge distillation from a teacher of the same class, online or from stored top-K posteriors)
 from .mixspeech import MixSpeechTraining                 # noqa: F401  (MixSpeech: pairs of utterances mixed with one Beta-drawn weight, one encoder pass for both target sets)
 from .bias import PhraseBias                             # noqa: F401  (phrase biasing / hotwords for SpeechToTextRecognizer(bias=...))

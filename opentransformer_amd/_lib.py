@@ -179,6 +179,9 @@ SIGNATURES = {
     'otr_ctc_loss': [_P, _P, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P],
     'otr_mixspeech_mix': [_P, _I64, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P],
     'otr_ctc_loss_pair': [_P, _P, _I64, _P, _P, _I64, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P],
+    'otr_ctc_mwer_workspace_floats': [_I32, _I32, _I32, _I32],
+    'otr_ctc_mwer_loss': [_P, _P, _P, _I64, _P, _P, _P, _I64, _P, _F32, _F32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P,
+                          _P, _I64, _P],
     'otr_ffn_fwd_split_slab': [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P],
     'otr_ffn_bwd_split_slab': [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P],
     'otr_ln_bwd_proj_slabs': [_P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _I32, _F32, C.c_uint64, _P],
@@ -281,7 +284,7 @@ _RESTYPE = {'otr_last_error_string': C.c_char_p, 'otr_dec_ffn_hsave_bytes': C.c_
             'otr_conv2_wide_scratch_bytes': C.c_int64, 'otr_add2_colsum_partial_rows': C.c_int64,
             'otr_ctc_beam_workspace_bytes': C.c_int64, 'otr_ctc_align_workspace_bytes': C.c_int64, 'otr_mwer_workspace_floats': C.c_int64,
             'otr_feature_prepare_workspace_bytes': C.c_int64, 'otr_ctc_segment_workspace_bytes': C.c_int64,
-            'otr_distill_workspace_floats': C.c_int64}
+            'otr_distill_workspace_floats': C.c_int64, 'otr_ctc_mwer_workspace_floats': C.c_int64}
 
 _libs = {}
 _kind = 'bf16'

@@ -332,3 +332,239 @@ extern "C" int32_t otr_ctc_loss_pair(const float* log_probs, const int64_t* targ
                        tgt_len_b, lam, P, T, V, blank, (const float*)alpha_ws, Smax, dlogits);
   return otr_check_launch("ctc_loss_pair");
 }
+
+// ------------------------------------------------------------------------------------------------ the N-best form (MWER for the CTC model)
+// otr_ctc_mwer_loss: ONE [B, T, V] table of log-probabilities scored against N hypotheses per utterance and, optionally, the reference:
+// the pair form with N + 1 label sets and a posterior step between the sweeps (include/otrans_hip.h states the semantics).  Four launches:
+//   1. ctc_mwer_alpha_kernel, grid (B, N or N + 1): the alpha sweep of (utterance, slot) into that slot's alpha table; slot N is the
+//      reference.  It leaves ll in seq_logp (-inf: the slot is dead) and the reference's nll in nll_ref.
+//   2. ctc_mwer_post_kernel, ONE workgroup over the B x N scalars, as mwer_post_kernel: P, E_b, the three losses through one LDS tree
+//      (the same bits on every run) and the weight wc of every (utterance, slot) the beta sweep multiplies its occupancies by.
+//   3. ctc_mwer_dense_kernel, grid (chunks, B): every cell of dlogits is written once.  sum_n c_n = 0 cancels the softmax term of the
+//      hypotheses, so only the reference's survives: wc_ref * exp(lp) on the frames below in_len, and zeros -- lp is not read -- behind
+//      them and wherever wc_ref is 0 (no reference, ctc_weight 0, no alignment).
+//   4. ctc_mwer_beta_kernel, grid (B, N or N + 1): the beta sweep adds -wc * gamma onto the slab; a weight of exactly 0 returns first.
+// As in the pair form the log-likelihood is re-formed from the last alpha row where it is needed; the workspace is the N + 1 alpha
+// tables and the B x (N + 1) weights.
+
+// the sequence of (utterance b, slot k): k < N hypothesis k, k == N the reference
+__device__ __forceinline__ CtcSeq ctc_mwer_seq(const int32_t* in_len, const int32_t* hyp_len, const int32_t* ref_len, int b, int k, int B,
+                                               int N, int T, int Smax) {
+  return k < N ? ctc_seq(in_len + b, hyp_len + (int64_t)b * N + k, 0, B, T, Smax) : ctc_seq(in_len, ref_len, b, B, T, Smax);
+}
+
+__global__ __launch_bounds__(256) void ctc_mwer_alpha_kernel(const float* lp, const int32_t* in_len, const int64_t* hyps, int64_t ldh,
+                                                            const int32_t* hyp_len, const int32_t* errors, const int64_t* ref, int64_t ldr,
+                                                            const int32_t* ref_len, int B, int N, int T, int V, int blank, float* alpha_ws,
+                                                            int Smax, float* seq_logp, float* nll_ref) {
+  __shared__ float sh[2][256];
+  const int b = blockIdx.x, k = blockIdx.y, s = threadIdx.x;
+  const int64_t h = (int64_t)b * N + k;
+  if (k < N && errors[h] < 0) {                               // an invalid pair: nothing of the slot is read
+    if (s == 0) seq_logp[h] = NEG_INF;
+    return;
+  }
+  const CtcSeq q = ctc_mwer_seq(in_len, hyp_len, ref_len, b, k, B, N, T, Smax);
+  const int Tb = q.Tb, S = q.S;
+  const float* lpb = lp + (int64_t)b * T * V;
+  float* aw = alpha_ws + ((int64_t)k * B + b) * T * Smax;
+  const int64_t* tg = k < N ? hyps + h * ldh : ref + (int64_t)b * ldr;
+  const bool live = s < S;
+  const int64_t lab = (live && (s & 1)) ? tg[s >> 1] : (int64_t)blank;
+  // a label outside [0, V): an alpha table of -inf, which every later launch reads as "no alignment" (ctc_pair_alpha_kernel)
+  const bool bad_label = __syncthreads_or(lab < 0 || lab >= V);
+  const int ext = bad_label ? blank : (int)lab;
+  const int ext_m2 = (live && s >= 2 && (s & 1) && !bad_label) ? (int)tg[(s - 2) >> 1] : blank;
+  const bool skip_b = live && s >= 2 && ext != blank && ext != ext_m2;       // s-2 -> s allowed
+  ctc_alpha_sweep(lpb, aw, sh, s, live, S, Tb, V, Smax, blank, ext, skip_b, Tb > 0 && !bad_label);
+  if (s == 0) {
+    float ll = NEG_INF;
+    if (Tb > 0 && !q.bad_len) {
+      const float* fin = sh[(Tb - 1) & 1];
+      ll = lse3(fin[S - 1], S > 1 ? fin[S - 2] : NEG_INF, NEG_INF);
+    }
+    if (k < N) seq_logp[h] = ll;
+    else nll_ref[b] = ll != NEG_INF ? -ll : 0.f;               // zero_infinity=True
+  }
+}
+
+__global__ __launch_bounds__(256) void ctc_mwer_post_kernel(const float* seq_logp, const int32_t* errors, const int32_t* in_len,
+                                                           const int32_t* ref_len, int B, int N, int T, int Smax, float ctc_weight,
+                                                           float scale, const float* gscale, const float* alpha_ws, float* nll_ref,
+                                                           float* loss3, float* post, float* utt_err, float* wc) {
+  __shared__ float s_sum[256], s_ctc[256];
+  __shared__ int s_cnt[256];
+  const int tid = threadIdx.x;
+  const float g = gscale ? *gscale : 1.f;
+  float esum = 0.f, csum = 0.f;
+  int cnt = 0;
+  for (int b = tid; b < B; b += 256) {
+    const float* s = seq_logp + (int64_t)b * N;
+    const int32_t* w = errors + (int64_t)b * N;
+    float* p = post + (int64_t)b * N;
+    float m = NEG_INF;
+    bool any = false;
+    for (int n = 0; n < N; ++n)
+      if (!(s[n] == NEG_INF)) {
+        m = fmaxf(m, scale * s[n]);
+        any = true;
+      }
+    float z = 0.f;
+    for (int n = 0; n < N; ++n)
+      if (!(s[n] == NEG_INF)) z += expf(scale * s[n] - m);
+    float e = 0.f;
+    for (int n = 0; n < N; ++n) {
+      const float pn = !(s[n] == NEG_INF) ? expf(scale * s[n] - m) / z : 0.f;
+      p[n] = pn;
+      if (pn != 0.f) e += pn * (float)w[n];
+    }
+    utt_err[b] = e;
+    if (any) {
+      esum += e;
+      ++cnt;
+    }
+    // the reference: its nll times coef, and the weight of its dense term and of its occupancies
+    float wr = 0.f;
+    if (ref_len) {
+      const CtcSeq q = ctc_seq(in_len, ref_len, b, B, T, Smax);
+      if (ctc_ll_of(alpha_ws + ((int64_t)N * B + b) * T * Smax, q, Smax) != NEG_INF) {
+        csum += nll_ref[b] * q.coef;
+        wr = g * ctc_weight * q.coef;
+      }
+    } else {
+      nll_ref[b] = 0.f;
+    }
+    wc[(int64_t)b * (N + 1) + N] = wr;
+  }
+  s_sum[tid] = esum;
+  s_ctc[tid] = csum;
+  s_cnt[tid] = cnt;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {                 // one tree, the same order on every run
+    if (tid < o) {
+      s_sum[tid] += s_sum[tid + o];
+      s_ctc[tid] += s_ctc[tid + o];
+      s_cnt[tid] += s_cnt[tid + o];
+    }
+    __syncthreads();
+  }
+  const int b_live = s_cnt[0];
+  if (tid == 0) {
+    const float mwer = b_live > 0 ? s_sum[0] / (float)b_live : 0.f;
+    loss3[0] = mwer + ctc_weight * s_ctc[0];
+    loss3[1] = mwer;
+    loss3[2] = s_ctc[0];
+  }
+  for (int b = tid; b < B; b += 256) {                // this thread wrote post and utt_err of these utterances
+    const float e = utt_err[b];
+    for (int n = 0; n < N; ++n) {
+      const int64_t h = (int64_t)b * N + n;
+      const float pn = post[h];                       // wc = -g c_n / B_live: the beta sweep adds -wc * gamma
+      wc[(int64_t)b * (N + 1) + n] = pn != 0.f ? -(g * (scale * pn * ((float)errors[h] - e)) / (float)b_live) : 0.f;
+    }
+  }
+}
+
+// the chunk body is ctc_pair_dense_kernel's, repeated: sharing it as one inline function gives that kernel another register allocation,
+// and the device code of otr_ctc_loss_pair stays what it was
+__global__ __launch_bounds__(256) void ctc_mwer_dense_kernel(const float* lp, const int32_t* in_len, int N, int T, int V, const float* wc,
+                                                            float* dlogits) {
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const float c = wc[(int64_t)b * (N + 1) + N];
+  const int Tb = max(min(in_len[b], T), 0);
+  const int64_t TV = (int64_t)T * V, n = c != 0.f ? (int64_t)Tb * V : 0;
+  const float* x = lp + (int64_t)b * TV;
+  float* y = dlogits + (int64_t)b * TV;
+  const bool xvec = ((uintptr_t)x & 15) == 0, yvec = ((uintptr_t)y & 15) == 0;
+  const int64_t e0 = (int64_t)blockIdx.x * CTC_PAIR_CHUNK;
+#pragma unroll
+  for (int q = 0; q < CTC_PAIR_CHUNK / 1024; ++q) {
+    const int64_t e = e0 + (int64_t)(q * 256 + tid) * 4;
+    if (e >= TV) continue;
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (e < n) {
+      if (xvec && e + 4 <= n) {
+        const uint4 u = ld_global_b128(x + e);
+        v[0] = c * expf(__uint_as_float(u.x)); v[1] = c * expf(__uint_as_float(u.y));
+        v[2] = c * expf(__uint_as_float(u.z)); v[3] = c * expf(__uint_as_float(u.w));
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (e + k < n) v[k] = c * expf(x[e + k]);
+      }
+    }
+    if (yvec && e + 4 <= TV) {
+      st_global_b128(y + e, make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])));
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (e + k < TV) y[e + k] = v[k];
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void ctc_mwer_beta_kernel(const float* lp, const int32_t* in_len, const int64_t* hyps, int64_t ldh,
+                                                           const int32_t* hyp_len, const int64_t* ref, int64_t ldr, const int32_t* ref_len,
+                                                           int B, int N, int T, int V, int blank, const float* alpha_ws, int Smax,
+                                                           const float* wc, float* dlogits) {
+  __shared__ float sh[2][256];
+  const int b = blockIdx.x, k = blockIdx.y, s = threadIdx.x;
+  const float w = wc[(int64_t)b * (N + 1) + k];
+  if (w == 0.f) return;                                       // a dead slot, P_n (W_n - E_b) == 0 (every slot at N = 1), or no CTC term
+  const CtcSeq q = ctc_mwer_seq(in_len, hyp_len, ref_len, b, k, B, N, T, Smax);
+  const float* aw = alpha_ws + ((int64_t)k * B + b) * T * Smax;
+  const float ll = ctc_ll_of(aw, q, Smax);                    // workgroup-uniform; finite: the post step gives a weight to live slots only
+  if (ll == NEG_INF) return;
+  const int Tb = q.Tb, S = q.S;
+  const float* lpb = lp + (int64_t)b * T * V;
+  const int64_t* tg = k < N ? hyps + ((int64_t)b * N + k) * ldh : ref + (int64_t)b * ldr;
+  const bool live = s < S;
+  const int ext = (live && (s & 1)) ? (int)tg[s >> 1] : blank;
+  const int ext_p2 = (s + 2 < S && (s & 1)) ? (int)tg[(s + 2) >> 1] : blank;
+  const bool skip_f = (s + 2 < S) && ext_p2 != blank && ext_p2 != ext;       // s -> s+2 allowed
+  ctc_beta_sweep(lpb, aw, dlogits + (int64_t)b * T * V, sh, s, live, S, Tb, V, Smax, ext, skip_f, ll, w);
+}
+
+static bool ctc_mwer_shape_ok(int64_t B, int64_t N, int64_t T, int64_t max_tgt) {
+  return B >= 1 && B <= 65535 && N >= 1 && N <= 32 && T >= 1 && max_tgt >= 0 && max_tgt <= 127;
+}
+
+extern "C" int64_t otr_ctc_mwer_workspace_floats(int32_t B, int32_t N, int32_t T, int32_t max_tgt) {
+  if (!ctc_mwer_shape_ok(B, N, T, max_tgt)) return -1;
+  return ((int64_t)N + 1) * B * T * (2 * max_tgt + 1) + (int64_t)B * (N + 1);     // the N + 1 alpha tables, then the weights
+}
+
+extern "C" int32_t otr_ctc_mwer_loss(const float* log_probs, const int32_t* in_len, const int64_t* hyps, int64_t ldh, const int32_t* hyp_len,
+                                     const int32_t* errors, const int64_t* ref, int64_t ldr, const int32_t* ref_len, float ctc_weight,
+                                     float scale, const float* gscale, int32_t B, int32_t N, int32_t T, int32_t V, int32_t max_tgt,
+                                     int32_t blank, float* loss3, float* seq_logp, float* post, float* utt_err, float* nll_ref,
+                                     float* dlogits, float* workspace, int64_t workspace_floats, void* stream) {
+  OTR_REQUIRE(log_probs && in_len && hyps && hyp_len && errors && loss3 && seq_logp && post && utt_err && nll_ref && workspace,
+              "ctc_mwer_loss: null pointer");
+  OTR_REQUIRE((ref != nullptr) == (ref_len != nullptr) && (ref || ldr == 0), "ctc_mwer_loss: ref, ldr and ref_len go together (all or none)");
+  OTR_REQUIRE(ctc_mwer_shape_ok(B, N, T, max_tgt) && V >= 2,
+              "ctc_mwer_loss: bad shape B=%d N=%d T=%d V=%d max_tgt=%d (B 1 .. 65535, N 1 .. 32, max_tgt 0 .. 127)", B, N, T, V, max_tgt);
+  OTR_REQUIRE(ldh >= max_tgt && (!ref || ldr >= max_tgt), "ctc_mwer_loss: label row strides %lld, %lld below max_tgt = %d", (long long)ldh,
+              (long long)ldr, max_tgt);
+  OTR_REQUIRE(blank >= 0 && blank < V, "ctc_mwer_loss: blank out of range");
+  OTR_REQUIRE(ctc_weight >= 0.f && ctc_weight < __builtin_huge_valf() && scale > 0.f && scale < __builtin_huge_valf(),
+              "ctc_mwer_loss: ctc_weight=%g must be finite and >= 0, scale=%g finite and > 0", (double)ctc_weight, (double)scale);
+  const int64_t need = otr_ctc_mwer_workspace_floats(B, N, T, max_tgt);
+  OTR_REQUIRE(need >= 0 && workspace_floats >= need, "ctc_mwer_loss: workspace of %lld floats, %lld needed", (long long)workspace_floats,
+              (long long)need);
+  hipStream_t s = (hipStream_t)stream;
+  const int Smax = 2 * max_tgt + 1, K = N + (ref ? 1 : 0);
+  float* wc = workspace + ((int64_t)N + 1) * B * T * Smax;
+  hipLaunchKernelGGL(ctc_mwer_alpha_kernel, dim3(B, K), dim3(256), 0, s, log_probs, in_len, hyps, ldh, hyp_len, errors, ref, ldr, ref_len, B, N,
+                     T, V, blank, workspace, Smax, seq_logp, nll_ref);
+  hipLaunchKernelGGL(ctc_mwer_post_kernel, dim3(1), dim3(256), 0, s, (const float*)seq_logp, errors, in_len, ref_len, B, N, T, Smax, ctc_weight,
+                     scale, gscale, (const float*)workspace, nll_ref, loss3, post, utt_err, wc);
+  if (dlogits) {
+    const int64_t TV = (int64_t)T * V;
+    hipLaunchKernelGGL(ctc_mwer_dense_kernel, dim3((unsigned)((TV + CTC_PAIR_CHUNK - 1) / CTC_PAIR_CHUNK), B), dim3(256), 0, s, log_probs, in_len,
+                       N, T, V, (const float*)wc, dlogits);
+    hipLaunchKernelGGL(ctc_mwer_beta_kernel, dim3(B, K), dim3(256), 0, s, log_probs, in_len, hyps, ldh, hyp_len, ref, ldr, ref_len, B, N, T, V,
+                       blank, (const float*)workspace, Smax, (const float*)wc, dlogits);
+  }
+  return otr_check_launch("ctc_mwer_loss");
+}

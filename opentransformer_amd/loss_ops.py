@@ -1,5 +1,5 @@
 """The loss wrappers over the C ABI (include/otrans_hip.h): label smoothing in its three-kernel and one-launch forms, CTC and its
-MixSpeech pair form, MWER, distillation (dense and top-K) and topk_rows.  The rules are those of ops.py.  ops.py re-exports every
+MixSpeech pair form, MWER (of the attention model and of the CTC model), distillation (dense and top-K) and topk_rows.  The rules are those of ops.py.  ops.py re-exports every
 public name below; callers write `ops.X`.
 
 Unlike decode_ops.py and data_ops.py this is no leaf: the losses need the autograd core (ScaleGradFn, the parked 16-bit hand-over,
@@ -333,6 +333,111 @@ def mwer_loss(logits, ys_out, n_rows, errors, grad_scale=None):
         raise L.OtransHipError('mwer_loss: logits f32, ys_out int64 (rows contiguous), n_rows int32, errors int32 expected')
     loss, seq_logp, post, utt_err = MwerLossFn.apply(logits, ys_out, n_rows.contiguous(), errors.contiguous(), grad_scale)
     return loss, {'seq_logp': seq_logp.view(B, N), 'post': post, 'utt_err': utt_err}
+
+
+# ------------------------------------------------------------------ MWER training of the CTC model (csrc/ctc.hip)
+class CtcMwerLossFn(torch.autograd.Function):
+    """The N-best expected number of errors of a CTC head (include/otrans_hip.h otr_ctc_mwer_loss), with the interpolated CTC loss on
+    the reference where one is given: ONE log-softmax of the logits, scored against N hypotheses per utterance (+ the reference), and
+    one gradient written by the forward call when the logits need one.  `gscale` (a device scalar; None = 1) rides in the written
+    gradient.  Returns (loss, mwer, ctc, seq_logp [B, N], post [B, N], utt_err [B]); only loss is differentiable.  backward scales
+    the saved gradient by the incoming seed (_saved_logits_grad: the buffer itself for the cached unit seed of ops.backward)."""
+
+    @staticmethod
+    def forward(ctx, logits, in_len, hyps, hyp_len, errors, ref, ref_len, ctc_weight, scale, blank, gscale, max_tgt):
+        B, T, V = logits.shape
+        N = errors.shape[1]
+        lp = log_softmax(logits)
+        f32 = _f32(logits.device)
+        loss3, seq_logp, post, utt_err, nll_ref = f32(3), f32(B, N), f32(B, N), f32(B), f32(B)
+        need = ctx.needs_input_grad[0]
+        dlogits = f32(B * T, V) if need else None
+        lib = L.load()
+        ws = f32(max(lib.otr_ctc_mwer_workspace_floats(B, N, T, max_tgt), 1))
+        L.check(_timed('ctc_mwer_loss %dx%dx%dx%d' % (B, N, T, V), {'bytes': B * T * (V * (2 if need else 1) + (N + 1) * (2 * max_tgt + 1)) * 4},
+                       lambda: lib.otr_ctc_mwer_loss(_p(lp), _p(in_len), _p(hyps), hyps.stride(1), _p(hyp_len), _p(errors), _p(ref),
+                                                     ref.stride(0) if ref is not None else 0, _p(ref_len), ctc_weight, scale, _p(gscale),
+                                                     B, N, T, V, max_tgt, blank, _p(loss3), _p(seq_logp), _p(post), _p(utt_err),
+                                                     _p(nll_ref), _p(dlogits), _p(ws), ws.numel(), _stream())), 'otr_ctc_mwer_loss')
+        ctx.save_for_backward(dlogits)
+        ctx.shape, ctx.V = logits.shape, V
+        loss, mwer, ctc = loss3[0], loss3[1], loss3[2]
+        ctx.mark_non_differentiable(mwer, ctc, seq_logp, post, utt_err)
+        return loss, mwer, ctc, seq_logp, post, utt_err
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        return (_saved_logits_grad(ctx, g),) + (None,) * 11
+
+
+def _label_width(t, width):
+    """t [..., W] as the entry reads it: unit inner stride, at least `width` labels per row (padded with -1, which no length reaches:
+    a label the kernel would refuse) and at most `width` of them looked at"""
+    if t.shape[-1] < width:
+        t = torch.nn.functional.pad(t, (0, width - t.shape[-1]), value=-1)
+    return t if t.stride(-1) == 1 else t.contiguous()
+
+
+def ctc_mwer_loss(logits, in_len, hyps, hyp_len, errors, ref=None, ref_len=None, ctc_weight=0.0, scale=1.0, blank=0, grad_scale=None):
+    """Minimum word error rate loss of a CTC head over an n-best list, mwer + ctc_weight * CTC(ref), in one call (include/otrans_hip.h
+    otr_ctc_mwer_loss).  logits f32 [B, T, V] (the head's raw output: ONE log-softmax is taken here); in_len [B] frames per utterance;
+    hyps int64 [B, N, L] tokens with unit stride along L (what ops.ctc_prefix_beam_search returns; a view whose rows are evenly strided
+    is read in place), hyp_len [B, N], errors int32 [B, N] from ops.edit_distance (< 0: the slot is left out).  A slot also takes no
+    part if its length is outside [0, min(L, 127)], a label inside its length is outside [0, V), or the labels do not fit into the
+    frames; nothing behind a length is read.  ref int64 [B, W] (W <= 127) and ref_len [B]: the reference labels of the interpolated
+    CTC term ('mean' over the B utterances of nll / max(L, 1), zero_infinity: what CTCLossFn computes), both or neither.  P_n =
+    softmax_n(scale * ll_n) over the live slots.  grad_scale: a device scalar the gradient into the logits is multiplied by (the loss
+    scale), None = 1.  Returns (loss, {'mwer', 'ctc' (scalars), 'seq_logp' [B, N] (-inf: not live), 'post' [B, N], 'utt_err' [B]}),
+    the dict detached.  Four launches behind the log-softmax (two without a gradient), no host synchronisation: capturable.  The
+    scalars and the dict have the same bits on every run; the gradient's occupancies are added with atomics, as CTCLossFn's."""
+    who = 'ctc_mwer_loss'
+    if logits.dim() != 3:
+        raise ValueError('%s: logits must be [B, T, V], got %s' % (who, tuple(logits.shape)))
+    B, T, V = logits.shape
+    if not 1 <= B <= 65535 or T < 1 or V < 2:
+        raise ValueError('%s: logits [B, T, V] = %s need 1 <= B <= 65535, T >= 1 and V >= 2' % (who, (B, T, V)))
+    if hyps.dim() != 3 or hyps.shape[0] != B or errors.dim() != 2 or tuple(errors.shape) != tuple(hyps.shape[:2]) or hyp_len.numel() != errors.numel():
+        raise ValueError('%s: hyps must be [B, N, L] = [%d, N, L], hyp_len and errors [B, N], got %s, %s and %s'
+                         % (who, B, tuple(hyps.shape), tuple(hyp_len.shape), tuple(errors.shape)))
+    N, Lh = hyps.shape[1], hyps.shape[2]
+    if not 1 <= N <= MWER_MAX_NBEST:
+        raise ValueError('%s: N=%d hypotheses per utterance must be in [1, %d]' % (who, N, MWER_MAX_NBEST))
+    if in_len.numel() != B:
+        raise ValueError('%s: in_len must hold B = %d entries, got %s' % (who, B, tuple(in_len.shape)))
+    if (ref is None) != (ref_len is None):
+        raise ValueError('%s: ref and ref_len go together (both or neither)' % who)
+    if ref is not None:
+        _label_rows(who, 'ref', ref, B)
+        if ref.shape[1] > CTC_MAX_TGT:
+            raise ValueError('%s: reference width %d > %d not supported' % (who, ref.shape[1], CTC_MAX_TGT))
+        if ref_len.numel() != B:
+            raise ValueError('%s: ref_len must hold B = %d entries, got %s' % (who, B, tuple(ref_len.shape)))
+    ctc_weight, scale = float(ctc_weight), float(scale)
+    if not 0 <= ctc_weight < float('inf'):
+        raise ValueError('%s: ctc_weight=%r must be finite and >= 0' % (who, ctc_weight))
+    if not 0 < scale < float('inf'):
+        raise ValueError('%s: scale=%r must be finite and > 0' % (who, scale))
+    if not 0 <= int(blank) < V:
+        raise ValueError('%s: blank=%r outside [0, V=%d)' % (who, blank, V))
+    _cuda(logits, in_len, hyps, hyp_len, errors, ref, ref_len, grad_scale)
+    if (logits.dtype != torch.float32 or hyps.dtype != torch.int64 or errors.dtype != torch.int32 or (ref is not None and ref.dtype != torch.int64)
+            or any(t is not None and t.dtype not in (torch.int32, torch.int64) for t in (in_len, hyp_len, ref_len))
+            or (grad_scale is not None and grad_scale.dtype != torch.float32)):
+        raise L.OtransHipError('%s: logits f32, hyps and ref int64, errors int32, lengths int32 (or int64), grad_scale f32 expected' % who)
+    # one bound for both label sets.  L is narrowed to 127 whatever the lengths are: a hypothesis longer than that is left to the kernel,
+    # which counts its slot as dead (no host read of hyp_len)
+    max_tgt = min(max(Lh, ref.shape[1] if ref is not None else 0), CTC_MAX_TGT)
+    hyps = _label_width(hyps, max(max_tgt, 1))
+    if hyps.stride(0) != N * hyps.stride(1) or hyps.stride(1) < max_tgt:       # row (b, n) is read at (b * N + n) * stride(1)
+        hyps = hyps.contiguous()
+    if ref is not None:
+        ref = _label_width(ref, max(max_tgt, 1))
+        if ref.stride(0) < max_tgt:
+            ref = ref.contiguous()
+    out = CtcMwerLossFn.apply(logits, _len32(in_len), hyps, _len32(hyp_len), errors.contiguous(), ref,
+                              _len32(ref_len) if ref_len is not None else None, ctc_weight, scale, int(blank), grad_scale, max_tgt)
+    loss, mwer, ctc, seq_logp, post, utt_err = out
+    return loss, {'mwer': mwer, 'ctc': ctc, 'seq_logp': seq_logp, 'post': post, 'utt_err': utt_err}
 
 
 # ------------------------------------------------------------------ knowledge distillation (csrc/distill.hip)
