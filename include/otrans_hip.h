@@ -1466,6 +1466,65 @@ int32_t otr_dec_self_bwd(const otr_dec_lnb_t* ln, int32_t B, int32_t L, const vo
                          const void* qkv16, const void* ctx16, const float* lse, void* dqkv16, void* slabs, void* stream);
 int32_t otr_dec_sum(const float* skip, const void* slabs, int32_t nslab, int64_t R, float* out, void* stream);
 
+/* ---- the transducer (RNN-T): joint, lattice loss, greedy decoding (csrc/rnnt.hip).  f32 in both builds; blank is an index of the
+ *      vocabulary (the models use 0).  U1 = U + 1 lattice columns, at most OTR_RNNT_MAX_TGT + 1 = 256 (one thread per column, four
+ *      wavefronts); B, T <= 65535 and B * T * U1 < 2^31 rows; every element offset is 64-bit (rows * V passes 2^32 bytes early).
+ *      enc_len / tgt_len int32 [B]: T_b frames and U_b labels of utterance b.
+ * otr_rnnt_joint_fwd: z[b,t,u,:] = tanh(pe[b,t,:] + pg[b,u,:]) for t < T_b, u <= U_b (lengths clamped to [0, T] / [0, U1]) and exact
+ *      zeros elsewhere, where pe / pg are not read.  pe f32 [B,T,J], pg f32 [B,U1,J], z f32 [B,T,U1,J], z16 its 16-bit twin (the
+ *      build's type) or NULL; J a multiple of 4, the four buffers 16-byte aligned.
+ * otr_rnnt_joint_bwd: dpe[b,t,:] = sum_u dz (1 - z^2), dpg[b,u,:] = sum_t dz (1 - z^2) over the same live positions; dz outside them
+ *      is not read (NaN there is harmless), dpe / dpg rows outside the lengths are zeros.  Two launches, each reads dz and z once,
+ *      16 bytes per lane along J; the partial sums meet in a fixed order: the same bits on every run.
+ * otr_rnnt_loss: logits f32, row (b,t,u) at logits + ((b*T + t)*U1 + u) * ld, ld >= V, RAW (one log-softmax is taken here): lp.
+ *      labels int64, y_1..y_U of utterance b at labels + b*ldl (ldl >= U1 - 1; a strided view is read in place).
+ *        alpha(0,0) = 0; alpha(t,u) = logaddexp(alpha(t-1,u) + lp[t-1,u,blank], alpha(t,u-1) + lp[t,u-1,y_u]);
+ *        beta(T_b-1,U_b) = lp[T_b-1,U_b,blank]; beta(t,u) = logaddexp(beta(t+1,u) + lp[t,u,blank], beta(t,u+1) + lp[t,u,y_{u+1}]);
+ *        nll[b] = -(alpha(T_b-1,U_b) + lp[T_b-1,U_b,blank]); loss = (1/B) sum_b nll[b].
+ *      An utterance is GUARDED (nll 0, valid 0, zero gradient, still counted in 1/B) when T_b <= 0, T_b > T, U_b < 0, U_b >= U1,
+ *      U_b > OTR_RNNT_MAX_TGT, or a label inside U_b lies outside [0, V) or equals blank; the guard is taken on the device and no
+ *      label is an index before it was range-checked.  Labels are read only where the lengths are in range.
+ *      dlogits (NULL: forward only), row stride ldd >= V, EVERY cell written: with p = softmax and s = *grad_scale / B (NULL: 1 / B)
+ *        s * [ p_v exp(alpha + beta - lnP) - [v == blank] exp(alpha + lp_blank + beta(t+1,u) - lnP)
+ *                                          - [v == y_{u+1}] exp(alpha + lp_label + beta(t,u+1) - lnP) ]   (beta(T_b,U_b) := 0)
+ *      on live rows of valid utterances, exact zeros on every other row and behind column V; rows that are not live are not read.
+ *      workspace: otr_rnnt_workspace_floats(B, T, U1) = 5 * B*T*U1 + 2 * B floats (lse, lp_blank, lp_label, alpha, beta; per utterance
+ *      the shifted ln P and the shift c), -1 for a refused shape.  The sweeps run on lp + c, c = minus the mean of lp_blank over up to
+ *      256 evenly spaced live cells: alpha + (t + u) c and beta + (T_b + U_b - t - u) c stay small numbers where the plain ones grow
+ *      like (t + u) |lp|, whose float32 ulp would otherwise sit in every exponent of the gradient; nll is shifted back.
+ *      Launches: a wave per live row (logsumexp, 16-byte loads behind the row's own alignment peel); 2B workgroups (alpha and beta of
+ *      every utterance, a barrier per anti-diagonal); one workgroup for the mean; a wave per row of dlogits.  No atomics: the same
+ *      bits on every run.  No allocation or host synchronisation: capturable.  Refused before any launch: a shape outside the limits
+ *      above, V < 2, ld or ldd < V, ldl < U1 - 1, blank outside [0, V), a NULL pointer other than grad_scale / dlogits (labels
+ *      may be NULL at U1 = 1), a workspace that is too small.
+ * otr_rnnt_greedy_joint: one decode step's joint input z[b,:] = tanh(pe[b, t[b], :] + pg_cur[b,:]) with its 16-bit twin; a row that is
+ *      done (t[b] >= T_b or n[b] >= max_len) gets zeros.
+ * otr_rnnt_greedy_advance: one decode step's tail on logits [B, V] (row stride ld).  A row that is done is left alone (emit 0).
+ *      Otherwise k = arg-max (lowest index on ties), lp = log-softmax of the row.  If k != blank and count[b] < max_symbols the row
+ *      EMITS: tokens[b, n[b]] = k, frames[b, n[b]] = t[b], score[b] += lp[k], n[b]++, count[b]++, emit[b] = 1, step_tok[b] = k.  Else
+ *      t[b]++, count[b] = 0, score[b] += lp[blank], emit[b] = 0, step_tok[b] = blank.  *remaining loses 1 when the row becomes done
+ *      (t[b] == T_b or n[b] == max_len): initialise it with the number of rows that start not done.  tokens int64 / frames int32
+ *      are [B, max_len].
+ * otr_rnnt_greedy_commit: for every item k < n_items (at most 16) and every row b with emit[b] != 0, copy row b (row_bytes[k] bytes,
+ *      a multiple of 4) of src[k] over row b of dst[k]: the candidate predictor state becomes the committed one.  src / dst /
+ *      row_bytes are HOST arrays of device pointers / sizes. */
+#define OTR_RNNT_MAX_TGT 255
+int32_t otr_rnnt_joint_fwd(const float* pe, const float* pg, const int32_t* enc_len, const int32_t* tgt_len, int32_t B, int32_t T, int32_t U1,
+                           int32_t J, float* z, void* z16, void* stream);
+int32_t otr_rnnt_joint_bwd(const float* dz, const float* z, const int32_t* enc_len, const int32_t* tgt_len, int32_t B, int32_t T, int32_t U1,
+                           int32_t J, float* dpe, float* dpg, void* stream);
+int64_t otr_rnnt_workspace_floats(int32_t B, int32_t T, int32_t U1);
+int32_t otr_rnnt_loss(const float* logits, int64_t ld, const int64_t* labels, int64_t ldl, const int32_t* enc_len, const int32_t* tgt_len,
+                      int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank, const float* grad_scale, float* loss, float* nll,
+                      int32_t* valid, float* dlogits, int64_t ldd, float* workspace, int64_t workspace_floats, void* stream);
+int32_t otr_rnnt_greedy_joint(const float* pe, const float* pg_cur, const int32_t* t, const int32_t* n, const int32_t* enc_len, int32_t B,
+                              int32_t T, int32_t J, int32_t max_len, float* z, void* z16, void* stream);
+int32_t otr_rnnt_greedy_advance(const float* logits, int64_t ld, const int32_t* enc_len, int32_t B, int32_t T, int32_t V, int32_t blank,
+                                int32_t max_symbols, int32_t max_len, int32_t* t, int32_t* n, int32_t* count, int64_t* tokens,
+                                int32_t* frames, float* score, int32_t* emit, int64_t* step_tok, int32_t* remaining, void* stream);
+int32_t otr_rnnt_greedy_commit(const int32_t* emit, const void* const* src, void* const* dst, const int32_t* row_bytes, int32_t n_items,
+                               int32_t B, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

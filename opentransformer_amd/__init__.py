@@ -14,6 +14,7 @@ from .evaluate import ErrorRateMeter, score_texts        # noqa: F401
 from .mwer import MWERTraining, CTCMWERTraining          # noqa: F401  (minimum word error rate training on the n-best of the beam search: attention model, CTC model)
 from .distill import DistillTraining                     # noqa: F401  (knowledge distillation from a teacher of the same class, online or from stored top-K posteriors)
 from .mixspeech import MixSpeechTraining                 # noqa: F401  (MixSpeech: pairs of utterances mixed with one Beta-drawn weight, one encoder pass for both target sets)
+from .transducer import TransducerModel, TransducerRecognizer   # noqa: F401  (the transducer: LSTM predictor + joint on the lattice loss, greedy decoding; End2EndModel['transducer'])
 from .bias import PhraseBias                             # noqa: F401  (phrase biasing / hotwords for SpeechToTextRecognizer(bias=...))
 from .segment import CTCSegmenter                        # noqa: F401  (CTC segmentation of long recordings against their transcript)
 from .nn import (ConvFrontEnd, ConformerEncoder, ConformerEncoderBlock, ConformerConvolutionModule,   # noqa: F401

@@ -277,6 +277,13 @@ SIGNATURES = {
     'otr_bn_swish_bwd': [_P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P],
     'otr_bn_swish_bwd_sums': [_P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P],
     'otr_conformer_conv_bwd_mid': [_P] * 13 + [_I32] * 7 + [_P],
+    'otr_rnnt_joint_fwd': [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P],
+    'otr_rnnt_joint_bwd': [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P],
+    'otr_rnnt_workspace_floats': [_I32, _I32, _I32],
+    'otr_rnnt_loss': [_P, _I64, _P, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P, _I64, _P],
+    'otr_rnnt_greedy_joint': [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P],
+    'otr_rnnt_greedy_advance': [_P, _I64, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    'otr_rnnt_greedy_commit': [_P, _P, _P, _P, _I32, _I32, _P],
 }
 _RESTYPE = {'otr_last_error_string': C.c_char_p, 'otr_dec_ffn_hsave_bytes': C.c_int64, 'otr_ffn_split_scratch_bytes': C.c_int64, 'otr_ffn_split_sync_ints': C.c_int64, 'otr_ffn_split_hsave_bytes': C.c_int64,
             'otr_ffn_split_padded_rows': C.c_int64, 'otr_add_layernorm_bwd_partial_rows': C.c_int64,
@@ -284,7 +291,8 @@ _RESTYPE = {'otr_last_error_string': C.c_char_p, 'otr_dec_ffn_hsave_bytes': C.c_
             'otr_conv2_wide_scratch_bytes': C.c_int64, 'otr_add2_colsum_partial_rows': C.c_int64,
             'otr_ctc_beam_workspace_bytes': C.c_int64, 'otr_ctc_align_workspace_bytes': C.c_int64, 'otr_mwer_workspace_floats': C.c_int64,
             'otr_feature_prepare_workspace_bytes': C.c_int64, 'otr_ctc_segment_workspace_bytes': C.c_int64,
-            'otr_distill_workspace_floats': C.c_int64, 'otr_ctc_mwer_workspace_floats': C.c_int64}
+            'otr_distill_workspace_floats': C.c_int64, 'otr_ctc_mwer_workspace_floats': C.c_int64,
+            'otr_rnnt_workspace_floats': C.c_int64}
 
 _libs = {}
 _kind = 'bf16'

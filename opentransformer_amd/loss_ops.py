@@ -1,11 +1,13 @@
 """The loss wrappers over the C ABI (include/otrans_hip.h): label smoothing in its three-kernel and one-launch forms, CTC and its
-MixSpeech pair form, MWER (of the attention model and of the CTC model), distillation (dense and top-K) and topk_rows.  The rules are those of ops.py.  ops.py re-exports every
+MixSpeech pair form, MWER (of the attention model and of the CTC model), the transducer (joint, loss, greedy loop), distillation (dense and top-K) and topk_rows.  The rules are those of ops.py.  ops.py re-exports every
 public name below; callers write `ops.X`.
 
 Unlike decode_ops.py and data_ops.py this is no leaf: the losses need the autograd core (ScaleGradFn, the parked 16-bit hand-over,
 the compute mode), which they reach at call time as `_ops.X`.  So this module is not to be imported before `ops`: the package
 always imports `ops` first, and `ops.py` ends by importing this one.  The switch `_LS_FUSED` is owned by `ops`
 (`ops._LS_FUSED`, OTR_SWITCHES=ops._LS_FUSED=0) and read there on every call; there is no copy of it here."""
+import ctypes as C
+
 import torch
 
 from . import ops as _ops
@@ -438,6 +440,211 @@ def ctc_mwer_loss(logits, in_len, hyps, hyp_len, errors, ref=None, ref_len=None,
                               _len32(ref_len) if ref_len is not None else None, ctc_weight, scale, int(blank), grad_scale, max_tgt)
     loss, mwer, ctc, seq_logp, post, utt_err = out
     return loss, {'mwer': mwer, 'ctc': ctc, 'seq_logp': seq_logp, 'post': post, 'utt_err': utt_err}
+
+
+# ------------------------------------------------------------------ the transducer (csrc/rnnt.hip)
+RNNT_MAX_TGT = 255          # include/otrans_hip.h OTR_RNNT_MAX_TGT: at most 256 lattice columns
+
+
+def _rnnt_int_vector(who, name, t, B):
+    if not torch.is_tensor(t) or t.dtype not in (torch.int32, torch.int64):
+        raise ValueError('%s: %s must be an int32 or int64 tensor, got %s' % (who, name, getattr(t, 'dtype', type(t).__name__)))
+    if t.numel() != B:
+        raise ValueError('%s: %s must hold B = %d entries, got %s' % (who, name, B, tuple(t.shape)))
+
+
+class RnntLossFn(torch.autograd.Function):
+    """The transducer loss (include/otrans_hip.h otr_rnnt_loss) of the joint's RAW logits [B, T, U1, V]: one log-softmax, the alpha and
+    beta sweeps and, when the logits need one, the gradient, all written by the forward call.  The head of a row-padded product is
+    read in place and the gradient leaves as the head of a zero-tailed buffer, as in MwerLossFn.  `gscale` (a device scalar; None = 1)
+    rides in the written gradient.  Returns (loss, nll [B], valid int32 [B]); only loss is differentiable.  backward scales the saved
+    gradient by the incoming seed (_saved_logits_grad: the buffer itself for the cached unit seed of ops.backward)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, enc_len, tgt_len, blank, gscale):
+        B, T, U1, V = logits.shape
+        lg, ld = _rows_in_place(logits, V)
+        R, ldd = lg.shape[0], _grad_width(ld, V)
+        f32 = _f32(lg.device)
+        loss, nll = f32(), f32(B)
+        valid = torch.empty((B,), dtype=torch.int32, device=lg.device)
+        need = ctx.needs_input_grad[0]
+        dlogits = f32(R, ldd) if need else None
+        lib = L.load()
+        ws = f32(max(lib.otr_rnnt_workspace_floats(B, T, U1), 1))
+        L.check(_timed('rnnt_loss %dx%dx%dx%d' % (B, T, U1, V), {'bytes': R * (V + (V + ldd if need else 0)) * 4},
+                       lambda: lib.otr_rnnt_loss(_p(lg), ld, _p(labels), labels.stride(0) if U1 > 1 else 0, _p(enc_len), _p(tgt_len), B, T, U1,
+                                                 V, blank, _p(gscale), _p(loss), _p(nll), _p(valid), _p(dlogits), ldd, _p(ws), ws.numel(),
+                                                 _stream())), 'otr_rnnt_loss')
+        ctx.save_for_backward(dlogits)
+        ctx.shape, ctx.V = logits.shape, V
+        ctx.mark_non_differentiable(nll, valid)
+        return loss, nll, valid
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        return _saved_logits_grad(ctx, g), None, None, None, None, None
+
+
+def rnnt_loss(logits, enc_len, labels, tgt_len, blank=0, grad_scale=None):
+    """The transducer (RNN-T) loss in one call (include/otrans_hip.h otr_rnnt_loss): (1 / B) sum_b -ln P(y_b | x_b) over the lattice of
+    the joint's logits.  logits f32 [B, T, U + 1, V] RAW (one log-softmax is taken here), unit stride along V (the head of a row-padded
+    product is read in place); enc_len [B] frames and tgt_len [B] labels per utterance (int32 or int64); labels int64 [B, >= U] with
+    unit inner stride: y_1 .. y_U, a view such as truth[:, 1:-1] is read in place.  U + 1 <= RNNT_MAX_TGT + 1 = 256.  An utterance
+    with a length out of range or a label outside [0, V) or equal to blank is guarded on the device: nll 0, valid 0, zero gradient,
+    still counted in 1 / B.  grad_scale: a device scalar the gradient into the logits is multiplied by (the loss scale), None = 1.
+    Returns (loss, {'nll' [B], 'valid' int32 [B]}), the dict detached.  Four launches (three without a gradient), no atomics, no host
+    synchronisation: the same bits on every run, capturable."""
+    who = 'rnnt_loss'
+    if logits.dim() != 4:
+        raise ValueError('%s: logits must be [B, T, U + 1, V], got %s' % (who, tuple(logits.shape)))
+    B, T, U1, V = logits.shape
+    if not 1 <= B <= 65535 or not 1 <= T <= 65535 or U1 < 1 or V < 2:
+        raise ValueError('%s: logits [B, T, U + 1, V] = %s need 1 <= B, T <= 65535, U + 1 >= 1 and V >= 2' % (who, (B, T, U1, V)))
+    if U1 > RNNT_MAX_TGT + 1:
+        raise ValueError('%s: U + 1 = %d lattice columns > %d not supported' % (who, U1, RNNT_MAX_TGT + 1))
+    if B * T * U1 >= (1 << 31) - 4:
+        raise ValueError('%s: B*T*(U + 1) = %d*%d*%d rows must stay below 2^31' % (who, B, T, U1))
+    if not torch.is_tensor(labels) or labels.dim() != 2 or labels.shape[0] != B or labels.shape[1] < U1 - 1:
+        raise ValueError('%s: labels must be [B, >= U] = [%d, >= %d], got %s' % (who, B, U1 - 1, tuple(getattr(labels, 'shape', ()))))
+    if labels.dtype != torch.int64:
+        raise ValueError('%s: labels must be int64, got %s' % (who, labels.dtype))
+    _rnnt_int_vector(who, 'enc_len', enc_len, B)
+    _rnnt_int_vector(who, 'tgt_len', tgt_len, B)
+    if not 0 <= int(blank) < V:
+        raise ValueError('%s: blank=%r outside [0, V=%d)' % (who, blank, V))
+    _cuda(logits, labels, enc_len, tgt_len, grad_scale)
+    if logits.dtype != torch.float32 or (grad_scale is not None and grad_scale.dtype != torch.float32):
+        raise L.OtransHipError('%s: logits f32 and grad_scale f32 expected' % who)
+    if U1 > 1 and not (labels.stride(1) == 1 and labels.stride(0) >= U1 - 1):
+        labels = labels.contiguous()
+    loss, nll, valid = RnntLossFn.apply(logits, labels, _len32(enc_len), _len32(tgt_len), int(blank), grad_scale)
+    return loss, {'nll': nll, 'valid': valid}
+
+
+class RnntJointFn(torch.autograd.Function):
+    """The transducer's joint activation z[b,t,u,:] = tanh(pe[b,t,:] + pg[b,u,:]) inside the lengths, zeros outside (include/otrans_hip.h
+    otr_rnnt_joint_fwd) -> (z f32 [B, T, U1, J], its 16-bit twin or None).  Backward (otr_rnnt_joint_bwd): dpe = sum_u dz (1 - z^2),
+    dpg = sum_t dz (1 - z^2), two launches that each read dz and z once; what lies outside the lengths is never read."""
+
+    @staticmethod
+    def forward(ctx, pe, pg, enc_len, tgt_len):
+        B, T, J = pe.shape
+        U1 = pg.shape[1]
+        z = torch.empty((B, T, U1, J), dtype=torch.float32, device=pe.device)
+        z16 = torch.empty((B, T, U1, J), dtype=_ops.half_dtype(), device=pe.device) if _ops.is_half() else None
+        L.check(_timed('rnnt_joint_fwd %dx%dx%dx%d' % (B, T, U1, J), {'bytes': z.numel() * (6 if z16 is not None else 4)},
+                       lambda: L.load().otr_rnnt_joint_fwd(_p(pe), _p(pg), _p(enc_len), _p(tgt_len), B, T, U1, J, _p(z), _p(z16), _stream())),
+                'otr_rnnt_joint_fwd')
+        ctx.save_for_backward(z, enc_len, tgt_len)
+        if z16 is not None:
+            ctx.mark_non_differentiable(z16)
+        return z, z16
+
+    @staticmethod
+    def backward(ctx, dz, _dz16=None):
+        z, enc_len, tgt_len = ctx.saved_tensors
+        B, T, U1, J = z.shape
+        dz = dz.contiguous().float()
+        dpe = torch.empty((B, T, J), dtype=torch.float32, device=z.device)
+        dpg = torch.empty((B, U1, J), dtype=torch.float32, device=z.device)
+        L.check(_timed('rnnt_joint_bwd %dx%dx%dx%d' % (B, T, U1, J), {'bytes': z.numel() * 16},
+                       lambda: L.load().otr_rnnt_joint_bwd(_p(dz), _p(z), _p(enc_len), _p(tgt_len), B, T, U1, J, _p(dpe), _p(dpg), _stream())),
+                'otr_rnnt_joint_bwd')
+        return dpe, dpg, None, None
+
+
+def rnnt_joint(pe, pg, enc_len, tgt_len):
+    """z = tanh(pe[:, :, None, :] + pg[:, None, :, :]) f32 [B, T, U + 1, J] with its 16-bit twin attached, zeros where t >= enc_len[b] or
+    u > tgt_len[b]; pe f32 [B, T, J] (the encoder projection), pg f32 [B, U + 1, J] (the predictor projection), J a multiple of 4,
+    U + 1 <= RNNT_MAX_TGT + 1.  Autograd to pe and pg."""
+    who = 'rnnt_joint'
+    if pe.dim() != 3 or pg.dim() != 3 or pe.shape[0] != pg.shape[0] or pe.shape[2] != pg.shape[2]:
+        raise ValueError('%s: pe must be [B, T, J] and pg [B, U + 1, J], got %s and %s' % (who, tuple(pe.shape), tuple(pg.shape)))
+    B, T, J = pe.shape
+    U1 = pg.shape[1]
+    if J < 4 or J % 4:
+        raise ValueError('%s: J=%d must be a positive multiple of 4' % (who, J))
+    if U1 > RNNT_MAX_TGT + 1:
+        raise ValueError('%s: U + 1 = %d lattice columns > %d not supported' % (who, U1, RNNT_MAX_TGT + 1))
+    if not 1 <= B <= 65535 or not 1 <= T <= 65535 or U1 < 1 or B * T * U1 >= (1 << 31) - 4:
+        raise ValueError('%s: [B, T, U + 1] = %s need 1 <= B, T <= 65535, U + 1 >= 1 and B*T*(U + 1) < 2^31' % (who, (B, T, U1)))
+    _rnnt_int_vector(who, 'enc_len', enc_len, B)
+    _rnnt_int_vector(who, 'tgt_len', tgt_len, B)
+    _cuda(pe, pg, enc_len, tgt_len)
+    if pe.dtype != torch.float32 or pg.dtype != torch.float32:
+        raise L.OtransHipError('%s: pe and pg must be f32, got %s and %s' % (who, pe.dtype, pg.dtype))
+    z, z16 = RnntJointFn.apply(pe.contiguous(), pg.contiguous(), _len32(enc_len), _len32(tgt_len))
+    return _ops.attach_lp(z, z16)
+
+
+@torch.no_grad()
+def rnnt_greedy(pe, enc_len, predictor_step, output, max_symbols=4, max_len=200, blank=0, bos=1):
+    """Greedy transducer decoding of a batch, all state on the device.  pe f32 [B, T, J]: the joint's encoder projection; enc_len [B].
+    predictor_step(tokens int64 [B, 1], h, c) -> (h', c', pg' f32 [B, J]): one predictor step for all rows from the per-layer state
+    lists h / c (None: the zero state; every h carries its 16-bit twin in the 16-bit modes) to the new lists and the joint's predictor
+    projection.  output(z) -> logits f32 [B, V].  Per step: otr_rnnt_greedy_joint, output, otr_rnnt_greedy_advance (arg-max; a row
+    emits unless the arg-max is blank or max_symbols tokens were already emitted at its frame, else it moves to the next frame),
+    predictor_step on the step's tokens, otr_rnnt_greedy_commit (the candidate state replaces the committed one where a row emitted).
+    At most T + max_len steps; the count of unfinished rows is read on the host every 16th step.  Returns (tokens int64 [B, max_len],
+    lengths int32 [B], scores f32 [B]: the sum of the log-probs of every decision, frames int32 [B, max_len]: the frame of each token)."""
+    who = 'rnnt_greedy'
+    if pe.dim() != 3:
+        raise ValueError('%s: pe must be [B, T, J], got %s' % (who, tuple(pe.shape)))
+    B, T, J = pe.shape
+    if J < 4 or J % 4:
+        raise ValueError('%s: J=%d must be a positive multiple of 4' % (who, J))
+    if not 1 <= B <= 65535 or T < 1:
+        raise ValueError('%s: pe [B, T, J] = %s needs 1 <= B <= 65535 and T >= 1' % (who, (B, T, J)))
+    for name, v in (('max_symbols', max_symbols), ('max_len', max_len)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError('%s: %s=%r must be an integer >= 1' % (who, name, v))
+    _rnnt_int_vector(who, 'enc_len', enc_len, B)
+    _cuda(pe, enc_len)
+    if pe.dtype != torch.float32:
+        raise L.OtransHipError('%s: pe must be f32, got %s' % (who, pe.dtype))
+    pe, dev, lib = pe.contiguous(), pe.device, L.load()
+    half = _ops.is_half()
+    el = _len32(enc_len)
+    i32 = lambda *sh: torch.zeros(sh, dtype=torch.int32, device=dev)      # noqa: E731
+    t, n, cnt, emit, frames = i32(B), i32(B), i32(B), i32(B), i32(B, max_len)
+    tokens = torch.zeros((B, max_len), dtype=torch.int64, device=dev)
+    score = torch.zeros((B,), dtype=torch.float32, device=dev)
+    step_tok = torch.full((B,), int(bos), dtype=torch.int64, device=dev)
+    remaining = (el.clamp(0, T) > 0).sum().to(torch.int32).view(1)
+    h, c, pg = predictor_step(step_tok.view(B, 1), None, None)           # the committed state: the predictor after BOS
+    pg = pg.contiguous()
+
+    def items(hs, cs, g):
+        out = list(hs) + list(cs) + [g]
+        if half:
+            out += [_ops.lp_of(x) for x in hs]
+        return out
+    dst = items(h, c, pg)
+    if any(x is None or not x.is_contiguous() for x in dst):
+        raise L.OtransHipError('%s: predictor_step must return contiguous states (with their 16-bit twins in the 16-bit modes)' % who)
+    # the commit entry takes at most 16 items a call: 3 per layer + 1 in the 16-bit modes, so a deep predictor takes more than one call
+    cuts = [(i, min(i + 16, len(dst))) for i in range(0, len(dst), 16)]
+    nbytes = [(C.c_int32 * (j - i))(*[x.shape[-1] * x.element_size() for x in dst[i:j]]) for i, j in cuts]
+    dst_p = [(C.c_void_p * (j - i))(*[x.data_ptr() for x in dst[i:j]]) for i, j in cuts]
+    z = torch.empty((B, J), dtype=torch.float32, device=dev)
+    z16 = torch.empty((B, J), dtype=_ops.half_dtype(), device=dev) if half else None
+    st = _stream()
+    for step in range(T + max_len):
+        L.check(lib.otr_rnnt_greedy_joint(_p(pe), _p(pg), _p(t), _p(n), _p(el), B, T, J, max_len, _p(z), _p(z16), st), 'otr_rnnt_greedy_joint')
+        logits = output(_ops.attach_lp(z, z16))
+        V = logits.shape[-1]
+        lg, ld = _rows_in_place(logits, V)
+        L.check(lib.otr_rnnt_greedy_advance(_p(lg), ld, _p(el), B, T, V, int(blank), max_symbols, max_len, _p(t), _p(n), _p(cnt), _p(tokens),
+                                            _p(frames), _p(score), _p(emit), _p(step_tok), _p(remaining), st), 'otr_rnnt_greedy_advance')
+        h1, c1, pg1 = predictor_step(step_tok.view(B, 1), h, c)
+        src = items(h1, c1, pg1.contiguous())
+        for k, (i, j) in enumerate(cuts):
+            src_p = (C.c_void_p * (j - i))(*[x.data_ptr() for x in src[i:j]])
+            L.check(lib.otr_rnnt_greedy_commit(_p(emit), src_p, dst_p[k], nbytes[k], j - i, B, st), 'otr_rnnt_greedy_commit')
+        if step % 16 == 15 and int(remaining) == 0:
+            break
+    return tokens, n, score, frames
 
 
 # ------------------------------------------------------------------ knowledge distillation (csrc/distill.hip)

@@ -3394,3 +3394,5 @@ from .loss_ops import *        # noqa: E402,F401,F403
 from .loss_ops import _ls_ticket      # noqa: E402,F401  (tests/test_gpu_round5.py reads ops._ls_ticket)
 # the MWER loss of the CTC model: named here, since tests/test_ops_layout.py pins loss_ops.__all__ to the names it had when it was split off
 from .loss_ops import CtcMwerLossFn, ctc_mwer_loss      # noqa: E402,F401
+# the transducer's wrappers, for the same reason
+from .loss_ops import RNNT_MAX_TGT, RnntJointFn, RnntLossFn, rnnt_greedy, rnnt_joint, rnnt_loss      # noqa: E402,F401

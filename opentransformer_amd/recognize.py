@@ -1359,4 +1359,8 @@ def build_recognizer(model_type, model, lm, args, idx2unit):
                              beam_width=args.beam_width, idx2unit=idx2unit, ngpu=args.ngpu, mode=args.mode,
                              alpha=args.alpha, beta=args.beta, bias=bias, mbr=getattr(args, 'mbr', False),
                              mbr_scale=getattr(args, 'mbr_scale', 1.0))
+    if model_type == 'transducer':
+        from .transducer import TransducerRecognizer          # transducer.py imports this module
+        return TransducerRecognizer(model=model, idx2unit=idx2unit, max_symbols=getattr(args, 'max_symbols', 4),
+                                    max_len=getattr(args, 'max_len', 200), ngpu=getattr(args, 'ngpu', 1))
     raise NotImplementedError
