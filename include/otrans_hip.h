@@ -40,7 +40,7 @@ extern "C" {
  * bump; 602: the rescoring entries, additions only; 603: otr_ctc_align, additions only; 604: otr_ngram_lookup and otr_ctc_beam_search_lm, additions only; 605:
  * otr_edit_distance, additions only; 606: otr_ngram_score_cands, otr_ngram_score_seqs and otr_rescore_select_add, additions only; 607: otr_ngram_count, otr_ngram_stats and otr_ngram_estimate, additions only;
  * 608: otr_mwer_workspace_floats and otr_mwer_loss, additions only; still 608: otr_feature_prepare_workspace_bytes, otr_feature_prepare and
- * otr_cmvn_accumulate, after them otr_ctc_segment_workspace_bytes and otr_ctc_segment, and after those otr_distill_workspace_floats and otr_distill_loss (additions only), after those otr_bias_score_cands and otr_bias_score_seqs (additions only), and otr_ctc_beam_search_bias (an addition only), after them otr_edit_align and otr_nbest_consensus (additions only), after them otr_mixspeech_mix and otr_ctc_loss_pair (additions only), and last otr_ctc_mwer_workspace_floats and otr_ctc_mwer_loss (additions only), were added without a bump -- no existing signature, structure or meaning changed, and a binding that needs them
+ * otr_cmvn_accumulate, after them otr_ctc_segment_workspace_bytes and otr_ctc_segment, and after those otr_distill_workspace_floats and otr_distill_loss (additions only), after those otr_bias_score_cands and otr_bias_score_seqs (additions only), and otr_ctc_beam_search_bias (an addition only), after them otr_edit_align and otr_nbest_consensus (additions only), after them otr_mixspeech_mix and otr_ctc_loss_pair (additions only), after them otr_ctc_mwer_workspace_floats and otr_ctc_mwer_loss (additions only), after them the otr_rnnt_* entries, and last otr_rnnt_beam_joint, otr_rnnt_beam_select and otr_rnnt_beam_gather (additions only), were added without a bump -- no existing signature, structure or meaning changed, and a binding that needs them
  * fails on the missing symbol of an older library when it loads it).  A binding compares otr_version() with the OTR_ABI_VERSION it was written against BEFORE its first call and refuses a
  * library that answers anything else: descriptors are passed by pointer and read at the library's idea of their size. */
 #define OTR_ABI_VERSION 608
@@ -1524,6 +1524,47 @@ int32_t otr_rnnt_greedy_advance(const float* logits, int64_t ld, const int32_t* 
                                 int32_t* frames, float* score, int32_t* emit, int64_t* step_tok, int32_t* remaining, void* stream);
 int32_t otr_rnnt_greedy_commit(const int32_t* emit, const void* const* src, void* const* dst, const int32_t* row_bytes, int32_t n_items,
                                int32_t B, void* stream);
+
+/* ---- the transducer's beam search (csrc/rnntbeam.hip): frame-synchronous, at most one symbol per frame, identical hypotheses merged
+ *      before pruning ("modified beam search").  f32 in both builds.  Rows are R = B * W, slot r belongs to utterance r / W; W <=
+ *      OTR_RNNT_BEAM_MAX, 1 <= max_len <= OTR_RNNT_BEAM_MAX_LEN, R <= 65535.  The beam of an utterance is score f32 [R] (-inf: a dead
+ *      slot), n int32 [R], tokens int64 [R, max_len], frames int32 [R, max_len], held twice: a frame reads one half and writes the other.
+ *      A search starts from slot 0 of every utterance at score 0 and length 0, the others dead.
+ *   One frame t of utterance b, for t < T_b = enc_len[b] clamped to [0, T]: with lp_i = log-softmax of row i of the logits, every live
+ *      slot i (tokens y_i, score s_i) offers its STAY (y_i, s_i + lp_i[blank]) and, if n_i < max_len, for every k != blank the EXTENSION
+ *      (y_i + [k], s_i + lp_i[k]) whose new token carries frame t.  Candidates that name the same sequence are merged before pruning,
+ *      scores combined with logaddexp: live hypotheses are distinct, so only the stay of i and the extension (j, k) with y_i == y_j +
+ *      [k] can meet, one j per i at most; the merged candidate keeps i's frames and predictor state (it is i's stay).  The new beam is
+ *      the W candidates of highest score, best first; equal scores: a stay before an extension, then the lower parent slot, then the
+ *      lower token.  (Two extensions of one slot tie by their LOGITS: two different logits whose f32 scores happen to round to the
+ *      same number keep the order of the logits.)  Slots that no candidate fills are dead (score -inf, n 0).  Nothing is written
+ *      behind a length.
+ * otr_rnnt_beam_joint: z[r,:] = tanh(pe[r / W, t, :] + pg[r,:]) with its 16-bit twin (z16 may be NULL); exact zeros for a slot that is
+ *      dead (score[r] == -inf) or whose utterance has ended (t >= T_b), where pe / pg are not read.  pe f32 [B, T, J], pg f32 [R, J];
+ *      J a multiple of 4; pe, pg, z 16-byte aligned.
+ * otr_rnnt_beam_select: the whole frame above on logits [R, V] (row stride ld >= V, RAW; nothing behind column V is read): one
+ *      workgroup per utterance, one wavefront per slot.  Per new slot, in rank order: parent[r] (the slot of the same utterance, 0 ..
+ *      W - 1, the candidate came from), step_tok[r] (the new token; blank for a stay), emit[r] (1 for an extension), and score, n, tokens,
+ *      frames in the OUT half: the parent's history copied, the new token appended.  A dead output slot gets score -inf, n 0, parent
+ *      = itself, step_tok blank, emit 0.  An utterance with t >= T_b is carried over unchanged into the out half (parent = itself,
+ *      step_tok blank, emit 0).  The partner's score s_j + lp_j[k] of a merge is read from row j of the logits whether or not k is
+ *      among j's W best; if it is, that candidate is removed.  Token histories are compared directly.
+ * otr_rnnt_beam_gather: for every item k < n_items (at most 16) and EVERY row r, dst[k][r] = src[k][(r / W) * W + parent[r]] (rows of
+ *      row_bytes[k] bytes, a multiple of 4): the committed predictor state re-seated onto the new slots.  src / dst / row_bytes are
+ *      HOST arrays as otr_rnnt_greedy_commit takes them; src[k] != dst[k] (the state is double-buffered).
+ *   No atomics: the same bits on every run.  No allocation or host synchronisation.  Refused before any launch: W outside [1,
+ *      OTR_RNNT_BEAM_MAX], R > 65535, max_len outside [1, OTR_RNNT_BEAM_MAX_LEN], J % 4 != 0, V < 2, ld < V, blank outside [0, V),
+ *      t outside [0, T), a NULL pointer other than z16, an in half that is its out half. */
+#define OTR_RNNT_BEAM_MAX 16
+#define OTR_RNNT_BEAM_MAX_LEN 256
+int32_t otr_rnnt_beam_joint(const float* pe, const float* pg, const float* score, const int32_t* enc_len, int32_t B, int32_t W, int32_t T,
+                            int32_t t, int32_t J, float* z, void* z16, void* stream);
+int32_t otr_rnnt_beam_select(const float* logits, int64_t ld, const int32_t* enc_len, int32_t B, int32_t W, int32_t T, int32_t t, int32_t V,
+                             int32_t blank, int32_t max_len, const float* score_in, const int32_t* n_in, const int64_t* tokens_in,
+                             const int32_t* frames_in, float* score_out, int32_t* n_out, int64_t* tokens_out, int32_t* frames_out,
+                             int32_t* parent, int64_t* step_tok, int32_t* emit, void* stream);
+int32_t otr_rnnt_beam_gather(const int32_t* parent, const void* const* src, void* const* dst, const int32_t* row_bytes, int32_t n_items,
+                             int32_t B, int32_t W, void* stream);
 
 #ifdef __cplusplus
 }

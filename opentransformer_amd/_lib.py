@@ -284,6 +284,9 @@ SIGNATURES = {
     'otr_rnnt_greedy_joint': [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P],
     'otr_rnnt_greedy_advance': [_P, _I64, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     'otr_rnnt_greedy_commit': [_P, _P, _P, _P, _I32, _I32, _P],
+    'otr_rnnt_beam_joint': [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P],
+    'otr_rnnt_beam_select': [_P, _I64, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32] + [_P] * 12,
+    'otr_rnnt_beam_gather': [_P, _P, _P, _P, _I32, _I32, _I32, _P],
 }
 _RESTYPE = {'otr_last_error_string': C.c_char_p, 'otr_dec_ffn_hsave_bytes': C.c_int64, 'otr_ffn_split_scratch_bytes': C.c_int64, 'otr_ffn_split_sync_ints': C.c_int64, 'otr_ffn_split_hsave_bytes': C.c_int64,
             'otr_ffn_split_padded_rows': C.c_int64, 'otr_add_layernorm_bwd_partial_rows': C.c_int64,

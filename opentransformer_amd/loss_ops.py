@@ -647,6 +647,121 @@ def rnnt_greedy(pe, enc_len, predictor_step, output, max_symbols=4, max_len=200,
     return tokens, n, score, frames
 
 
+# ------------------------------------------------------------------ the transducer's beam search (csrc/rnntbeam.hip)
+RNNT_BEAM_MAX, RNNT_BEAM_MAX_LEN = 16, 256      # include/otrans_hip.h OTR_RNNT_BEAM_MAX, OTR_RNNT_BEAM_MAX_LEN
+
+
+def rnnt_beam_limits(who, beam_width, max_len):
+    """the limits of the search that need no tensor (TransducerRecognizer checks them in its constructor too)"""
+    for name, v in (('beam_width', beam_width), ('max_len', max_len)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError('%s: %s=%r must be an integer' % (who, name, v))
+    if not 1 <= beam_width <= RNNT_BEAM_MAX:
+        raise ValueError('%s: beam_width=%d must be in [1, %d]' % (who, beam_width, RNNT_BEAM_MAX))
+    if not 1 <= max_len <= RNNT_BEAM_MAX_LEN:
+        raise ValueError('%s: max_len=%d must be in [1, %d]' % (who, max_len, RNNT_BEAM_MAX_LEN))
+
+
+@torch.no_grad()
+def rnnt_beam(pe, enc_len, predictor_step, output, beam_width=4, max_len=200, blank=0, bos=1):
+    """Beam search of the transducer, all state on the device: frame-synchronous, at most ONE symbol per frame, hypotheses that name the
+    same token sequence merged (logaddexp) before pruning -- "modified beam search"; include/otrans_hip.h (otr_rnnt_beam_select)
+    states a frame in full.  pe f32 [B, T, J]: the joint's encoder projection; enc_len [B].  predictor_step and output are
+    rnnt_greedy's callbacks, here on B * W rows (slot r belongs to utterance r // W); the first predictor_step runs on B rows of
+    `bos` and its result is placed in slot 0 of every utterance.  Per frame: otr_rnnt_beam_joint, output, otr_rnnt_beam_select,
+    otr_rnnt_beam_gather (the committed predictor state follows its hypothesis to the new slot, into the other half of a double
+    buffer), predictor_step on the step's tokens, otr_rnnt_greedy_commit (the candidate state replaces the committed one where the slot
+    was extended).  Exactly T iterations; nothing is read back on the way.  Returns (tokens int64 [B, W, max_len], lengths int32
+    [B, W], scores f32 [B, W], frames int32 [B, W, max_len]: the frame of each token), best first; a slot that never became live has
+    score -inf and length 0, and everything behind a length is 0.
+    The score is the log of the summed probability of the alignments the search kept.  It is NOT rnnt_greedy's score: greedy pays a
+    blank to leave a frame after an emission, this search moves to the next frame with every candidate, stay or extension.  For
+    the same reason beam_width=1 -- one-symbol-per-frame arg-max decoding -- is not rnnt_greedy at max_symbols=1: after an emission
+    greedy looks at the same frame again (and is forced to take its blank), this search does not.
+    Everything that can be judged from the arguments is refused before the device is touched.  V is known only from what `output`
+    returns, so V >= 2 and blank < V are checked on the first frame's logits: behind the first joint launch and the first `output`,
+    in front of the first select launch (whose entry refuses the same)."""
+    who = 'rnnt_beam'
+    if pe.dim() != 3:
+        raise ValueError('%s: pe must be [B, T, J], got %s' % (who, tuple(pe.shape)))
+    B, T, J = pe.shape
+    if J < 4 or J % 4:
+        raise ValueError('%s: J=%d must be a positive multiple of 4' % (who, J))
+    rnnt_beam_limits(who, beam_width, max_len)
+    if int(blank) < 0:
+        raise ValueError('%s: blank=%r must be >= 0' % (who, blank))
+    W = beam_width
+    R = B * W
+    if B < 1 or T < 1 or R > 65535:
+        raise ValueError('%s: pe [B, T, J] = %s at beam_width=%d needs B, T >= 1 and B * beam_width <= 65535 rows' % (who, (B, T, J), W))
+    _rnnt_int_vector(who, 'enc_len', enc_len, B)
+    _cuda(pe, enc_len)
+    if pe.dtype != torch.float32:
+        raise L.OtransHipError('%s: pe must be f32, got %s' % (who, pe.dtype))
+    pe, dev, lib = pe.contiguous(), pe.device, L.load()
+    half = _ops.is_half()
+    el = _len32(enc_len)
+    # the beam, twice: frame t reads half t & 1 and writes the other
+    score = [torch.full((R,), float('-inf'), dtype=torch.float32, device=dev) for _ in range(2)]
+    score[0].view(B, W)[:, 0] = 0.0
+    n = [torch.zeros((R,), dtype=torch.int32, device=dev) for _ in range(2)]
+    tokens = [torch.zeros((R, max_len), dtype=torch.int64, device=dev) for _ in range(2)]
+    frames = [torch.zeros((R, max_len), dtype=torch.int32, device=dev) for _ in range(2)]
+    parent, emit = (torch.zeros((R,), dtype=torch.int32, device=dev) for _ in range(2))
+    step_tok = torch.full((R,), int(blank), dtype=torch.int64, device=dev)
+    h0, c0, pg0 = predictor_step(torch.full((B, 1), int(bos), dtype=torch.int64, device=dev), None, None)
+    nl = len(h0)
+
+    def items(hs, cs, g):
+        out = list(hs) + list(cs) + [g]
+        if half:
+            out += [_ops.lp_of(x) for x in hs]
+        return out
+    first = items(h0, c0, pg0.contiguous())
+    if any(x is None or not x.is_contiguous() or x.dim() != 2 or x.shape[0] != B for x in first):
+        raise L.OtransHipError('%s: predictor_step must return contiguous [rows, width] states (with their 16-bit twins in the 16-bit modes)' % who)
+    # the committed predictor state, twice, on R rows: the state after BOS sits in slot 0 of every utterance
+    state = [[torch.zeros((R, x.shape[1]), dtype=x.dtype, device=dev) for x in first] for _ in range(2)]
+    for buf, x in zip(state[0], first):
+        buf.view(B, W, -1)[:, 0] = x
+
+    def lists(bufs):
+        hs = [_ops.attach_lp(bufs[k], bufs[2 * nl + 1 + k]) if half else bufs[k] for k in range(nl)]
+        return hs, bufs[nl:2 * nl], bufs[2 * nl]
+    # the gather and commit entries take at most 16 items a call: 3 per layer + 1 in the 16-bit modes, so a deep predictor takes more
+    cuts = [(i, min(i + 16, len(first))) for i in range(0, len(first), 16)]
+    nbytes = [(C.c_int32 * (j - i))(*[x.shape[1] * x.element_size() for x in first[i:j]]) for i, j in cuts]
+    ptrs = [[(C.c_void_p * (j - i))(*[x.data_ptr() for x in state[s][i:j]]) for i, j in cuts] for s in range(2)]
+    z = torch.empty((R, J), dtype=torch.float32, device=dev)
+    z16 = torch.empty((R, J), dtype=_ops.half_dtype(), device=dev) if half else None
+    st = _stream()
+    for t in range(T):
+        cur, nxt = t & 1, 1 - (t & 1)
+        h, c, pg = lists(state[cur])
+        L.check(lib.otr_rnnt_beam_joint(_p(pe), _p(pg), _p(score[cur]), _p(el), B, W, T, t, J, _p(z), _p(z16), st), 'otr_rnnt_beam_joint')
+        logits = output(_ops.attach_lp(z, z16))
+        V = logits.shape[-1]
+        if t == 0 and (V < 2 or not 0 <= int(blank) < V):
+            raise ValueError('%s: V=%d must be >= 2 and blank=%r inside [0, V)' % (who, V, blank))
+        lg, ld = _rows_in_place(logits, V)
+        L.check(lib.otr_rnnt_beam_select(_p(lg), ld, _p(el), B, W, T, t, V, int(blank), max_len, _p(score[cur]), _p(n[cur]), _p(tokens[cur]),
+                                         _p(frames[cur]), _p(score[nxt]), _p(n[nxt]), _p(tokens[nxt]), _p(frames[nxt]), _p(parent),
+                                         _p(step_tok), _p(emit), st), 'otr_rnnt_beam_select')
+        for k, (i, j) in enumerate(cuts):
+            L.check(lib.otr_rnnt_beam_gather(_p(parent), ptrs[cur][k], ptrs[nxt][k], nbytes[k], j - i, B, W, st), 'otr_rnnt_beam_gather')
+        h, c, _ = lists(state[nxt])
+        h1, c1, pg1 = predictor_step(step_tok.view(R, 1), h, c)
+        src = items(h1, c1, pg1.contiguous())
+        for k, (i, j) in enumerate(cuts):
+            src_p = (C.c_void_p * (j - i))(*[x.data_ptr() for x in src[i:j]])
+            L.check(lib.otr_rnnt_greedy_commit(_p(emit), src_p, ptrs[nxt][k], nbytes[k], j - i, R, st), 'otr_rnnt_greedy_commit')
+    fin = T & 1
+    # a slot may hold a shorter hypothesis than the one it held two frames ago: what that left behind the length is cleared once, here
+    behind = torch.arange(max_len, device=dev).view(1, -1) >= n[fin].view(-1, 1)
+    return (tokens[fin].masked_fill_(behind, 0).view(B, W, max_len), n[fin].view(B, W), score[fin].view(B, W),
+            frames[fin].masked_fill_(behind, 0).view(B, W, max_len))
+
+
 # ------------------------------------------------------------------ knowledge distillation (csrc/distill.hip)
 DISTILL_MAX_V, DISTILL_MAX_K = 8192, 128
 

@@ -3396,3 +3396,4 @@ from .loss_ops import _ls_ticket      # noqa: E402,F401  (tests/test_gpu_round5.
 from .loss_ops import CtcMwerLossFn, ctc_mwer_loss      # noqa: E402,F401
 # the transducer's wrappers, for the same reason
 from .loss_ops import RNNT_MAX_TGT, RnntJointFn, RnntLossFn, rnnt_greedy, rnnt_joint, rnnt_loss      # noqa: E402,F401
+from .loss_ops import RNNT_BEAM_MAX, RNNT_BEAM_MAX_LEN, rnnt_beam, rnnt_beam_limits      # noqa: E402,F401

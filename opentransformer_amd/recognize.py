@@ -508,22 +508,26 @@ def _mbr_args(who, mbr, mbr_scale, beam_width):
     return bool(mbr), mbr_scale
 
 
-def _consensus_nbest(tokens, lengths, scores, scale, mbr, n, eos):
+def _consensus_nbest(tokens, lengths, scores, scale, mbr, n, eos, follow=None):
     """The consensus of a final beam (tokens [B, W, L], lengths [B, W], scores [B, W], best score first) and the n-best it leaves:
     ordered by ascending risk where `mbr` (a stable sort: ties keep the higher score, then the lower rank; dead slots, of risk +inf,
     last), as it stands otherwise.  -> (tokens [B, n, L], lengths [B, n], scores [B, n], conf f32 [B, L] and post f32 [B] of the
     1-best).  Only the first ops.NBEST_MAX_LEN columns go into the consensus: a longer hypothesis is a dead slot there.  No host
-    synchronisation."""
+    synchronisation.  follow: a tensor [B, W, L] that belongs to the tokens (the transducer's frames); it is cut and permuted as
+    they are and returned as a sixth element."""
     L_ = tokens.size(-1)
     post, risk, _, conf = ops.nbest_consensus(tokens[:, :, :ops.NBEST_MAX_LEN], lengths, scores, scale=scale, eos=eos)
     if conf.size(-1) < L_:
         conf = torch.nn.functional.pad(conf, (0, L_ - conf.size(-1)))
     if not mbr:
-        return tokens[:, :n], lengths[:, :n], scores[:, :n], conf[:, 0], post[:, 0]
+        out = (tokens[:, :n], lengths[:, :n], scores[:, :n], conf[:, 0], post[:, 0])
+        return out if follow is None else out + (follow[:, :n],)
     order = torch.sort(risk, dim=-1, stable=True)[1][:, :n]
     first = order[:, :1]
-    return (torch.gather(tokens, 1, order.unsqueeze(-1).expand(-1, -1, L_)), torch.gather(lengths, 1, order), torch.gather(scores, 1, order),
-            torch.gather(conf, 1, first.unsqueeze(-1).expand(-1, -1, L_))[:, 0], torch.gather(post, 1, first)[:, 0])
+    wide = order.unsqueeze(-1).expand(-1, -1, L_)
+    out = (torch.gather(tokens, 1, wide), torch.gather(lengths, 1, order), torch.gather(scores, 1, order),
+           torch.gather(conf, 1, first.unsqueeze(-1).expand(-1, -1, L_))[:, 0], torch.gather(post, 1, first)[:, 0])
+    return out if follow is None else out + (torch.gather(follow, 1, wide),)
 
 
 class SpeechToTextRecognizer(Recognizer):
@@ -1362,5 +1366,8 @@ def build_recognizer(model_type, model, lm, args, idx2unit):
     if model_type == 'transducer':
         from .transducer import TransducerRecognizer          # transducer.py imports this module
         return TransducerRecognizer(model=model, idx2unit=idx2unit, max_symbols=getattr(args, 'max_symbols', 4),
-                                    max_len=getattr(args, 'max_len', 200), ngpu=getattr(args, 'ngpu', 1))
+                                    max_len=getattr(args, 'max_len', 200), ngpu=getattr(args, 'ngpu', 1),
+                                    mode=getattr(args, 'mode', 'greedy'), beam_width=getattr(args, 'beam_width', 4),
+                                    nbest=getattr(args, 'nbest', 1), mbr=getattr(args, 'mbr', False),
+                                    mbr_scale=getattr(args, 'mbr_scale', 1.0))
     raise NotImplementedError

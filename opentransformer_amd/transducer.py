@@ -15,7 +15,7 @@ import torch.nn as nn
 from . import ops
 from .model import AcousticModel, BuildEncoder, BuildFrontEnd, End2EndModel
 from .nn import BLK, BOS
-from .recognize import Recognizer
+from .recognize import Recognizer, _consensus_nbest, _mbr_args
 
 
 class TransducerPredictor(nn.Module):
@@ -136,28 +136,110 @@ End2EndModel['transducer'] = TransducerModel
 class TransducerRecognizer(Recognizer):
     """Greedy frame-synchronous decoding (ops.rnnt_greedy): at every frame the arg-max of the joint is emitted and fed back to the
     predictor until it is blank or `max_symbols` tokens came out of that frame; a hypothesis ends with its frames or at `max_len`
-    tokens.  The score is the sum of the log-probs of every decision, blanks included."""
+    tokens.  The score is the sum of the log-probs of every decision, blanks included.
+    mode 'beam': ops.rnnt_beam at `beam_width` -- frame-synchronous with at most ONE symbol per frame, identical hypotheses merged
+    before pruning; the 1-best everywhere, the `nbest` best from recognize_tokens.  Its score is the log of the summed probability
+    of the alignments the search kept, not greedy's score: greedy pays a blank to leave a frame after an emission, the beam does
+    not.  beam_width=1 is one-symbol-per-frame arg-max decoding, which is not mode 'greedy' at max_symbols=1 either: after an
+    emission greedy looks at the same frame again and is forced to its blank, the beam moves on.  max_symbols keeps its meaning
+    in greedy mode and is unused in beam mode; beam mode takes max_len up to ops.RNNT_BEAM_MAX_LEN.  beam_width and nbest are unused
+    and unchecked in greedy mode (an args namespace shared with the other recognizers builds the greedy recognizer it always built):
+    greedy decoding has one hypothesis, and recognize_tokens returns that one.
+    mbr=True (beam mode only): the beam_width hypotheses of the search are re-ordered by ascending risk under softmax(mbr_scale *
+    score), as the other recognizers do, and the 1-best everywhere is the hypothesis of least risk; the frames follow the same
+    permutation.  recognize_with_confidence gives the 1-best's tokens the posterior mass that agrees with them (beam mode only)."""
 
-    def __init__(self, model, idx2unit=None, max_symbols=4, max_len=200, ngpu=1):
+    def __init__(self, model, idx2unit=None, max_symbols=4, max_len=200, ngpu=1, mode='greedy', beam_width=4, nbest=1, mbr=False,
+                 mbr_scale=1.0):
         super().__init__(model, idx2unit, None, None, ngpu)
         if not isinstance(model, TransducerModel):
             raise TypeError('TransducerRecognizer: model must be a TransducerModel, not %s' % type(model).__name__)
+        if mbr and mode != 'beam':
+            raise ValueError("TransducerRecognizer: mbr=True needs mode='beam': greedy decoding has no beam to take a consensus of")
+        if mode not in ('greedy', 'beam'):
+            raise NotImplementedError("TransducerRecognizer mode '%s': 'greedy' and 'beam' are built" % mode)
         self.max_symbols, self.max_len = int(max_symbols), int(max_len)
+        self.mode, self.beam_width, self.nbest = mode, int(beam_width), int(nbest)
+        if mode == 'beam':                                  # greedy mode ignores beam_width and nbest, whatever they are
+            if not 1 <= self.beam_width <= ops.RNNT_BEAM_MAX:
+                raise ValueError('TransducerRecognizer: beam_width=%d must be in [1, %d]' % (self.beam_width, ops.RNNT_BEAM_MAX))
+            if not 1 <= self.nbest <= self.beam_width:
+                raise ValueError('TransducerRecognizer: nbest=%d must be in [1, beam_width=%d]' % (self.nbest, self.beam_width))
+            ops.rnnt_beam_limits('TransducerRecognizer', self.beam_width, self.max_len)
+        self.mbr, self.mbr_scale = _mbr_args('TransducerRecognizer', mbr, mbr_scale, self.beam_width)
 
-    @torch.no_grad()
-    def _decode(self, inputs, inputs_mask):
-        """(tokens int64 [B, L], lengths int32 [B], scores f32 [B], frames int32 [B, L]) on the device"""
+    def _project(self, inputs, inputs_mask):
         x, mask, _ = self.model.frontend.inference(inputs, inputs_mask, None)
         memory, memory_mask, _ = self.model.encoder(x, mask)
         memory_length = torch.sum(memory_mask.squeeze(1) if memory_mask.dim() == 3 else memory_mask, dim=-1)
-        pe = self.model.joint.project_encoder(memory)
-        return ops.rnnt_greedy(pe, memory_length.to(torch.int32), self.model.predictor_step, self.model.joint.logits,
+        return self.model.joint.project_encoder(memory), memory_length.to(torch.int32)
+
+    @torch.no_grad()
+    def _beam_search(self, inputs, inputs_mask):
+        """the search's own beam, best score first: (tokens int64 [B, W, L], lengths int32 [B, W], scores f32 [B, W], frames int32
+        [B, W, L]) on the device"""
+        pe, memory_length = self._project(inputs, inputs_mask)
+        return ops.rnnt_beam(pe, memory_length, self.model.predictor_step, self.model.joint.logits, beam_width=self.beam_width,
+                             max_len=self.max_len, blank=BLK, bos=BOS)
+
+    def _beam(self, inputs, inputs_mask, n):
+        """the n best of the beam with their frames, and the consensus of the whole beam: (tokens [B, n, L], lengths [B, n], scores
+        [B, n], frames [B, n, L], conf [B, L], post [B]); in ascending order of risk with mbr=True, by score otherwise"""
+        tokens, lengths, scores, frames = self._beam_search(inputs, inputs_mask)
+        tok, ln, sc, conf, post, fr = _consensus_nbest(tokens, lengths, scores, self.mbr_scale, self.mbr, n, -1, follow=frames)
+        return tok, ln, sc, fr, conf, post
+
+    @torch.no_grad()
+    def _decode(self, inputs, inputs_mask):
+        """(tokens int64 [B, L], lengths int32 [B], scores f32 [B], frames int32 [B, L]) of the 1-best, on the device"""
+        if self.mode == 'beam':
+            if self.mbr:
+                tokens, lengths, scores, frames = self._beam(inputs, inputs_mask, 1)[:4]
+            else:
+                tokens, lengths, scores, frames = self._beam_search(inputs, inputs_mask)
+            return tokens[:, 0], lengths[:, 0], scores[:, 0], frames[:, 0]
+        pe, memory_length = self._project(inputs, inputs_mask)
+        return ops.rnnt_greedy(pe, memory_length, self.model.predictor_step, self.model.joint.logits,
                                max_symbols=self.max_symbols, max_len=self.max_len, blank=BLK, bos=BOS)
 
     def recognize_tokens(self, inputs, inputs_mask):
-        """(tokens int64 [B, 1, L], lengths int32 [B, 1], scores f32 [B, 1]) for ops.edit_distance / evaluate.evaluate"""
+        """(tokens int64 [B, N, L], lengths int32 [B, N], scores f32 [B, N]) for ops.edit_distance / evaluate.evaluate: N = 1 in greedy
+        mode, nbest in beam mode (in ascending order of risk with mbr=True)"""
+        if self.mode == 'beam':
+            if self.mbr:
+                return self._beam(inputs, inputs_mask, self.nbest)[:3]
+            tokens, lengths, scores, _ = self._beam_search(inputs, inputs_mask)
+            return tokens[:, :self.nbest], lengths[:, :self.nbest], scores[:, :self.nbest]
         tokens, lengths, scores, _ = self._decode(inputs, inputs_mask)
         return tokens.unsqueeze(1), lengths.unsqueeze(1), scores.unsqueeze(1)
+
+    @torch.no_grad()
+    def recognize_tokens_with_confidence(self, inputs, inputs_mask):
+        """recognize_tokens() narrowed to the 1-best plus the consensus of the search's beam_width hypotheses (ops.nbest_consensus at
+        mbr_scale), on the device: (tokens [B, 1, L], lengths [B, 1], scores [B, 1] of the 1-best -- the hypothesis of least risk with
+        mbr=True --, conf f32 [B, L]: per token the posterior mass of the hypotheses whose alignment matches it, post f32 [B]: the
+        1-best's own posterior)."""
+        if self.mode != 'beam':
+            raise ValueError("TransducerRecognizer: confidences need mode='beam': greedy decoding has no beam to take a consensus of")
+        tokens, lengths, scores, _, conf, post = self._beam(inputs, inputs_mask, 1)
+        return tokens, lengths, scores, conf, post
+
+    @torch.no_grad()
+    def recognize_with_confidence(self, inputs, inputs_mask):
+        """recognize() with token confidences: (texts, confidences: per utterance [(unit, confidence), ...] for the 1-best, its units
+        read in order being the words of its text as in recognize_with_times, utt_posterior: the 1-best's posterior, a host tensor [B])"""
+        tokens, lengths, _, conf, post = self.recognize_tokens_with_confidence(inputs, inputs_mask)
+        preds, conf = self._lists(tokens[:, 0], lengths[:, 0]), conf.cpu()
+        confidences = []
+        for b, pred in enumerate(preds):
+            items = []
+            for k, t in enumerate(pred):                   # translate()'s walk: a list ends before its first EOS and skips PAD
+                if t == BOS:
+                    break
+                if t != BLK:
+                    items.append((self.idx2unit[t], float(conf[b, k])))
+            confidences.append(items)
+        return self.translate(preds), confidences, post.cpu()
 
     def _lists(self, tokens, lengths):
         tok, n = tokens.cpu(), lengths.cpu()
